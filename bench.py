@@ -8,10 +8,16 @@ A "step" is one pass of the hot path over one batch of synthetic queries:
     merge kernel when --gpus > 1, mode "shard").
 Inputs (corpus rows, graph, queries) are resident in HBM before the timed region.
 
-Without --workload (the driver's command shape) and N = 1: the headline workload runs first (a child process, --headline-only), then
-compact legs of every other 1-GPU BASELINE config — configs[1] hnsw1m at ef = 128, configs[2] exhaustive recompute and the
-recompute-on graph (throughput batch and batch 64), configs[4] DiskANN R = 32 at 1536-d WITH the hybrid leg — each its own process,
-and ONE line comes out: the headline's plus `other_configs` (LEANN_BENCH_BUDGET_S bounds the whole run, default 420 s).
+A plain run (`--gpus 1 --steps K --warmup W`, the driver's command shape) does only what the headline figure needs: it generates the
+corpus and builds the index in HBM, measures the recall that picks ef, warms up, times the K steps, writes the last step's results if
+--dump-outputs DIR is given, and prints the line.
+--full adds everything else: the CPU baseline, the single-query latency / 64-caller section, the PCIe-inclusive rate and (N > 1) the
+replica curve; and without --workload (N = 1) the headline workload runs first (a child process, --headline-only), then compact legs of
+every other 1-GPU BASELINE config — configs[1] hnsw1m at ef = 128, configs[2] exhaustive recompute and the recompute-on graph
+(throughput batch and batch 64), configs[4] DiskANN R = 32 at 1536-d WITH the hybrid leg — each its own process, and ONE line comes
+out: the headline's plus `other_configs` (LEANN_BENCH_BUDGET_S bounds the whole run, default 420 s).
+--dump-outputs DIR: after the timed steps, the arrays the last step handed its caller (ids, distances or scores, counts) go to
+DIR/<name>.npy as float64 / float32; the inputs are seeded, so equal arguments give equal inputs from run to run.
 --hybrid (graph workloads): every step is search(fetch_k = 5 k) + BM25 injection + hybrid_rerank on the device (csrc/hybrid.hip).
 
 N > 1: `python bench.py --gpus N` starts `python -m torch.distributed.run --nproc-per-node N ... bench.py` itself as a child process
@@ -97,6 +103,53 @@ def emit(out):
         os.write(_REAL_STDOUT, line)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array of `arrays` (host numpy, first axis = queries), ids and counts as float64 (exact
+    below 2^53; an empty slot's UINT64_MAX id reads -1), f32 values as float32.  Past 64 MB in all, a fixed seeded sample of query rows
+    is written instead, their indices as query_rows.npy."""
+    os.makedirs(dirpath, exist_ok=True)
+    out = {name: np.asarray(a).astype(np.float32 if np.asarray(a).dtype == np.float32 else np.float64) for name, a in arrays.items()}
+    n = next(iter(out.values())).shape[0]
+    per_row = sum(a.nbytes for a in out.values()) / max(1, n) + 8
+    qr = os.path.join(dirpath, "query_rows.npy")
+    if n * per_row > DUMP_LIMIT_BYTES:
+        keep = int((DUMP_LIMIT_BYTES - 4096 * (len(out) + 1)) // per_row)  # (+ one .npy header per file)
+        rows = np.sort(np.random.default_rng(0x5EED0007).choice(n, keep, replace=False))
+        out = {name: a[rows] for name, a in out.items()}
+        out["query_rows"] = rows.astype(np.float64)
+    elif os.path.exists(qr):
+        os.remove(qr)  # left by an earlier, sampled dump into the same directory
+    for name, a in out.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+
+
+def in_background(fn):
+    """fn() on a host thread of its own (the library's calls release the GIL); the returned join() gives (result, seconds) or raises
+    fn's error"""
+    import threading
+    box = {}
+
+    def run():
+        t0 = time.time()
+        try:
+            box["value"] = fn()
+        except BaseException as e:  # noqa: BLE001  (raised again by join)
+            box["error"] = e
+        box["s"] = time.time() - t0
+    th = threading.Thread(target=run, name="index-build")
+    th.start()
+
+    def join():
+        th.join()
+        if "error" in box:
+            raise box["error"]
+        return box["value"], box["s"]
+    return join
+
+
 def host_cores():
     """threads this process may really use: affinity mask capped by the cgroup CPU quota"""
     n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
@@ -162,8 +215,8 @@ def bench_recompute(args, wl, la, L, chk, dev, local_rank, world, rank, dist, lo
         if shard:
             with torch.cuda.stream(stream):
                 gk, gs, gc = exchange_topk(keys, scores, counts, world)
-                return hip_merge(gk, gs, gc, k, True, stream.cuda_stream)[0]
-        return keys
+                return hip_merge(gk, gs, gc, k, True, stream.cuda_stream)
+        return keys, scores, counts
 
     # recall@10 measured in-run, not assumed: the reference's literal order — materialise every embedding (recompute.rs:86-93), then
     # dot + sort + take (:96-109) — as leann_recompute_encode_device + leann_scan_topk_device over the same rows, against the fused search
@@ -193,7 +246,7 @@ def bench_recompute(args, wl, la, L, chk, dev, local_rank, world, rank, dist, lo
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for s_ in range(steps):
-        step(s_)
+        last = step(s_)
     stream.synchronize()
     torch.cuda.synchronize()
     if dist is not None:
@@ -204,6 +257,8 @@ def bench_recompute(args, wl, la, L, chk, dev, local_rank, world, rank, dist, lo
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"keys": last[0].cpu().numpy(), "scores": last[1].cpu().numpy(), "counts": last[2].cpu().numpy()})
     enc_ms, sc_ms, tk_ms = [float(np.mean([t[i] for t in tm])) for i in range(3)]
     # fused kernel: encode GEMM F[N x h] W[h x d] + feature-space scoring F (W Q^T) as three bf16 pieces (hi/lo/lo2)
     enc_flops, sc_flops = 2.0 * rows * h * d, 3 * 2.0 * rows * h * ((B + 31) // 32 * 32)  # one encode shared by the batch; a G tile per 32 queries
@@ -237,7 +292,7 @@ def bench_recompute(args, wl, la, L, chk, dev, local_rank, world, rank, dist, lo
     if shard:
         out["shard_searches_per_s"] = B * steps * world / elapsed
     # ---- CPU baseline: the oracle's literal recompute.rs:86-109 (embed every passage, dot, sort) on a bounded sample -------
-    if world == 1 and rank == 0 and not args.no_cpu_baseline and allow is None:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline and allow is None:
         try:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import pyoracle as po
@@ -313,6 +368,8 @@ def bench_scan(args, wl, la, L, chk, dev, local_rank, world, rank, dist, log):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"keys": keys.cpu().numpy(), "scores": scores.cpu().numpy(), "counts": counts.cpu().numpy()})
     step_s = elapsed / steps
     nbytes, flops = rows * d * 4.0, 2.0 * rows * d * B
     out = {"metric": "queries/sec @ recall@10>=0.95", "value": B * steps * world / elapsed, "unit": "queries/s", "n_gpus": world,
@@ -330,7 +387,7 @@ def bench_scan(args, wl, la, L, chk, dev, local_rank, world, rank, dist, log):
     if (2.0 * B) / 4.0 < F32_MFMA_PEAK_TFLOPS * 1e12 / (HBM_PEAK_GBS * 1e9):  # small batches: HBM-bound
         r_ = out["roofline"]
         r_.update({"bound": "hbm", "achieved": r_["hbm_gbps"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": r_["hbm_frac"]})
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:  # CPU baseline: the oracle's literal dot + stable sort + take on the host cores
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:  # CPU baseline: the oracle's literal dot + stable sort + take on the host cores
         try:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import pyoracle as po
@@ -439,12 +496,12 @@ def self_launch(args, argv, run=None):
 
 # compact legs of the other 1-GPU BASELINE configs: (name, argv, rough seconds on an MI355X box incl. corpus generation and index build)
 OTHER_CONFIGS = [
-    ("hnsw1m_ef128", ["--workload", "hnsw1m", "--ef", "128", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-latency"], 25),
-    ("recompute10m_exhaustive_batch64", ["--workload", "recompute10m", "--steps", "10", "--warmup", "2", "--no-cpu-baseline"], 40),
+    ("hnsw1m_ef128", ["--workload", "hnsw1m", "--ef", "128", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-latency", "--full"], 25),
+    ("recompute10m_exhaustive_batch64", ["--workload", "recompute10m", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--full"], 40),
     ("recompute10m_graph", ["--workload", "recompute10m_graph", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-latency",
-                            "--small-batch", "64"], 70),
+                            "--small-batch", "64", "--full"], 70),
     ("vamana10m1536_r32_hybrid", ["--workload", "vamana10m1536_r32", "--hybrid", "--steps", "10", "--warmup", "2", "--no-latency",
-                                  "--cpu-queries", "1024"], 170),
+                                  "--cpu-queries", "1024", "--full"], 170),
 ]
 
 
@@ -473,9 +530,9 @@ def summarise_leg(j):
 
 
 def run_all_configs(args, argv, run=None):
-    """Default run: the headline workload (a child with --headline-only and the caller's flags), then compact legs of configs[1], [2]
-    and [4] while the time budget lasts (LEANN_BENCH_BUDGET_S, default 420 s), one JSON line in the end: the headline's line plus
-    `other_configs`.  Returns the exit code (the headline's)."""
+    """--full run without --workload: the headline workload (a child with --headline-only and the caller's flags), then compact legs of
+    configs[1], [2] and [4] while the time budget lasts (LEANN_BENCH_BUDGET_S, default 420 s), one JSON line in the end: the headline's
+    line plus `other_configs`.  Returns the exit code (the headline's)."""
     import subprocess
     me = os.path.abspath(__file__)
     t_start = time.time()
@@ -541,8 +598,15 @@ def main():
                     help="N > 1, modes shard / composite: STRONG scaling — the workload's rows are the WHOLE corpus, split N ways (rows / N per GPU), instead of "
                          "rows per GPU (weak scaling, the default).  SURVEY.md §8e: every GPU still processes every query, so expect little gain.")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the workload itself.  Without it (and without --workload) the default run measures the headline AND compact legs "
+                    help="only the workload itself.  Without it (and without --workload) a --full run measures the headline AND compact legs "
                          "of every other 1-GPU BASELINE config, each in a child process, and reports them under `other_configs` of the one line")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the CPU baseline, the single-query latency / 64-caller section, the "
+                         "PCIe-inclusive rate, (N > 1) the replica curve, and without --workload (N = 1) the other 1-GPU BASELINE configs.  "
+                         "Without it a run sets up, warms up, times the K steps and prints its line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step handed its caller (ids, distances or scores, counts) as "
+                         "DIR/<name>.npy (float64 / float32; a fixed seeded sample of the queries past 64 MB)")
     ap.add_argument("--small-batch", type=int, default=0,
                     help="graph workloads: also time calls of this many queries (BASELINE configs[2] names batch-64) on the same index -> `small_batch`")
     ap.add_argument("--hybrid", action="store_true",
@@ -565,9 +629,9 @@ def main():
     if args.clusters is not None:
         GEN_CLUSTERS = int(args.clusters)
     explicit_workload = any(x == "--workload" or x.startswith("--workload=") for x in sys.argv[1:])
-    if args.gpus == 1 and "WORLD_SIZE" not in os.environ and not explicit_workload and not args.headline_only:
-        # the driver's command shape (`python bench.py --gpus 1 --steps K --warmup W`): headline + every other 1-GPU BASELINE config.
-        # This parent never touches the GPU; every leg is a child process of its own.
+    if args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not explicit_workload and not args.headline_only:
+        # `python bench.py --gpus 1 --full`: headline + every other 1-GPU BASELINE config.  This parent never touches the GPU; every leg
+        # is a child process of its own.  (Without --full the driver's command shape runs the headline workload in this process.)
         sys.exit(run_all_configs(args, sys.argv[1:]))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and args.mode != "composite":
         # `python bench.py --gpus N` without a launcher (the driver's command shape): this process has not touched the GPU yet, so
@@ -641,6 +705,7 @@ def main():
     q_first = 0 if (shard or world == 1) else rank * n_pool * B
     t0 = time.time()
     Xs, keep = [], []
+    build = None
     if composite:
         # ONE process, G devices: shard g's rows (or features) live on device g, one sub-index with its own graph per device, all of them
         # behind one composite leann_backend handle whose searches fan out, peer-copy the per-shard lists to device 0 and merge there
@@ -704,15 +769,12 @@ def main():
             chk(L.leann_synth_rows_device(SEED, d, ld, GEN_R, GEN_CLUSTERS, GEN_SIGMA, 0, row0, rows, X.data_ptr(), sp))
         stream.synchronize()
         log(f"rank {rank}: corpus rows [{row0}, {row0 + rows}) x {d} generated in {time.time() - t0:.1f}s")
-        t0 = time.time()
-        searcher = la.BackendSearcher.build_device(backend, X.data_ptr(), rows, d, ld, M, efc, device=local_rank,
-                                                   key_offset=row0)
-    torch.cuda.synchronize()
-    build_s = time.time() - t0
-    gi = subs[0].graph_info() if (composite and rgraph) else searcher.graph_info()
-    if composite:  # the composite handle carries n and dims only: degrees are the build's
-        gi = dict(gi, M=M, M0=(M if backend else 2 * M))
-    log(f"rank {rank}: index built on GPU in {build_s:.1f}s ({rows * G / build_s:.0f} rows/s), max_level={gi['max_level']}")
+        # built on a host thread of its own, started just before the exact ground truth below, which only reads the rows too: the
+        # two overlap instead of following each other
+        build = lambda: la.BackendSearcher.build_device(backend, X.data_ptr(), rows, d, ld, M, efc, device=local_rank, key_offset=row0)
+    if build is None:
+        torch.cuda.synchronize()
+        build_s = time.time() - t0
 
     # ---- queries: a pool of distinct batches, same on every rank in shard mode --------------------
     Q = torch.empty((n_pool * B, ld), dtype=torch.float32, device=dev)
@@ -747,25 +809,6 @@ def main():
     stream.synchronize()
     group, tickets = None, [None, None]
     rccl = shard and dist.get_backend() == "nccl"
-    if rccl:
-        # one RCCL communicator of the LIBRARY's own: local traversal, ncclAllGather of the packed per-shard block, merge kernel
-        # (csrc/shard.hip).  torch.distributed only carries the 128-byte id from rank 0 to the other ranks.
-        from leann_rs_amd.shard import rccl_group
-        ok = 1
-        try:
-            group = rccl_group(searcher, corpus_total, world, rank)
-        except Exception as e:  # noqa: BLE001  (e.g. librccl.so not resolvable): every rank agrees on the fallback below
-            ok, group = 0, None
-            print(f"[bench] rank {rank}: library RCCL group unavailable: {e}", file=sys.stderr, flush=True)
-        flag = torch.tensor([ok], dtype=torch.int32, device=dev)
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        if int(flag.item()) == 0:
-            if group is not None:
-                group.close()
-            group, rccl = None, False
-            log("falling back to the torch.distributed all-gather + HIP merge kernel for the exchange step")
-        else:
-            log(f"rank {rank}: attached to the library's RCCL group ({group.n_shards()} shards, {group.len()} rows)")
     ev_search = [torch.cuda.Event() for _ in range(2)]
     ev_xdone = [None, None]
 
@@ -779,6 +822,8 @@ def main():
         allow = (bits.view(-1, 8) * wts).sum(1, dtype=torch.int32).to(torch.uint8).contiguous()  # bit i&7 of byte i>>3
         del bits
         torch.cuda.synchronize()
+
+    last = [None]  # what the latest step hands its caller: name -> device tensor (--dump-outputs)
 
     def search(step, timed_events=None):
         """one step of the hot path on `stream` (N > 1: + exchange and merge on the library's stream, overlapping the next step's traversal)"""
@@ -818,10 +863,15 @@ def main():
             xstream.wait_event(ev_search[b])
             with torch.cuda.stream(xstream):
                 g_keys, g_dists, g_counts = exchange_topk(keys, dists, counts, world)
-                m_keys, _, _ = hip_merge(g_keys, g_dists, g_counts, k, False, xstream.cuda_stream)
+                m_keys, m_dists, m_counts = hip_merge(g_keys, g_dists, g_counts, k, False, xstream.cuda_stream)
                 ev_xdone[b] = torch.cuda.Event()
                 ev_xdone[b].record(xstream)
+            last[0] = {"keys": m_keys, "distances": m_dists, "counts": m_counts}
             return m_keys
+        if hybrid and hyb["pos"] is not None:
+            last[0] = {"keys": hyb["keys"], "scores": hyb["scores"], "counts": hyb["counts"]}
+        else:
+            last[0] = {"keys": keys, "distances": dists, "counts": counts}
         return keys
 
     def drain():
@@ -837,6 +887,8 @@ def main():
     gt_k = torch.empty((nrq, k), dtype=torch.int64, device=dev)
     gt_s = torch.empty((nrq, k), dtype=torch.float32, device=dev)
     gt_c = torch.empty((nrq,), dtype=torch.int32, device=dev)
+    stream.synchronize()
+    build_job = in_background(build) if build is not None else None
     t0 = time.time()
     if composite:  # per-device exact lists (scores descending), gathered on device 0 and merged there
         parts = []
@@ -872,6 +924,32 @@ def main():
         stream.synchronize(); xstream.synchronize()
     log(f"exact ground truth for {nrq} queries in {time.time() - t0:.2f}s")
     truth = gt_k.cpu().numpy()
+    if build is not None:
+        searcher, build_s = build_job()
+    torch.cuda.synchronize()
+    gi = subs[0].graph_info() if (composite and rgraph) else searcher.graph_info()
+    if composite:  # the composite handle carries n and dims only: degrees are the build's
+        gi = dict(gi, M=M, M0=(M if backend else 2 * M))
+    log(f"rank {rank}: index built on GPU in {build_s:.1f}s ({rows * G / build_s:.0f} rows/s), max_level={gi['max_level']}")
+    if rccl:
+        # one RCCL communicator of the LIBRARY's own: local traversal, ncclAllGather of the packed per-shard block, merge kernel
+        # (csrc/shard.hip).  torch.distributed only carries the 128-byte id from rank 0 to the other ranks.
+        from leann_rs_amd.shard import rccl_group
+        ok = 1
+        try:
+            group = rccl_group(searcher, corpus_total, world, rank)
+        except Exception as e:  # noqa: BLE001  (e.g. librccl.so not resolvable): every rank agrees on the fallback below
+            ok, group = 0, None
+            print(f"[bench] rank {rank}: library RCCL group unavailable: {e}", file=sys.stderr, flush=True)
+        flag = torch.tensor([ok], dtype=torch.int32, device=dev)
+        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+        if int(flag.item()) == 0:
+            if group is not None:
+                group.close()
+            group, rccl = None, False
+            log("falling back to the torch.distributed all-gather + HIP merge kernel for the exchange step")
+        else:
+            log(f"rank {rank}: attached to the library's RCCL group ({group.n_shards()} shards, {group.len()} rows)")
 
     def measure_recall(lo_q, hi_q):
         found = search(0)
@@ -945,11 +1023,13 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:  # before anything below reuses the result buffers
+        dump_outputs(args.dump_outputs, {name: t.cpu().numpy() for name, t in last[0].items()})
 
     # ---- N > 1, second curve ("report both shard and replica curves"): no collective — every rank answers DIFFERENT
     # query batches from its own `rows`-row index, which is what N replicas of a `rows`-row corpus do.  Not `value`: a side key.
     replica_qps = None
-    if shard and allow is None:
+    if args.full and shard and allow is None:
         def local(step):
             qb = (step + 3 * rank) % n_pool
             searcher.search_batch_device(Q.data_ptr() + qb * B * ld * 4, B, k, ef, kbuf[0].data_ptr(), dbuf[0].data_ptr(), cbuf[0].data_ptr(), None, sp)
@@ -1156,7 +1236,7 @@ def main():
         out["recall_note"] = f"recall@{k} of the ANN stage (first {k} of the {kk} fetched) against the exact scan; the reranked order is BM25-blended by design"
 
     # ---- PCIe-inclusive rate: the same batch through the host-pointer entry point (queries and results in host memory) ----
-    if n_gpus == 1 and rank == 0 and allow is None and not rgraph:
+    if args.full and n_gpus == 1 and rank == 0 and allow is None and not rgraph:
         try:
             Qh = Q[:B, :d].contiguous().cpu().numpy()
             searcher.search_batch(Qh, k, ef)
@@ -1171,7 +1251,7 @@ def main():
     # (src/backend/traits.rs:16-21), one query per call from host memory; and the serve pattern: 64 concurrent single-query callers
     # (src/cli/serve.rs:289-292), plain and with the library's request coalescing ------------------------------------------------
     lat = None
-    if n_gpus == 1 and rank == 0 and allow is None and not args.no_latency:
+    if args.full and n_gpus == 1 and rank == 0 and allow is None and not args.no_latency:
         try:
             import threading
             nlat = min(2000, n_pool * B)
@@ -1219,7 +1299,7 @@ def main():
             log("single-query timing failed:", e)
 
     # ---- CPU baseline: the oracle (C restatement) walking the SAME graph on the host cores --------
-    if n_gpus == 1 and not args.no_cpu_baseline and rank == 0 and allow is None:
+    if args.full and n_gpus == 1 and not args.no_cpu_baseline and rank == 0 and allow is None:
         try:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import pyoracle as po

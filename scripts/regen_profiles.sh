@@ -11,7 +11,7 @@ part=${1:-all}
 run() { # name, bench args...
   name=$1; shift
   echo "== $name: bench.py $*"
-  python bench.py "$@" > $out/${name}_bench.json 2> $out/${name}_bench.log || { tail -5 $out/${name}_bench.log; return 1; }
+  python bench.py --full "$@" > $out/${name}_bench.json 2> $out/${name}_bench.log || { tail -5 $out/${name}_bench.log; return 1; }
   python - "$out/${name}_bench.json" <<'PY'
 import json, sys
 j = json.load(open(sys.argv[1]))

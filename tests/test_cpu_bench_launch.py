@@ -118,3 +118,53 @@ def test_hanging_ranks_are_ended_at_the_deadline_and_the_fallback_runs(capsys, m
     assert b.self_launch(args, ["--gpus", "2"]) == 0
     assert time.time() - t0 < 40
     assert "composite2" in capsys.readouterr().out
+
+
+def test_plain_run_stays_in_process_and_full_starts_the_legs(monkeypatch):
+    """`python bench.py --gpus 1 --steps K --warmup W` measures the headline in its own process (here: a stand-in torch without a GPU
+    stops it at the device check); only --full hands the run to run_all_configs"""
+    import pytest
+    b = _bench()
+    calls = []
+    monkeypatch.setattr(b, "run_all_configs", lambda args, argv, run=None: calls.append(list(argv)) or 0)
+    monkeypatch.setattr(b, "quiet_stdout", lambda: None)
+    monkeypatch.setitem(sys.modules, "torch", types.SimpleNamespace(cuda=types.SimpleNamespace(is_available=lambda: False)))
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "1"]
+    monkeypatch.setattr(sys, "argv", ["bench.py", *argv, "--full"])
+    with pytest.raises(SystemExit) as e:
+        b.main()
+    assert e.value.code == 0 and calls == [argv + ["--full"]]
+    monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+    with pytest.raises(SystemExit) as e:
+        b.main()
+    assert "needs a GPU" in str(e.value.code) and len(calls) == 1
+    assert all("--full" in extra for _, extra, _ in b.OTHER_CONFIGS)  # the legs keep their side figures
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_past_64mb(tmp_path):
+    import numpy as np
+    b = _bench()
+    keys = np.arange(20, dtype=np.int64).reshape(10, 2)
+    keys[0, 1] = -1  # an empty slot (UINT64_MAX read as int64)
+    small = {"keys": keys, "distances": np.linspace(0, 1, 20, dtype=np.float32).reshape(10, 2), "counts": np.full(10, 2, np.int32)}
+    b.dump_outputs(str(tmp_path / "s"), small)
+    got = {n: np.load(tmp_path / "s" / f"{n}.npy") for n in small}
+    assert got["keys"].dtype == np.float64 and got["distances"].dtype == np.float32 and got["counts"].dtype == np.float64
+    for n in small:
+        assert np.array_equal(got[n], small[n]), n
+    assert sorted(os.listdir(tmp_path / "s")) == ["counts.npy", "distances.npy", "keys.npy"]
+    n = 1_000_000  # 80 MB of ids as float64 + 8 MB of counts: over the limit
+    big = {"keys": np.arange(n * 10, dtype=np.int64).reshape(n, 10), "counts": np.arange(n, dtype=np.int32)}
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), big)
+    sizes = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert sizes <= 64 << 20
+    rows = np.load(tmp_path / "a" / "query_rows.npy")
+    assert rows.dtype == np.float64 and len(rows) > n // 2 and (np.diff(rows) > 0).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "keys.npy"), big["keys"][rows.astype(np.int64)].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "a" / "counts.npy"), rows)
+    for f in ("keys.npy", "counts.npy", "query_rows.npy"):  # a fixed sample: the same rows every time
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    b.dump_outputs(str(tmp_path / "a"), small)  # an unsampled dump into the same directory leaves no stale index file
+    assert not os.path.exists(tmp_path / "a" / "query_rows.npy")

@@ -1,6 +1,7 @@
 """-m gpu: bench.py end to end on its smallest workload (hnsw100k: 100k x 768, seconds) — the contract's keys are there, the in-run checks
-(GPU == oracle on the sampled queries; device hybrid rerank == oracle/searcher_oracle.py) hold, and the default-run orchestration merges its
-legs into one line.  Guards the measurement harness itself; the numbers of record come from the full-size workloads."""
+(GPU == oracle on the sampled queries; device hybrid rerank == oracle/searcher_oracle.py) hold, the --full run's orchestration merges its
+legs into one line, and a plain run is lean and dumps what it computed.  Guards the measurement harness itself; the numbers of record come
+from the full-size workloads."""
 import json
 import os
 import subprocess
@@ -22,7 +23,7 @@ def _bench(*args, env=None):
 
 
 def test_bench_line_contract_and_in_run_identity_check(gpu):
-    j = _bench("--workload", "hnsw100k", "--steps", "3", "--warmup", "1", "--no-latency", "--cpu-queries", "512", "--small-batch", "64")
+    j = _bench("--workload", "hnsw100k", "--steps", "3", "--warmup", "1", "--no-latency", "--cpu-queries", "512", "--small-batch", "64", "--full")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
                 "config", "roofline", "cpu_baseline", "recall_at_10"):
         assert key in j, key
@@ -44,7 +45,8 @@ def test_bench_line_contract_and_in_run_identity_check(gpu):
 
 
 def test_bench_hybrid_leg_checks_itself_against_the_oracle(gpu):
-    j = _bench("--workload", "hnsw100k", "--hybrid", "--steps", "3", "--warmup", "1", "--no-latency", "--cpu-queries", "1024", "--compat-polarity", "false")
+    j = _bench("--workload", "hnsw100k", "--hybrid", "--steps", "3", "--warmup", "1", "--no-latency", "--cpu-queries", "1024", "--compat-polarity", "false",
+               "--full")
     h = j["hybrid"]
     assert h["fetch_k"] == 50 and h["compat_polarity"] is False and h["rerank_avg_ms"] > 0
     assert h["rerank_parity"]["sample"] == 1024 and h["rerank_parity"]["mismatching_queries"] == 0
@@ -55,7 +57,7 @@ def test_bench_hybrid_leg_checks_itself_against_the_oracle(gpu):
 def test_gpus_2_rehearsals_on_one_gpu(gpu):
     """the N > 1 paths with what one GPU allows: two ranks over gloo sharing the device (started by bench.py itself), and two shards behind
     one composite handle"""
-    j = _bench("--gpus", "2", "--workload", "hnsw100k", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-latency",
+    j = _bench("--gpus", "2", "--workload", "hnsw100k", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-latency", "--full",
                env={"LEANN_BENCH_DIST_BACKEND": "gloo"})
     assert j["n_gpus"] == 2 and "shard2" in j["config"]["parallelism"] and j["recall_at_10"] >= 0.95 and "replica_mode" in j
     j = _bench("--gpus", "2", "--mode", "composite", "--workload", "hnsw100k", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-latency",
@@ -69,8 +71,29 @@ def test_gpus_2_rehearsals_on_one_gpu(gpu):
 
 
 def test_default_run_parent_needs_no_gpu_and_relays_one_line(gpu):
-    """the driver's command shape (no --workload): the parent only starts children — here the headline leg alone (LEANN_BENCH_SKIP_OTHERS) at
+    """the --full run without --workload: the parent only starts children — here the headline leg alone (LEANN_BENCH_SKIP_OTHERS) at
     2 steps — and prints ONE line with the `other_configs` key"""
-    j = _bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-latency", env={"LEANN_BENCH_SKIP_OTHERS": "1"})
+    j = _bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-latency", "--full", env={"LEANN_BENCH_SKIP_OTHERS": "1"})
     assert j["steps"] == 2 and j["warmup"] == 1 and j["n_gpus"] == 1 and j["config"]["rows_per_gpu"] == 10_000_000
     assert j["other_configs"] == {} and j["recall_at_10"] >= 0.95 and 0.5 < j["roofline"]["frac"] < 1
+
+
+def test_plain_run_is_lean_and_dumps_its_last_step(gpu, tmp_path):
+    """without --full a run times its K steps and prints the line, nothing else; --dump-outputs writes the last step's results, and two
+    runs with the same arguments write the same arrays"""
+    import numpy as np
+    args = ("--workload", "hnsw100k", "--steps", "5", "--warmup", "2")
+    j = _bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    assert j["steps"] == 5 and j["warmup"] == 2 and j["ms_per_step"] > 0 and j["recall_at_10"] >= 0.95
+    assert abs(j["value"] - 16384 * 5 / (j["ms_per_step"] * 5e-3)) < 1e-6 * j["value"]
+    for side in ("cpu_baseline", "single_query", "pcie_inclusive_qps", "other_configs", "small_batch"):
+        assert side not in j, side
+    _bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["counts.npy", "distances.npy", "keys.npy"] and sorted(os.listdir(tmp_path / "b")) == names
+    a = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert a["keys"].dtype == np.float64 and a["distances"].dtype == np.float32 and a["counts"].dtype == np.float64
+    assert a["keys"].shape == a["distances"].shape == (16384, 10) and a["counts"].shape == (16384,)
+    assert (a["counts"] == 10).all() and (a["keys"] >= 0).all() and (a["keys"] < 100_000).all()
+    for n in a:
+        assert np.array_equal(a[n], np.load(tmp_path / "b" / f"{n}.npy")), n
