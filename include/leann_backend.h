@@ -130,7 +130,9 @@ void leann_backend_close(leann_backend *h);
 
 /* ---- BackendBuilder::build(embeddings, ids, index_path, dims, graph_degree, complexity)
  *      src/backend/mod.rs:55-79 -> hnsw.rs:96-139 / diskann.rs:70-105 ---------------------------
- * vectors: [n x dims] row-major host memory.  Writes "<stem>.index" / "<stem>.diskann". */
+ * vectors: [n x dims] row-major host memory.  Writes "<stem>.index" / "<stem>.diskann".
+ * graph_degree: HNSW M in [2, 64] (level-0 lists hold 2 M <= 128 ids), DiskANN R in [2, 128]; outside -> LEANN_ERR_INVALID
+ * before any device work.  Lists of more than 64 ids take the wide kernels; the file layout is the same. */
 int leann_backend_build(int backend, const float *vectors, size_t n, size_t dims,
                         size_t graph_degree, size_t complexity, const char *index_path_stem);
 /* BackendBuilder::add_to_index(embeddings, index_path, dims, start_id)  mod.rs:82-100,
@@ -160,11 +162,11 @@ int leann_backend_stats(const leann_backend *h, leann_search_stats *out, int res
 /* In-memory index straight from device-resident rows (no file round trip).
  * d_vectors: [n x ld] f32 in HBM, ld % 4 == 0, ld >= dims, padding zero; borrowed if `take_copy`
  * is 0 (must outlive the handle).  key_offset is added to every returned key (shard rebasing,
- * SURVEY.md §8e). */
+ * SURVEY.md §8e).  graph_degree: HNSW [2, 64], DiskANN [2, 128], as leann_backend_build. */
 int leann_backend_build_device(int backend, const float *d_vectors, size_t n, size_t dims,
                                size_t ld, size_t graph_degree, size_t complexity, int device,
                                uint64_t key_offset, int take_copy, leann_backend **out);
-/* Wrap host-side flat graph arrays + host rows into a device index. */
+/* Wrap host-side flat graph arrays + host rows into a device index.  M, M0 in [1, 128]. */
 int leann_backend_from_arrays(int backend, const float *vectors, size_t n, size_t dims,
                               uint32_t M, uint32_t M0, uint32_t max_level, uint32_t entry,
                               const uint8_t *levels, const uint32_t *upper_off,
@@ -253,7 +255,8 @@ void leann_recompute_close(leann_recompute *r);
 /* Recompute-on GRAPH index: HNSW / Vamana whose distances are recomputed from the encoder inputs.  The graph is
  * built on transiently materialised embeddings; the returned searcher keeps the graph, the bf16 features and one
  * f32 per passage (||W^T f||) — no vectors — and evaluates dist = 1 - <f, W q> / ||W^T f|| (== 1 - <e, q>).
- * It is an ordinary leann_backend handle: leann_backend_search* work unchanged (queries in embedding space). */
+ * It is an ordinary leann_backend handle: leann_backend_search* work unchanged (queries in embedding space).
+ * graph_degree: HNSW [2, 64], DiskANN [2, 128], as leann_backend_build. */
 int leann_recompute_build_index(const leann_recompute *r, int backend, size_t graph_degree, size_t complexity,
                                 leann_backend **out);
 int leann_backend_feature_rows_export(const leann_backend *h, uint32_t *feat_h, uint32_t *row_bytes, void *out);
@@ -305,7 +308,8 @@ int leann_sharded_open(const char *index_path_stem, int backend, size_t dims, co
  * graph_info / graph_export / feature_rows_export work on it.  leann_backend_shard_count: 0 for a plain handle. */
 size_t leann_backend_shard_count(const leann_backend *h);
 int leann_backend_shard(const leann_backend *h, size_t g, leann_backend **out);
-/* d_vectors[g]: rows of shard g on devices[g] ([rows[g] x ld] f32, borrowed); keys are rebased by the prefix sums of rows[] */
+/* d_vectors[g]: rows of shard g on devices[g] ([rows[g] x ld] f32, borrowed); keys are rebased by the prefix sums of rows[];
+ * graph_degree: HNSW [2, 64], DiskANN [2, 128], as leann_backend_build */
 int leann_sharded_build_device(int backend, const float *const *d_vectors, const size_t *rows, size_t n_shards, size_t dims,
                                size_t ld, size_t graph_degree, size_t complexity, const int *devices, leann_sharded **out);
 /* existing handles (each built with its key_offset); take_ownership: leann_sharded_close closes them */

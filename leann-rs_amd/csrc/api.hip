@@ -270,10 +270,21 @@ static int search_lds_checked(const GraphView &g, const SearchArgs &a, size_t *l
     return LEANN_OK;
 }
 
+// Lists of more than 64 ids (HNSW M > 32, DiskANN R > 64) take the wide kernels: two list ids per lane of wave 0 (search.cuh, LW = 2).
+// They exist in the 4- and 16-wave forms only (the 8-wave form's batches, 385..640 queries, run 16 waves): every wide form adds the
+// compile time of a narrow one, and all three doubled that of this file (34 -> 70 s).
+static bool wide_graph(const GraphView &g) { return std::max(g.M0, g.M) > 64; }
+
 template <int T, int R, int NW>
 static int launch_search_NW(const GraphView &g, const SearchArgs &a, hipStream_t st) {
     size_t lds;
     if (int rc = search_lds_checked(g, a, &lds, NW)) return rc;
+    if constexpr (NW != 8)
+        if (wide_graph(g)) {
+            if (a.allow) return launch_one(wide_beam_search_filtered_kernel<T, R, NW>, NW * 64, lds, g, a, st);
+            if (a.q_rows) return launch_one(wide_beam_search_kernel<T, R, NW, true>, NW * 64, lds, g, a, st);
+            return launch_one(wide_beam_search_kernel<T, R, NW, false>, NW * 64, lds, g, a, st);
+        }
     if (a.allow) return launch_one(beam_search_filtered_kernel<T, R, NW>, NW * 64, lds, g, a, st);
     if (a.q_rows) return launch_one(beam_search_kernel<T, R, NW, true>, NW * 64, lds, g, a, st);
     return launch_one(beam_search_kernel<T, R, NW, false>, NW * 64, lds, g, a, st);
@@ -286,6 +297,7 @@ template <int T, int R>
 static int launch_search_T(const GraphView &g, const SearchArgs &a, hipStream_t st) {
     int nw = a.nq <= 384 ? 16 : a.nq <= 640 ? 8 : 4; // 10M x 768, ef = 56: 16 waves win up to 256 queries, 8 at 512, 4 from 768 on (scripts/exp/batch_sweep.py)
     if (const int v = leann_knobs().nw) nw = v;
+    if (nw >= 8 && wide_graph(g)) nw = 16; // (no 8-wave wide kernels)
     if (nw >= 16) return launch_search_NW<T, R, 16>(g, a, st);
     if (nw >= 8) return launch_search_NW<T, R, 8>(g, a, st);
     return launch_search_NW<T, R, 4>(g, a, st);
@@ -295,13 +307,30 @@ template <int T, int R>
 static int launch_search_feat(const GraphView &g, const SearchArgs &a, hipStream_t st) {
     size_t lds;
     if (int rc = search_lds_checked(g, a, &lds, a.nq <= 512 ? 16 : 4)) return rc;
+    const bool wide = wide_graph(g);
     if (T == 1 && g.feat_h == 256 && !leann_knobs().no_feat256) { // four rows per wave instruction
+        if (wide) {
+            if (a.nq <= 512) {
+                if (a.allow) return launch_one(wide_beam_search_feat256_filtered_kernel<1, 16>, 16 * 64, lds, g, a, st);
+                return launch_one(wide_beam_search_feat256_kernel<1, 16>, 16 * 64, lds, g, a, st);
+            }
+            if (a.allow) return launch_one(wide_beam_search_feat256_filtered_kernel<LEANN_FEAT_G, 4>, 4 * 64, lds, g, a, st);
+            return launch_one(wide_beam_search_feat256_kernel<LEANN_FEAT_G, 4>, 4 * 64, lds, g, a, st);
+        }
         if (a.nq <= 512) {
             if (a.allow) return launch_one(beam_search_feat256_filtered_kernel<1, 16>, 16 * 64, lds, g, a, st);
             return launch_one(beam_search_feat256_kernel<1, 16>, 16 * 64, lds, g, a, st);
         }
         if (a.allow) return launch_one(beam_search_feat256_filtered_kernel<LEANN_FEAT_G, 4>, 4 * 64, lds, g, a, st);
         return launch_one(beam_search_feat256_kernel<LEANN_FEAT_G, 4>, 4 * 64, lds, g, a, st);
+    }
+    if (wide) {
+        if (a.nq <= 512) {
+            if (a.allow) return launch_one(wide_beam_search_feat_filtered_kernel<T, R, 16>, 16 * 64, lds, g, a, st);
+            return launch_one(wide_beam_search_feat_kernel<T, R, 16>, 16 * 64, lds, g, a, st);
+        }
+        if (a.allow) return launch_one(wide_beam_search_feat_filtered_kernel<T, R, 4>, 4 * 64, lds, g, a, st);
+        return launch_one(wide_beam_search_feat_kernel<T, R, 4>, 4 * 64, lds, g, a, st);
     }
     if (a.nq <= 512) {
         if (a.allow) return launch_one(beam_search_feat_filtered_kernel<T, R, 16>, 16 * 64, lds, g, a, st);
@@ -967,7 +996,7 @@ extern "C" int leann_backend_search_filtered(const leann_backend *hc, const floa
 // upper_off[node] + level - 1 and trusts both (search.cuh), so one bad entry in an index file would be an out-of-bounds read on the GPU.
 static const char *validate_graph(size_t n, uint32_t M, uint32_t M0, uint32_t max_level, uint32_t entry, const uint8_t *levels,
                                   const uint32_t *upper_off, const uint32_t *adj0, const uint32_t *adjU, size_t n_upper_lists) {
-    if (M == 0 || M0 == 0 || M > 64 || M0 > 64) return "graph degree outside [1, 64]";
+    if (M == 0 || M0 == 0 || M > 128 || M0 > 128) return "graph degree outside [1, 128]";
     if (max_level > 15) return "max_level > 15";
     if (n == 0) return nullptr;
     if (entry >= n) return "entry point is not a row of the index";

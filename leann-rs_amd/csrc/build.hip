@@ -25,10 +25,20 @@
 #include <cstring>
 #include <numeric>
 
+// Candidate pool of one prune: NC = 128 for lists of <= 64 ids; wide graphs (lists of up to 128 ids: HNSW M > 32, DiskANN R > 64)
+// take their own instantiations with NC = 256, so that a full 128-id list can still take proposals.  Their lower triangle (127.5 KiB)
+// plus the staging tile and the small arrays (~152 KiB of LDS) leave one workgroup per CU; narrow builds keep their kernels.
 #define NCMAX 128
+#define NCWIDE 256
 #define EXPCAP 256 // expanded nodes recorded per construction search (Vamana)
 #define PATHMAX 48 // of which at most this many path nodes join the prune candidates
-#define TRI_ELEMS (NCMAX * (NCMAX - 1) / 2)
+template <int NC> struct Pool {
+    static constexpr int TRI = NC * (NC - 1) / 2;
+    static constexpr int KC = 16 * (256 / NC); // gram_lower staging tile: KC x LDW floats; one 16-float piece of a row per thread
+    static constexpr int LDW = NC + 4;
+    static constexpr int STAGE = NC > NCMAX ? KC * LDW : 1; // wide: a tile of its own (see gram_lower); narrow: inside the triangle
+    static constexpr int KS = NC > NCMAX ? 2 : 1;           // kept slots per lane of wave 0 in prune_core
+};
 
 struct ListView {
     uint32_t *adj0; float *adjd0;  // [n x M0]
@@ -36,7 +46,7 @@ struct ListView {
     const uint32_t *upper_off;
     uint32_t M, M0;
     // Vamana only: per-node PENDING back-edges (ids + distances, [n x P], compact, LEANN_EMPTY padded).  DiskANN lets a list grow to
-    // 1.3 R before it re-runs RobustPrune; lists here hold one id per lane of a wave (<= 64), so the slack lives beside the list:
+    // 1.3 R before it re-runs RobustPrune; lists here have a fixed width (R ids), so the slack lives beside the list:
     // a back-edge that finds its target full waits here, invisible to searches, until P of them have gathered; then ONE RobustPrune
     // over list + pending + proposals rewrites the list.  Every touched list being full, the strict rule pruned per proposal:
     // ~600k prunes per 16k-point batch, each gathering 64+ rows (0.4 MB at 1536-d) — 67 % of a 10M x 1536 build.
@@ -64,30 +74,35 @@ __device__ __forceinline__ void list_ptr(const ListView &lv, uint32_t node, uint
 // (drop c if alpha * dist(c, kept) <= dist(c, p)).   256 threads.  Returns count in every thread;
 // kept candidate positions in s_sel[0..count).
 // ------------------------------------------------------------------------------------------------
-template <int TS> // per-thread tile TS x TS; the 16 x 16 thread grid covers 16*TS candidates
+template <int TS, int NC = NCMAX> // per-thread tile TS x TS; the (NC/8) x (NC/8) tile grid covers NC/8*TS candidates
 __device__ __forceinline__ void gram_lower(const float *__restrict__ X, uint32_t ld, const uint32_t *c_id, uint32_t nc,
                                            float *tri, float *stage_) {
     float *stage = static_cast<float *>(__builtin_assume_aligned(stage_, 16));
-    constexpr int KC = 32, LDW = NCMAX + 4; // rows of the staging tile stay 16-byte aligned: the 2 x TS operands of a k step are 16-B LDS reads
+    constexpr int KC = Pool<NC>::KC, LDW = Pool<NC>::LDW; // rows of the staging tile stay 16-byte aligned: the 2 x TS operands of a k step are 16-B LDS reads
+    constexpr int TD = NC / 8, RS = 256 / NC;              // tile rows / columns; threads per staged row
     // The blocks that touch the lower triangle of the nc x nc matrix — (ty, tx) with tx <= ty < ceil(nc / TS) — are handed to the FIRST
     // threads of the workgroup in triangular order, so the multiply loop runs in ceil(ntiles / 64) waves (1 for the ~70 candidates of a
     // full Vamana list) instead of in every wave that owns a row of a 16 x 16 thread grid (3 of 4 there, a handful of lanes each).
+    // Wide pools (NC = 256: up to 528 tiles of 8 x 8) walk the tile list in passes of 256 tiles, each streaming the rows again; their
+    // staging tile lives outside the triangle, which the passes before have begun to fill.
     const int tid = threadIdx.x;
-    const int tdim = min(16, (int)((nc + TS - 1) / TS)), ntiles = tdim * (tdim + 1) / 2;
-    const bool active = tid < ntiles;
+    const int tdim = min(TD, (int)((nc + TS - 1) / TS)), ntiles = tdim * (tdim + 1) / 2;
+    for (int t0 = 0; t0 < ntiles; t0 += 256) {
+    const int tile = t0 + tid;
+    const bool active = tile < ntiles;
     int ty = 0, tx = 0;
     if (active) {
-        ty = (int)((sqrtf(8.f * (float)tid + 1.f) - 1.f) * 0.5f);
-        while (ty * (ty + 1) / 2 > tid) ty--;
-        while ((ty + 1) * (ty + 2) / 2 <= tid) ty++;
-        tx = tid - ty * (ty + 1) / 2;
+        ty = (int)((sqrtf(8.f * (float)tile + 1.f) - 1.f) * 0.5f);
+        while (ty * (ty + 1) / 2 > tile) ty--;
+        while ((ty + 1) * (ty + 2) / 2 <= tile) ty++;
+        tx = tile - ty * (ty + 1) / 2;
     }
     float acc[TS][TS];
 #pragma unroll
     for (int i = 0; i < TS; i++)
 #pragma unroll
         for (int j = 0; j < TS; j++) acc[i][j] = 0.f;
-    const int srow = tid >> 1, shalf = tid & 1;
+    const int srow = tid / RS, shalf = tid % RS;
     const float *rowp = (srow < (int)nc) ? X + (size_t)c_id[srow] * ld : nullptr;
     for (uint32_t k0 = 0; k0 < ld; k0 += KC) {
         float4 v[4];
@@ -97,7 +112,7 @@ __device__ __forceinline__ void gram_lower(const float *__restrict__ X, uint32_t
             v[e] = (rowp && j < ld) ? *reinterpret_cast<const float4 *>(rowp + j) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
         __syncthreads(); // previous chunk fully consumed
-        if (srow < 16 * TS) {
+        if (srow < TD * TS) {
 #pragma unroll
             for (int e = 0; e < 4; e++) {
                 int kk = shalf * 16 + e * 4;
@@ -134,20 +149,24 @@ __device__ __forceinline__ void gram_lower(const float *__restrict__ X, uint32_t
             }
     }
     __syncthreads();
+    }
 }
 
+// NC = NCWIDE: up to 128 kept, two slots per lane (slot s in lane s % 64); `stage` is then a tile of its own (Pool<NC>::STAGE floats).
+template <int NC = NCMAX>
 __device__ uint32_t prune_core(const float *__restrict__ X, uint32_t ld, const uint32_t *c_id, const float *c_d,
-                               uint32_t nc, uint32_t limit, float alpha, float *tri /* TRI_ELEMS floats, LDS */,
-                               uint32_t *s_sel /* [64] LDS */, uint32_t *s_cnt /* LDS */, bool stage1) {
-    float *stage = static_cast<float *>(__builtin_assume_aligned(tri, 16)); // [KC][LDW] aliased: dead before tri is written
+                               uint32_t nc, uint32_t limit, float alpha, float *tri /* Pool<NC>::TRI floats, LDS */,
+                               uint32_t *s_sel /* [64 KS] LDS */, uint32_t *s_cnt /* LDS */, bool stage1, float *wide_stage = nullptr) {
+    float *stage = static_cast<float *>(__builtin_assume_aligned(NC > NCMAX ? wide_stage : tri, 16)); // narrow: [KC][LDW] aliased, dead before tri is written
+    constexpr int KS = Pool<NC>::KS;
     const int tid = threadIdx.x;
-    if (nc <= 32) gram_lower<2>(X, ld, c_id, nc, tri, stage);       // work ~ nc^2: small lists use small tiles
-    else if (nc <= 64) gram_lower<4>(X, ld, c_id, nc, tri, stage);
-    else gram_lower<8>(X, ld, c_id, nc, tri, stage);
-    __shared__ uint8_t s_taken[NCMAX];
+    if (nc <= 32) gram_lower<2, NC>(X, ld, c_id, nc, tri, stage);       // work ~ nc^2: small lists use small tiles
+    else if (nc <= 64) gram_lower<4, NC>(X, ld, c_id, nc, tri, stage);
+    else gram_lower<8, NC>(X, ld, c_id, nc, tri, stage);
+    __shared__ uint8_t s_taken[NC];
     if (tid < 64) { // wave 0: sequential walk over candidates, lanes = kept slots
         uint32_t ns = 0;
-        int my = -1;
+        int my = -1, my1 = -1; // my1: kept slot 64 + lane (KS = 2)
         // Vamana, two-stage form (DiskANN's occlude_list): the FIRST walk over the whole pool keeps a candidate only if no kept
         // one is at least as close to it as the point itself (alpha = 1: the diverse core, which reaches the far end of the pool before
         // the list is full); only the slots still free after it are filled by the relaxed rule alpha * d(c, kept) <= d(c, p) -> drop.
@@ -164,8 +183,13 @@ __device__ uint32_t prune_core(const float *__restrict__ X, uint32_t ld, const u
                 float gdist = tri[i * (i - 1) / 2 + my];
                 bad = (alpha == 0.f) ? (gdist < di) : ((two_stage ? 1.0f : alpha) * gdist <= di);
             }
+            if (KS == 2 && tid + 64 < (int)ns) {
+                float gdist = tri[i * (i - 1) / 2 + my1];
+                bad = bad || ((alpha == 0.f) ? (gdist < di) : ((two_stage ? 1.0f : alpha) * gdist <= di));
+            }
             if (!__any(bad)) {
                 if (tid == (int)ns) my = (int)i;
+                if (KS == 2 && tid + 64 == (int)ns) my1 = (int)i;
                 if (two_stage && tid == 0) s_taken[i] = 1;
                 ns++;
                 if (ns == limit) break;
@@ -180,14 +204,20 @@ __device__ uint32_t prune_core(const float *__restrict__ X, uint32_t ld, const u
                     const uint32_t hi = max(i, (uint32_t)my), lo = min(i, (uint32_t)my);
                     bad = alpha * tri[hi * (hi - 1) / 2 + lo] <= di;
                 }
+                if (KS == 2 && tid + 64 < (int)ns) {
+                    const uint32_t hi = max(i, (uint32_t)my1), lo = min(i, (uint32_t)my1);
+                    bad = bad || alpha * tri[hi * (hi - 1) / 2 + lo] <= di;
+                }
                 if (!__any(bad)) {
                     if (tid == (int)ns) my = (int)i;
+                    if (KS == 2 && tid + 64 == (int)ns) my1 = (int)i;
                     ns++;
                     if (ns == limit) break;
                 }
             }
         }
         if (tid < (int)ns) s_sel[tid] = (uint32_t)my;
+        if (KS == 2 && tid + 64 < (int)ns) s_sel[tid + 64] = (uint32_t)my1;
         if (tid == 0) *s_cnt = ns;
     }
     __syncthreads();
@@ -197,28 +227,30 @@ __device__ uint32_t prune_core(const float *__restrict__ X, uint32_t ld, const u
 // ------------------------------------------------------------------------------------------------
 // select_kernel: one workgroup per new point of the batch (at one level).
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) select_kernel(const float *__restrict__ X, uint32_t ld, ListView lv,
-                                                     const uint32_t *__restrict__ q_rows, uint32_t nq, uint32_t level,
-                                                     const uint64_t *__restrict__ cand_keys, const float *__restrict__ cand_d,
-                                                     const uint32_t *__restrict__ cand_cnt, uint32_t efc, uint32_t msel,
-                                                     float alpha, uint64_t *__restrict__ prop_key, uint32_t *__restrict__ prop_src,
-                                                     const uint64_t *__restrict__ exp_keys, const uint32_t *__restrict__ exp_cnt,
-                                                     uint32_t exp_cap) {
-    __shared__ __attribute__((aligned(16))) float tri[TRI_ELEMS];
-    __shared__ uint32_t c_id[NCMAX];
-    __shared__ float c_d[NCMAX];
-    __shared__ uint32_t s_sel[64];
+template <int NC>
+__device__ __forceinline__ void select_one(const float *__restrict__ X, uint32_t ld, ListView lv,
+                                           const uint32_t *__restrict__ q_rows, uint32_t nq, uint32_t level,
+                                           const uint64_t *__restrict__ cand_keys, const float *__restrict__ cand_d,
+                                           const uint32_t *__restrict__ cand_cnt, uint32_t efc, uint32_t msel,
+                                           float alpha, uint64_t *__restrict__ prop_key, uint32_t *__restrict__ prop_src,
+                                           const uint64_t *__restrict__ exp_keys, const uint32_t *__restrict__ exp_cnt,
+                                           uint32_t exp_cap) {
+    __shared__ __attribute__((aligned(16))) float tri[Pool<NC>::TRI];
+    __shared__ uint32_t c_id[NC];
+    __shared__ float c_d[NC];
+    __shared__ __attribute__((aligned(16))) float wstage[Pool<NC>::STAGE];
+    __shared__ uint32_t s_sel[64 * Pool<NC>::KS];
     __shared__ uint32_t s_cnt;
     __shared__ uint64_t pkey[EXPCAP];
     const uint32_t qi = blockIdx.x;
     if (qi >= nq) return;
     const uint32_t q = q_rows[qi];
-    uint32_t nc = min(min(cand_cnt[qi], efc), (uint32_t)NCMAX);
-    for (uint32_t i = threadIdx.x; i < NCMAX; i += 256) {
+    uint32_t nc = min(min(cand_cnt[qi], efc), (uint32_t)NC);
+    for (uint32_t i = threadIdx.x; i < NC; i += 256) {
         c_id[i] = i < nc ? (uint32_t)cand_keys[(size_t)qi * efc + i] : 0u;
         c_d[i] = i < nc ? cand_d[(size_t)qi * efc + i] : 0.f;
     }
-    if (threadIdx.x == 0) s_cnt = NCMAX;
+    if (threadIdx.x == 0) s_cnt = NC;
     __syncthreads();
     // a point that is already linked (second Vamana pass) finds itself: drop it from its own candidates
     for (uint32_t i = threadIdx.x; i < nc; i += 256)
@@ -226,8 +258,8 @@ __global__ void __launch_bounds__(256) select_kernel(const float *__restrict__ X
     __syncthreads();
     if (s_cnt < nc) {
         const uint32_t self = s_cnt;
-        uint32_t mv_id[NCMAX / 256 + 1];
-        float mv_d[NCMAX / 256 + 1];
+        uint32_t mv_id[NC / 256 + 1];
+        float mv_d[NC / 256 + 1];
         int t = 0;
         for (uint32_t i = self + threadIdx.x; i + 1 < nc; i += 256, t++) { mv_id[t] = c_id[i + 1]; mv_d[t] = c_d[i + 1]; }
         __syncthreads();
@@ -266,7 +298,7 @@ __global__ void __launch_bounds__(256) select_kernel(const float *__restrict__ X
         __syncthreads();
         const uint32_t n_path = s_cnt;
         const uint32_t take = min(n_path, (uint32_t)PATHMAX);
-        const uint32_t keep = min(nc, (uint32_t)NCMAX - take);
+        const uint32_t keep = min(nc, (uint32_t)NC - take);
         __syncthreads();
         for (uint32_t t = threadIdx.x; t < take; t += 256) { // even subsample keeps near and far path nodes
             const uint64_t key = pkey[(uint64_t)t * n_path / take];
@@ -276,7 +308,7 @@ __global__ void __launch_bounds__(256) select_kernel(const float *__restrict__ X
         nc = keep + take;
         __syncthreads();
     }
-    uint32_t ns = prune_core(X, ld, c_id, c_d, nc, msel, alpha, tri, s_sel, &s_cnt, lv.two_stage != 0);
+    uint32_t ns = prune_core<NC>(X, ld, c_id, c_d, nc, msel, alpha, tri, s_sel, &s_cnt, lv.two_stage != 0, wstage);
     uint32_t *ids; float *ds; uint32_t cap;
     list_ptr(lv, q, level, &ids, &ds, &cap);
     for (uint32_t j = threadIdx.x; j < msel; j += 256) {
@@ -293,6 +325,25 @@ __global__ void __launch_bounds__(256) select_kernel(const float *__restrict__ X
     for (uint32_t j = ns + threadIdx.x; j < cap; j += 256) ids[j] = LEANN_EMPTY; // (a re-linked point: nothing of its old list stays behind the new one)
 }
 
+__global__ void __launch_bounds__(256) select_kernel(const float *__restrict__ X, uint32_t ld, ListView lv,
+                                                     const uint32_t *__restrict__ q_rows, uint32_t nq, uint32_t level,
+                                                     const uint64_t *__restrict__ cand_keys, const float *__restrict__ cand_d,
+                                                     const uint32_t *__restrict__ cand_cnt, uint32_t efc, uint32_t msel,
+                                                     float alpha, uint64_t *__restrict__ prop_key, uint32_t *__restrict__ prop_src,
+                                                     const uint64_t *__restrict__ exp_keys, const uint32_t *__restrict__ exp_cnt,
+                                                     uint32_t exp_cap) {
+    select_one<NCMAX>(X, ld, lv, q_rows, nq, level, cand_keys, cand_d, cand_cnt, efc, msel, alpha, prop_key, prop_src, exp_keys, exp_cnt, exp_cap);
+}
+__global__ void __launch_bounds__(256) wide_select_kernel(const float *__restrict__ X, uint32_t ld, ListView lv,
+                                                          const uint32_t *__restrict__ q_rows, uint32_t nq, uint32_t level,
+                                                          const uint64_t *__restrict__ cand_keys, const float *__restrict__ cand_d,
+                                                          const uint32_t *__restrict__ cand_cnt, uint32_t efc, uint32_t msel,
+                                                          float alpha, uint64_t *__restrict__ prop_key, uint32_t *__restrict__ prop_src,
+                                                          const uint64_t *__restrict__ exp_keys, const uint32_t *__restrict__ exp_cnt,
+                                                          uint32_t exp_cap) {
+    select_one<NCWIDE>(X, ld, lv, q_rows, nq, level, cand_keys, cand_d, cand_cnt, efc, msel, alpha, prop_key, prop_src, exp_keys, exp_cnt, exp_cap);
+}
+
 // heads of equal-target runs in the sorted proposal array
 __global__ void segment_heads_kernel(const uint64_t *__restrict__ keys, uint32_t num, uint32_t *__restrict__ seg_start,
                                      uint32_t *__restrict__ nseg) {
@@ -306,17 +357,19 @@ __global__ void segment_heads_kernel(const uint64_t *__restrict__ keys, uint32_t
 // ------------------------------------------------------------------------------------------------
 // reverse_merge_kernel: one workgroup per touched list (target node at `level`).
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) reverse_merge_kernel(const float *__restrict__ X, uint32_t ld, ListView lv,
-                                                            uint32_t level, const uint64_t *__restrict__ keys,
-                                                            const uint32_t *__restrict__ srcs, uint32_t num,
-                                                            const uint32_t *__restrict__ seg_start,
-                                                            const uint32_t *__restrict__ nseg_p, float alpha, uint32_t flush_nodes) {
+template <int NC>
+__device__ __forceinline__ void reverse_merge_one(const float *__restrict__ X, uint32_t ld, ListView lv,
+                                                  uint32_t level, const uint64_t *__restrict__ keys,
+                                                  const uint32_t *__restrict__ srcs, uint32_t num,
+                                                  const uint32_t *__restrict__ seg_start,
+                                                  const uint32_t *__restrict__ nseg_p, float alpha, uint32_t flush_nodes) {
     // flush_nodes != 0: final pass over nodes [0, flush_nodes) — fold whatever is still pending into its list (no proposals)
-    __shared__ __attribute__((aligned(16))) float tri[TRI_ELEMS];
-    __shared__ uint64_t skey[NCMAX];
-    __shared__ uint32_t c_id[NCMAX];
-    __shared__ float c_d[NCMAX];
-    __shared__ uint32_t s_sel[64];
+    __shared__ __attribute__((aligned(16))) float tri[Pool<NC>::TRI];
+    __shared__ uint64_t skey[NC];
+    __shared__ uint32_t c_id[NC];
+    __shared__ float c_d[NC];
+    __shared__ __attribute__((aligned(16))) float wstage[Pool<NC>::STAGE];
+    __shared__ uint32_t s_sel[64 * Pool<NC>::KS];
     __shared__ uint32_t s_cnt, s_k, s_len, s_pl;
     const uint32_t nseg = flush_nodes ? flush_nodes : *nseg_p;
     const uint32_t P = level == 0 ? lv.P : 0u;
@@ -329,8 +382,8 @@ __global__ void __launch_bounds__(256) reverse_merge_kernel(const float *__restr
         float *pdd = P ? lv.pendd + (size_t)t * P : nullptr;
         if (threadIdx.x == 0) { s_k = 0; s_len = 0; s_pl = 0; }
         __syncthreads();
-        // proposals of this run (sorted by dist): count up to NCMAX; existing list / pending lengths
-        if (!flush_nodes && threadIdx.x < NCMAX) {
+        // proposals of this run (sorted by dist): count up to NC; existing list / pending lengths
+        if (!flush_nodes && threadIdx.x < NC) {
             uint32_t i = start + threadIdx.x;
             if (i < num && (uint32_t)(keys[i] >> 32) == t) atomicAdd(&s_k, 1u); // run is contiguous
         }
@@ -352,20 +405,20 @@ __global__ void __launch_bounds__(256) reverse_merge_kernel(const float *__restr
             __syncthreads();
             continue;
         }
-        if (len + pl + k > NCMAX) k = NCMAX - len - pl; // keep the closest proposals only
+        if (len + pl + k > NC) k = NC - len - pl; // keep the closest proposals only
         const uint32_t nc = len + pl + k;
-        for (uint32_t i = threadIdx.x; i < NCMAX; i += 256) {
+        for (uint32_t i = threadIdx.x; i < NC; i += 256) {
             uint64_t key = ~0ull;
             if (i < len) key = ((uint64_t)f32_orderable(ds[i]) << 32) | ids[i];
             else if (i < len + pl) key = ((uint64_t)f32_orderable(pdd[i - len]) << 32) | pid[i - len];
             else if (i < nc) key = ((uint64_t)(uint32_t)keys[start + i - len - pl] << 32) | srcs[start + i - len - pl];
             skey[i] = key;
         }
-        // bitonic sort of NCMAX keys by (dist, id)
-        for (int size = 2; size <= NCMAX; size <<= 1)
+        // bitonic sort of NC keys by (dist, id)
+        for (int size = 2; size <= NC; size <<= 1)
             for (int stride = size >> 1; stride > 0; stride >>= 1) {
                 __syncthreads();
-                if (threadIdx.x < NCMAX / 2) {
+                if (threadIdx.x < NC / 2) {
                     int i = threadIdx.x;
                     int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
                     bool up = ((lo & size) == 0);
@@ -374,12 +427,12 @@ __global__ void __launch_bounds__(256) reverse_merge_kernel(const float *__restr
                 }
             }
         __syncthreads();
-        for (uint32_t i = threadIdx.x; i < NCMAX; i += 256) {
+        for (uint32_t i = threadIdx.x; i < NC; i += 256) {
             c_id[i] = i < nc ? (uint32_t)skey[i] : 0u;
             c_d[i] = i < nc ? orderable_f32((uint32_t)(skey[i] >> 32)) : 0.f;
         }
         __syncthreads();
-        uint32_t ns = prune_core(X, ld, c_id, c_d, nc, cap, alpha, tri, s_sel, &s_cnt, lv.two_stage != 0);
+        uint32_t ns = prune_core<NC>(X, ld, c_id, c_d, nc, cap, alpha, tri, s_sel, &s_cnt, lv.two_stage != 0, wstage);
         for (uint32_t j = threadIdx.x; j < cap; j += 256) {
             if (j < ns) {
                 uint32_t c = s_sel[j];
@@ -393,6 +446,21 @@ __global__ void __launch_bounds__(256) reverse_merge_kernel(const float *__restr
         for (uint32_t j = threadIdx.x; j < P; j += 256) { pid[j] = LEANN_EMPTY; pdd[j] = 0.f; }
         __syncthreads();
     }
+}
+
+__global__ void __launch_bounds__(256) reverse_merge_kernel(const float *__restrict__ X, uint32_t ld, ListView lv,
+                                                            uint32_t level, const uint64_t *__restrict__ keys,
+                                                            const uint32_t *__restrict__ srcs, uint32_t num,
+                                                            const uint32_t *__restrict__ seg_start,
+                                                            const uint32_t *__restrict__ nseg_p, float alpha, uint32_t flush_nodes) {
+    reverse_merge_one<NCMAX>(X, ld, lv, level, keys, srcs, num, seg_start, nseg_p, alpha, flush_nodes);
+}
+__global__ void __launch_bounds__(256) wide_reverse_merge_kernel(const float *__restrict__ X, uint32_t ld, ListView lv,
+                                                                 uint32_t level, const uint64_t *__restrict__ keys,
+                                                                 const uint32_t *__restrict__ srcs, uint32_t num,
+                                                                 const uint32_t *__restrict__ seg_start,
+                                                                 const uint32_t *__restrict__ nseg_p, float alpha, uint32_t flush_nodes) {
+    reverse_merge_one<NCWIDE>(X, ld, lv, level, keys, srcs, num, seg_start, nseg_p, alpha, flush_nodes);
 }
 
 __global__ void fill_u32_kernel(uint32_t *p, size_t n, uint32_t v) {
@@ -501,16 +569,17 @@ static int link_level(Builder &b, const uint32_t *d_rows, uint32_t nq, uint32_t 
     leann_backend *h = b.h;
     const uint32_t efc = h->efc, msel = h->g.M; // M new links per point on every level (Malkov Alg. 1)
     const float alpha = h->kind == LEANN_BACKEND_DISKANN ? b.alpha_now : 0.f;
-    hipLaunchKernelGGL(select_kernel, dim3(nq), dim3(256), 0, b.st, h->g.X, h->g.ld, b.lv, d_rows, nq, level, ck, cd, cc,
-                       efc, msel, alpha, b.prop_key, b.prop_src, ek, ec, (uint32_t)EXPCAP);
+    const bool wide = std::max(h->g.M0, h->g.M) > 64; // lists of up to 128 ids: 256-candidate pools (NCWIDE)
+    hipLaunchKernelGGL(wide ? wide_select_kernel : select_kernel, dim3(nq), dim3(256), 0, b.st, h->g.X, h->g.ld, b.lv, d_rows, nq, level,
+                       ck, cd, cc, efc, msel, alpha, b.prop_key, b.prop_src, ek, ec, (uint32_t)EXPCAP);
     const uint32_t num = nq * msel;
     size_t tmp = b.cub_bytes;
     BCHECK(hipcub::DeviceRadixSort::SortPairs(b.cub_tmp, tmp, b.prop_key, b.prop_key2, b.prop_src, b.prop_src2, (int)num, 0, 64, b.st));
     BCHECK(hipMemsetAsync(b.nseg, 0, 4, b.st));
     hipLaunchKernelGGL(segment_heads_kernel, dim3((num + 255) / 256), dim3(256), 0, b.st, b.prop_key2, num, b.seg_start, b.nseg);
     uint32_t grid = std::min<uint32_t>(num, 256 * 16);
-    hipLaunchKernelGGL(reverse_merge_kernel, dim3(grid), dim3(256), 0, b.st, h->g.X, h->g.ld, b.lv, level, b.prop_key2,
-                       b.prop_src2, num, b.seg_start, b.nseg, alpha, 0u);
+    hipLaunchKernelGGL(wide ? wide_reverse_merge_kernel : reverse_merge_kernel, dim3(grid), dim3(256), 0, b.st, h->g.X, h->g.ld, b.lv,
+                       level, b.prop_key2, b.prop_src2, num, b.seg_start, b.nseg, alpha, 0u);
     BCHECK(hipGetLastError());
     return LEANN_OK;
 }
@@ -748,7 +817,8 @@ static int build_on_device(leann_backend *h, size_t n_existing, size_t bmax_hint
     b.alpha_now = h->alpha;
     if (rc == LEANN_OK && b.lv.P && n) { // fold what is still pending into the lists (DiskANN's final trim)
         const float alpha = h->alpha;
-        hipLaunchKernelGGL(reverse_merge_kernel, dim3(256 * 16), dim3(256), 0, b.st, h->g.X, h->g.ld, b.lv, 0u, (const uint64_t *)nullptr,
+        hipLaunchKernelGGL(std::max(h->g.M0, h->g.M) > 64 ? wide_reverse_merge_kernel : reverse_merge_kernel, dim3(256 * 16), dim3(256), 0,
+                           b.st, h->g.X, h->g.ld, b.lv, 0u, (const uint64_t *)nullptr,
                            (const uint32_t *)nullptr, 0u, (const uint32_t *)nullptr, (const uint32_t *)nullptr, alpha, (uint32_t)n);
         BCHECK(hipGetLastError());
         BCHECK(hipStreamSynchronize(b.st));
@@ -787,6 +857,16 @@ static constexpr uint64_t LEVEL_SEED = 0x5EED0003ull;
 
 static int build_device_impl(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld, size_t graph_degree, size_t complexity,
                              int device, uint64_t key_offset, int take_copy, leann_backend **out);
+// Lists hold at most 128 ids: HNSW graph_degree M in [2, 64] (level 0 keeps 2 M), DiskANN R in [2, 128].  Checked before any device work.
+static int check_degree(int backend, size_t graph_degree, size_t complexity) {
+    const size_t maxdeg = backend == LEANN_BACKEND_HNSW ? 64 : 128;
+    if (graph_degree < 2 || graph_degree > maxdeg || complexity < 1) {
+        leann_set_error("build: graph_degree must be in [2, %zu] (%s) and complexity >= 1 (got %zu, %zu)", maxdeg,
+                        backend == LEANN_BACKEND_HNSW ? "hnsw" : "diskann", graph_degree, complexity);
+        return LEANN_ERR_INVALID;
+    }
+    return LEANN_OK;
+}
 extern "C" int leann_backend_build_device(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld,
                                           size_t graph_degree, size_t complexity, int device, uint64_t key_offset,
                                           int take_copy, leann_backend **out) {
@@ -807,11 +887,7 @@ static int build_device_impl(int backend, const float *d_vectors, size_t n, size
         leann_set_error("Unknown backend: %d", backend);
         return LEANN_ERR_INVALID;
     }
-    const size_t maxdeg = backend == LEANN_BACKEND_HNSW ? 32 : 64;
-    if (graph_degree < 2 || graph_degree > maxdeg || complexity < 1) {
-        leann_set_error("build: graph_degree must be in [2, %zu] and complexity >= 1 (got %zu, %zu)", maxdeg, graph_degree, complexity);
-        return LEANN_ERR_INVALID;
-    }
+    if (int rc = check_degree(backend, graph_degree, complexity)) return rc;
     int ndev = 0;
     leann_device_count(&ndev);
     if (device < 0 || device >= ndev) {
@@ -861,6 +937,11 @@ extern "C" int leann_backend_build(int backend, const float *vectors, size_t n, 
         leann_set_error("leann_backend_build: invalid arguments");
         return LEANN_ERR_INVALID;
     }
+    if (backend != LEANN_BACKEND_HNSW && backend != LEANN_BACKEND_DISKANN) {
+        leann_set_error("Unknown backend: %d", backend);
+        return LEANN_ERR_INVALID;
+    }
+    if (int rc = check_degree(backend, graph_degree, complexity)) return rc;
     int ndev = 0;
     leann_device_count(&ndev);
     if (ndev < 1) {

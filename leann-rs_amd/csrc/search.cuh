@@ -9,7 +9,7 @@
 //   * result/candidate beam W: sorted u64 keys in LDS, double buffered, merged by rank;
 //   * visited set: open-addressing hash table in LDS; a query that outgrows it migrates, mid-search, to a pooled
 //     table in HBM (generation-tagged slots touched only by atomics) and continues;
-//   * per hop: wave 0 reads the adjacency list (one neighbour id per lane) and filters it through
+//   * per hop: wave 0 reads the adjacency list (LW neighbour ids per lane: ids l and 64 + l) and filters it through
 //     the visited table; the not-yet-seen rows are dealt round-robin to the NW waves, each wave
 //     streams a whole row per instruction group (64 lanes x 16 B = 1 KiB coalesced), R rows in
 //     flight, and reduces with the canonical wave tree (common.cuh);
@@ -263,11 +263,15 @@ __host__ __device__ inline size_t search_lds_bytes(uint32_t ef, uint32_t maxdeg,
 
 // G16 (recompute-on rows of 256 features only): phase C evaluates four rows per wave instruction (group_dist_rows_feat256), R = groups
 // in flight per wave.
-template <int T, int R, int NW, bool FEAT, bool FILT = false, bool G16 = false>
+// LW: adjacency-list ids per lane of wave 0 — 1 for lists of <= 64 ids, 2 for wide graphs (<= 128 ids: lane l holds ids l and 64 + l).
+// Phase B compacts the second half behind the first with a second ballot (the unseen ids keep list order), phase E reduces over both
+// keys of a lane and adds a second rank count; phases C and D already loop over n_new.  LW = 1 compiles to the narrow code unchanged.
+template <int T, int R, int NW, bool FEAT, bool FILT = false, bool G16 = false, int LW = 1>
 __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_t qi, unsigned char *smem) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const auto *const za = lazy_search_args(); // arguments of the rare paths and of the epilogue: read where they are used
     const uint32_t ef = a.ef;
+    static_assert(LW == 1 || LW == 2, "lists of at most 128 ids");
     const uint32_t maxdeg = g.M0 > g.M ? g.M0 : g.M;
     const uint32_t efp = (ef + 1) & ~1u;
     SearchLds s;
@@ -378,14 +382,17 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
         // of the throughput form is faster (recompute-on search: 3.05 against 2.98 M queries/s; hnsw10m equal; scripts/exp/ab.sh).
         constexpr bool EARLY_B = NW > 4;
         if constexpr (!EARLY_B) {
-            // Adjacency list of the NEXT node to expand, one neighbour id per lane of wave 0 (lists hold at most 64 ids).  The load is
+            // Adjacency list of the NEXT node to expand, LW neighbour ids per lane of wave 0 (lists hold at most 64 LW ids).  The load is
             // issued as soon as the next candidate is known — right after the new distances exist, BEFORE the merge (phase E below) —
             // so its HBM round trip runs under the merge and the barrier instead of at the head of the next hop.
-            uint32_t e_pref = LEANN_EMPTY;
+            uint32_t e_pref = LEANN_EMPTY, e_pref1 = LEANN_EMPTY; // e_pref1: ids 64..127 (LW = 2)
             // (level-dependent pieces of the list address as VALUES: selecting between the two struct members by address makes hipcc keep
             // the by-value GraphView in scratch memory)
             const uint32_t *const adj_base = lv == 0 ? adj0_p : adjU_p;
-            if (wave == 0) e_pref = (uint32_t)lane < deg ? adj_list(adj_base, upoff_p, deg, lv, key_id(best))[lane] : LEANN_EMPTY;
+            if (wave == 0) {
+                e_pref = (uint32_t)lane < deg ? adj_list(adj_base, upoff_p, deg, lv, key_id(best))[lane] : LEANN_EMPTY;
+                if constexpr (LW == 2) e_pref1 = (uint32_t)lane + 64u < deg ? adj_list(adj_base, upoff_p, deg, lv, key_id(best))[lane + 64] : LEANN_EMPTY;
+            }
             while (sel != LEANN_EMPTY) {
                 uint64_t *Wc = W0 + cur * efp, *Wn = W0 + (cur ^ 1) * efp;
     #ifdef LEANN_STAMPS // diagnostic build only (scripts/stamps.sh): where does a hop spend its cycles?
@@ -406,6 +413,14 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
                         uint32_t pos = __popcll(m & ((1ull << lane) - 1ull));
                         if (isnew) s.s_new[pos] = e;
                         n_new = __popcll(m);
+                        if constexpr (LW == 2) { // ids 64..127: a second ballot, compacted behind the first half's unseen ids
+                            const uint32_t e1 = e_pref1;
+                            bool isnew1 = false;
+                            if (e1 != LEANN_EMPTY) isnew1 = hbm ? vis_insert_hbm(gtab, gbits, gen, e1) : vis_insert_lds(table, hbits, e1);
+                            const unsigned long long m1 = __ballot(isnew1);
+                            if (isnew1) s.s_new[n_new + __popcll(m1 & ((1ull << lane) - 1ull))] = e1;
+                            n_new += __popcll(m1);
+                        }
                     }
                     n_vis += n_new;
                     n_evals += n_new;
@@ -545,15 +560,18 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
                         if (m) u = base + (uint32_t)__ffsll((long long)m) - 1u;
                     }
                     const uint64_t c_old = u != LEANN_EMPTY ? Wc[u] : ~0ull;
-                    const uint64_t kj = (uint32_t)lane < n_new ? s.s_key[lane] : ~0ull; // n_new <= 64: one key per lane
-                    const uint32_t hi = wave_min_u32((uint32_t)(kj >> 32));
-                    const uint32_t lo = wave_min_u32((uint32_t)(kj >> 32) == hi ? (uint32_t)kj : 0xFFFFFFFFu);
+                    const uint64_t kj = (uint32_t)lane < n_new ? s.s_key[lane] : ~0ull; // n_new <= 64 LW: LW keys per lane
+                    const uint64_t kj1 = LW == 2 && (uint32_t)lane + 64u < n_new ? s.s_key[lane + 64] : ~0ull;
+                    const uint64_t km = LW == 2 ? min(kj, kj1) : kj;
+                    const uint32_t hi = wave_min_u32((uint32_t)(km >> 32));
+                    const uint32_t lo = wave_min_u32((uint32_t)(km >> 32) == hi ? (uint32_t)km : 0xFFFFFFFFu);
                     const uint64_t c_new = n_new ? (((uint64_t)hi << 32) | lo) : ~0ull;
                     uint32_t next = LEANN_EMPTY, cnode = 0;
                     if (c_old != ~0ull || c_new != ~0ull) {
                         uint32_t rank;
                         if ((c_old >> 1) < (c_new >> 1)) {
                             rank = u + (uint32_t)__popcll(__ballot((kj >> 1) < (c_old >> 1)));
+                            if constexpr (LW == 2) rank += (uint32_t)__popcll(__ballot((kj1 >> 1) < (c_old >> 1)));
                             cnode = key_id(c_old);
     #ifdef LEANN_STAMPS
                             stamp[7] += 1;
@@ -569,8 +587,10 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
                         if (rank < ef_l) next = rank;
                     }
                     if (lane == 0) *next_slot = next;
-                    if (next != LEANN_EMPTY) // in flight across the merge and barrier B3
+                    if (next != LEANN_EMPTY) { // in flight across the merge and barrier B3
                         e_pref = (uint32_t)lane < deg ? adj_list(adj_base, upoff_p, deg, lv, cnode)[lane] : LEANN_EMPTY;
+                        if constexpr (LW == 2) e_pref1 = (uint32_t)lane + 64u < deg ? adj_list(adj_base, upoff_p, deg, lv, cnode)[lane + 64] : LEANN_EMPTY;
+                    }
                 } else {
                     // ---- phase D (waves 1 .. NW-1): merge by rank into the other buffer ---------------------------------
                     // One work item per old entry (rank = index + #new keys below it) and per new key (rank = #old below it, by
@@ -655,13 +675,13 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
             //   C  every wave: distances of the hop's unseen neighbours (rows in flight, wave-tree reductions)            | barrier
             //   E  wave 0: the NEXT candidate, known before the merge — the merged beam's first unexpanded entry is the smaller of the old
             //      beam's first unexpanded entry other than the one just expanded and the smallest new key; its index is the number of
-            //      keys below it — then that node's adjacency list (one id per lane, lists hold <= 64) through the visited table:
+            //      keys below it — then that node's adjacency list (LW ids per lane, lists hold <= 64 LW) through the visited table:
             //      phase B of the next hop, into the other parity's buffers
             //   D  waves 1 .. NW-1, meanwhile: merge by rank into the other beam buffer                                    | barrier
             // The adjacency round trip of hop h + 1 thus runs under the merge of hop h.  Exactly one candidate is expanded per step, in
             // the sequential order: same entry, same index as a scan of the merged list would give.
             const uint32_t *const adj_base = lv == 0 ? adj0_p : adjU_p; // (as VALUES: an address-select between struct members puts the by-value GraphView in scratch)
-            uint32_t e_pref = LEANN_EMPTY;
+            uint32_t e_pref = LEANN_EMPTY, e_pref1 = LEANN_EMPTY; // e_pref1: ids 64..127 (LW = 2)
             auto phase_b = [&](uint32_t p, uint64_t ckey, uint32_t hidx) __attribute__((always_inline)) { // wave 0
                 uint64_t *skey = s.s_key + p * kstride;
                 uint32_t *snew = s.s_new + p * maxdeg;
@@ -678,6 +698,14 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
                     const uint32_t pos = __popcll(m & ((1ull << lane) - 1ull));
                     if (isnew) snew[pos] = e;
                     n_new = __popcll(m);
+                    if constexpr (LW == 2) { // ids 64..127: a second ballot, compacted behind the first half's unseen ids
+                        const uint32_t e1 = e_pref1;
+                        bool isnew1 = false;
+                        if (e1 != LEANN_EMPTY) isnew1 = hbm ? vis_insert_hbm(gtab, gbits, gen, e1) : vis_insert_lds(table, hbits, e1);
+                        const unsigned long long m1 = __ballot(isnew1);
+                        if (isnew1) snew[n_new + __popcll(m1 & ((1ull << lane) - 1ull))] = e1;
+                        n_new += __popcll(m1);
+                    }
                 }
                 n_vis += n_new;
                 n_evals += n_new;
@@ -691,6 +719,7 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
             };
             if (wave == 0) {
                 e_pref = (uint32_t)lane < deg ? adj_list(adj_base, upoff_p, deg, lv, key_id(best))[lane] : LEANN_EMPTY;
+                if constexpr (LW == 2) e_pref1 = (uint32_t)lane + 64u < deg ? adj_list(adj_base, upoff_p, deg, lv, key_id(best))[lane + 64] : LEANN_EMPTY;
                 phase_b(0u, best, 0u);
             }
             __syncthreads();
@@ -843,9 +872,11 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
                         if (m) u = base + (uint32_t)__ffsll((long long)m) - 1u;
                     }
                     const uint64_t c_old = u != LEANN_EMPTY ? Wc[u] : ~0ull;
-                    const uint64_t kj = (uint32_t)lane < n_new ? skey[lane] : ~0ull; // n_new <= 64: one key per lane
-                    const uint32_t hi = wave_min_u32((uint32_t)(kj >> 32));
-                    const uint32_t lo = wave_min_u32((uint32_t)(kj >> 32) == hi ? (uint32_t)kj : 0xFFFFFFFFu);
+                    const uint64_t kj = (uint32_t)lane < n_new ? skey[lane] : ~0ull; // n_new <= 64 LW: LW keys per lane
+                    const uint64_t kj1 = LW == 2 && (uint32_t)lane + 64u < n_new ? skey[lane + 64] : ~0ull;
+                    const uint64_t km = LW == 2 ? min(kj, kj1) : kj;
+                    const uint32_t hi = wave_min_u32((uint32_t)(km >> 32));
+                    const uint32_t lo = wave_min_u32((uint32_t)(km >> 32) == hi ? (uint32_t)km : 0xFFFFFFFFu);
                     const uint64_t c_new = n_new ? (((uint64_t)hi << 32) | lo) : ~0ull;
                     uint32_t next = LEANN_EMPTY;
                     uint64_t ckey = 0;
@@ -853,6 +884,7 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
                         uint32_t rank;
                         if ((c_old >> 1) < (c_new >> 1)) {
                             rank = u + (uint32_t)__popcll(__ballot((kj >> 1) < (c_old >> 1)));
+                            if constexpr (LW == 2) rank += (uint32_t)__popcll(__ballot((kj1 >> 1) < (c_old >> 1)));
                             ckey = c_old;
 #ifdef LEANN_STAMPS
                             stamp[7] += 1;
@@ -870,6 +902,7 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
                     if (lane == 0) *next_slot = next;
                     if (next != LEANN_EMPTY) {
                         e_pref = (uint32_t)lane < deg ? adj_list(adj_base, upoff_p, deg, lv, key_id(ckey))[lane] : LEANN_EMPTY;
+                        if constexpr (LW == 2) e_pref1 = (uint32_t)lane + 64u < deg ? adj_list(adj_base, upoff_p, deg, lv, key_id(ckey))[lane + 64] : LEANN_EMPTY;
                         phase_b(par ^ 1u, ckey, hop + 1); // waits for the list while the other waves merge
                     }
                 } else {
@@ -1087,4 +1120,51 @@ __global__ void __launch_bounds__(NW * 64, (NW == 4 && T == 1) ? LEANN_FEAT_OCC 
     uint32_t qi = blockIdx.x;
     if (qi >= a.nq) return;
     beam_search_one<T, R, NW, true>(g, a, qi, smem);
+}
+
+// Wide graphs (M0 or M > 64, lists of up to 128 ids: HNSW M <= 64, DiskANN R <= 128): the same kernels with two list ids per lane of
+// wave 0 (LW = 2 above).  Separate templates, so the narrow kernels keep their symbols and code objects; api.hip dispatches here only
+// when max(M, M0) > 64.  No occupancy requests: wide lists double a hop's unseen neighbours and the tuning above was measured on
+// narrow graphs.
+template <int T, int R, int NW, bool BUILD>
+__global__ void __launch_bounds__(NW * 64) wide_beam_search_kernel(GraphView g, SearchArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t qi = blockIdx.x;
+    if (qi >= a.nq) return;
+    beam_search_one<T, R, NW, false, false, false, 2>(g, a, qi, smem);
+}
+template <int T, int R, int NW>
+__global__ void __launch_bounds__(NW * 64) wide_beam_search_filtered_kernel(GraphView g, SearchArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t qi = blockIdx.x;
+    if (qi >= a.nq) return;
+    beam_search_one<T, R, NW, false, true, false, 2>(g, a, qi, smem);
+}
+template <int T, int R, int NW>
+__global__ void __launch_bounds__(NW * 64) wide_beam_search_feat_kernel(GraphView g, SearchArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t qi = blockIdx.x;
+    if (qi >= a.nq) return;
+    beam_search_one<T, R, NW, true, false, false, 2>(g, a, qi, smem);
+}
+template <int T, int R, int NW>
+__global__ void __launch_bounds__(NW * 64) wide_beam_search_feat_filtered_kernel(GraphView g, SearchArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t qi = blockIdx.x;
+    if (qi >= a.nq) return;
+    beam_search_one<T, R, NW, true, true, false, 2>(g, a, qi, smem);
+}
+template <int G, int NW>
+__global__ void __launch_bounds__(NW * 64) wide_beam_search_feat256_kernel(GraphView g, SearchArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t qi = blockIdx.x;
+    if (qi >= a.nq) return;
+    beam_search_one<1, G, NW, true, false, true, 2>(g, a, qi, smem);
+}
+template <int G, int NW>
+__global__ void __launch_bounds__(NW * 64) wide_beam_search_feat256_filtered_kernel(GraphView g, SearchArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t qi = blockIdx.x;
+    if (qi >= a.nq) return;
+    beam_search_one<1, G, NW, true, true, true, 2>(g, a, qi, smem);
 }
