@@ -283,11 +283,50 @@ int leann_merge_topk_device(const uint64_t *d_keys, const float *d_dists, const 
  * BM25 scores arrive SPARSE, as the host's Bm25Scorer::search produces them: per query `d_bm25_count[q]` positives (position, score),
  * sorted by score descending, ties by position ascending (Rust's stable sort, bm25.rs:118), rows `bm25_stride` entries apart; every
  * other passage scores 0.0.  compat_polarity != 0: the backend's DISTANCES enter the blend as the reference has it (the
- * worst ANN hit gets the largest vector term); 0: corrected, 1 - dist.  fetch_k <= 256. */
+ * worst ANN hit gets the largest vector term); 0: corrected, 1 - dist.  fetch_k <= 256.  Positives beyond `bm25_stride` are dropped
+ * (P = min(count, stride): min_b / max_b and the scores then differ from the reference's); leann_bm25_hybrid_rerank_device below is
+ * the call without that limit. */
 int leann_hybrid_rerank_device(const uint64_t *d_keys, const float *d_dists, const uint32_t *d_counts, size_t nq, size_t fetch_k,
                                const uint32_t *d_bm25_pos, const float *d_bm25_score, const uint32_t *d_bm25_count,
                                size_t bm25_stride, size_t n_docs, float alpha, int compat_polarity, size_t top_k,
                                uint64_t *d_out_keys, float *d_out_scores, uint32_t *d_out_counts, void *stream);
+
+/* ---- BM25 on the device (src/index/bm25.rs:77-122 for batches of queries; DESIGN.md "BM25 on the device") ---------------------------
+ * An inverted index in HBM: CSR postings — post_off [n_terms + 1], post_doc (passage positions, strictly ascending within a term's
+ * list), post_tf (> 0) — plus the passage lengths; the arrays are host pointers, copied at creation.  A query is its KNOWN tokens in
+ * query order (a repeated token appears twice, an unknown one not at all), each with its term id and its idf
+ * ln((N - df + 0.5) / (df + 0.5) + 1) computed on the host with libm's logf (bm25.rs:88): the device's logf differs in the last bit.
+ * Scores are the reference's f32 arithmetic bit for bit: per passage the contributions idf * (tf * (K1 + 1)) / (tf + K1 * norm) are
+ * added in query-token order.  Every argument is validated before any device work (LEANN_ERR_INVALID with a message naming it); the
+ * checks of the query arrays are also callable on their own (leann_bm25_check_queries), with no handle and no device.
+ * A handle serves one batch at a time (calls on one handle serialise) and holds `leann_bm25_slots` dense accumulators of n_docs
+ * floats, sized from a fixed 1 GiB budget (at most 64); a batch is processed in chunks of that many queries.  The *_device calls
+ * enqueue on `stream` and return after the stream has finished the batch.  Keys are global positions: the lists of a sharded handle
+ * live on the first device of its list, and a BM25 handle created on that device reranks them unchanged. */
+typedef struct leann_bm25 leann_bm25;
+int leann_bm25_create(size_t n_docs, size_t n_terms, const uint64_t *post_off, const uint32_t *post_doc, const uint32_t *post_tf,
+                      const uint32_t *doc_len, float avg_doc_len, int device, leann_bm25 **out);
+size_t leann_bm25_len(const leann_bm25 *b);
+size_t leann_bm25_slots(const leann_bm25 *b);
+void leann_bm25_close(leann_bm25 *b);
+/* q_off [nq + 1] from 0, monotone; q_term < n_terms; q_idf finite and >= 0 */
+int leann_bm25_check_queries(size_t n_terms, size_t nq, const uint32_t *q_off, const uint32_t *q_term, const float *q_idf);
+/* Bm25Scorer::search for nq queries: query i has tokens q_term / q_idf [q_off[i], q_off[i + 1]) in query order (host pointers).
+ * pos / scores [nq x top_k]: the positives (> 0.0), score descending, ties by position ascending, unused tail UINT32_MAX / -inf;
+ * counts [nq]; optional n_positive [nq] = number of positives, min_max [nq x 2] = min and max over ALL n_docs scores.
+ * top_k <= 1024. */
+int leann_bm25_search_batch(const leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint32_t *q_term, const float *q_idf,
+                            size_t top_k, uint32_t *pos, float *scores, uint32_t *counts, uint32_t *n_positive, float *min_max);
+int leann_bm25_search_batch_device(const leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint32_t *q_term, const float *q_idf,
+                                   size_t top_k, uint32_t *d_pos, float *d_scores, uint32_t *d_counts, uint32_t *d_n_positive,
+                                   float *d_min_max, void *stream);
+/* scoring + BM25-only injection + hybrid_rerank (see leann_hybrid_rerank_device) on the lists a search_batch_device call with
+ * top_k = fetch_k left in HBM; the BM25 score of a merged key is read from the query's dense score vector, so there is no limit
+ * on the number of positives.  fetch_k <= 256, top_k <= 512, alpha in [0, 1]. */
+int leann_bm25_hybrid_rerank_device(const leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint32_t *q_term, const float *q_idf,
+                                    const uint64_t *d_keys, const float *d_dists, const uint32_t *d_counts, size_t fetch_k,
+                                    float alpha, int compat_polarity, size_t top_k,
+                                    uint64_t *d_out_keys, float *d_out_scores, uint32_t *d_out_counts, void *stream);
 
 /* ---- sharded indexes (the reference has no counterpart: IndexSearcher owns one Box<dyn BackendSearcher>,
  * src/index/searcher.rs:68) --------------------------------------------------------------------------------------------------

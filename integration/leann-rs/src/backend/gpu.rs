@@ -20,9 +20,29 @@ pub struct LeannBackend {
     _p: [u8; 0],
 }
 
+#[repr(C)]
+pub struct LeannBm25 {
+    _p: [u8; 0],
+}
+
 #[link(name = "leann_hip")]
 extern "C" {
     fn leann_last_error() -> *const c_char;
+    // BM25 on the device: Bm25Scorer's tables as CSR postings in HBM; a query is its known tokens (term id, idf) in
+    // token order.  src/index/searcher.rs:153-167 then becomes one leann_bm25_hybrid_rerank_device call on the backend's lists.
+    #[allow(dead_code)]
+    pub fn leann_bm25_create(n_docs: usize, n_terms: usize, post_off: *const u64, post_doc: *const u32, post_tf: *const u32,
+                             doc_len: *const u32, avg_doc_len: f32, device: c_int, out: *mut *mut LeannBm25) -> c_int;
+    #[allow(dead_code)]
+    pub fn leann_bm25_search_batch(b: *const LeannBm25, nq: usize, q_off: *const u32, q_term: *const u32, q_idf: *const f32, top_k: usize,
+                                   pos: *mut u32, scores: *mut f32, counts: *mut u32, n_positive: *mut u32, min_max: *mut f32) -> c_int;
+    #[allow(dead_code)]
+    pub fn leann_bm25_hybrid_rerank_device(b: *const LeannBm25, nq: usize, q_off: *const u32, q_term: *const u32, q_idf: *const f32,
+                                           d_keys: *const u64, d_dists: *const f32, d_counts: *const u32, fetch_k: usize, alpha: f32,
+                                           compat_polarity: c_int, top_k: usize, d_out_keys: *mut u64, d_out_scores: *mut f32,
+                                           d_out_counts: *mut u32, stream: *mut std::ffi::c_void) -> c_int;
+    #[allow(dead_code)]
+    pub fn leann_bm25_close(b: *mut LeannBm25);
     fn leann_backend_open(stem: *const c_char, backend: c_int, dims: usize, device_spec: *const c_char,
                           out: *mut *mut LeannBackend) -> c_int;
     fn leann_backend_search(h: *const LeannBackend, query: *const f32, top_k: usize, complexity: usize,

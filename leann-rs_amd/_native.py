@@ -37,6 +37,15 @@ SIGNATURES = {
     "leann_backend_shard": (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
     "leann_hybrid_rerank_device": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp, C.c_size_t, C.c_size_t, C.c_float, C.c_int,
                                             C.c_size_t, vp, vp, vp, vp]),
+    "leann_bm25_create": (C.c_int, [C.c_size_t, C.c_size_t, u64p, u32p, u32p, u32p, C.c_float, C.c_int, C.POINTER(vp)]),
+    "leann_bm25_len": (C.c_size_t, [vp]),
+    "leann_bm25_slots": (C.c_size_t, [vp]),
+    "leann_bm25_close": (None, [vp]),
+    "leann_bm25_check_queries": (C.c_int, [C.c_size_t, C.c_size_t, u32p, u32p, f32p]),
+    "leann_bm25_search_batch": (C.c_int, [vp, C.c_size_t, u32p, u32p, f32p, C.c_size_t, u32p, f32p, u32p, u32p, f32p]),
+    "leann_bm25_search_batch_device": (C.c_int, [vp, C.c_size_t, u32p, u32p, f32p, C.c_size_t, vp, vp, vp, vp, vp, vp]),
+    "leann_bm25_hybrid_rerank_device": (C.c_int, [vp, C.c_size_t, u32p, u32p, f32p, vp, vp, vp, C.c_size_t, C.c_float, C.c_int,
+                                                 C.c_size_t, vp, vp, vp, vp]),
     "leann_backend_open": (C.c_int, [C.c_char_p, C.c_int, C.c_size_t, C.c_char_p, C.POINTER(vp)]),
     "leann_backend_search": (C.c_int, [vp, f32p, C.c_size_t, C.c_size_t, u64p, f32p, C.POINTER(C.c_size_t)]),
     "leann_backend_search_batch": (C.c_int, [vp, f32p, C.c_size_t, C.c_size_t, C.c_size_t, u64p, f32p, u32p]),

@@ -1,0 +1,174 @@
+"""Bm25Index — the device-resident BM25 inverted index (csrc/bm25.hip) behind ctypes.
+
+Tokenisation, the term dictionary and the idf of a query term are host work (strings, and libm's logf: src/index/bm25.rs:88,
+:127-132); scoring, selection and the hybrid rerank run on the device, bit for bit the reference's f32 arithmetic."""
+import ctypes as C
+import ctypes.util
+import re
+
+import numpy as np
+
+from . import _native as N
+from .device import DeviceArray
+
+_TOKEN = re.compile(r"[a-zA-Z0-9]+")
+_libm = C.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+_libm.logf.restype = C.c_float
+_libm.logf.argtypes = [C.c_float]
+f32 = np.float32
+
+
+def tokenize(text):
+    """bm25.rs:127-132: [a-zA-Z0-9]+, lowercased, one-character tokens dropped"""
+    return [m.group(0).lower() for m in _TOKEN.finditer(text) if len(m.group(0)) > 1]
+
+
+def idf(num_docs, df):
+    """bm25.rs:88 in f32, ln through libm's logf"""
+    df = f32(df)
+    ratio = f32(f32(f32(num_docs) - df) + f32(0.5)) / f32(df + f32(0.5))
+    return f32(_libm.logf(float(f32(ratio + f32(1.0)))))
+
+
+def _p(a, t):
+    return a.ctypes.data_as(C.POINTER(t))
+
+
+class Bm25Index:
+    def __init__(self, handle, n_docs, post_off, vocab=None):
+        self._h = handle
+        self.n_docs = int(n_docs)
+        self.post_off = post_off
+        self.n_terms = len(post_off) - 1
+        self.vocab = vocab  # token -> term id (from_texts only)
+
+    @classmethod
+    def from_postings(cls, n_docs, post_off, post_doc, post_tf, doc_len, avg_doc_len, device=0, vocab=None):
+        post_off = np.ascontiguousarray(post_off, np.uint64)
+        post_doc = np.ascontiguousarray(post_doc, np.uint32)
+        post_tf = np.ascontiguousarray(post_tf, np.uint32)
+        doc_len = np.ascontiguousarray(doc_len, np.uint32)
+        if post_off.ndim != 1 or len(post_off) < 1:
+            raise N.LeannError(1, "Bm25Index.from_postings: post_off must hold n_terms + 1 offsets")
+        if len(doc_len) != n_docs:
+            raise N.LeannError(1, f"Bm25Index.from_postings: doc_len has {len(doc_len)} entries, n_docs is {n_docs}")
+        if len(post_doc) != len(post_tf) or int(post_off[-1]) != len(post_doc):
+            raise N.LeannError(1, f"Bm25Index.from_postings: post_off ends at {int(post_off[-1])}, not at the posting count "
+                                  f"{len(post_doc)} (post_tf: {len(post_tf)})")
+        h = C.c_void_p()
+        N.check(N.lib().leann_bm25_create(n_docs, len(post_off) - 1, _p(post_off, C.c_uint64), _p(post_doc, C.c_uint32),
+                                          _p(post_tf, C.c_uint32), _p(doc_len, C.c_uint32), float(f32(avg_doc_len)), device, C.byref(h)))
+        return cls(h, n_docs, post_off, vocab)
+
+    @staticmethod
+    def postings_from_texts(texts):
+        """Bm25Scorer::build (bm25.rs:33-74) as CSR: term ids in order of first appearance, passages ascending within a list.
+        Returns (vocab, post_off, post_doc, post_tf, doc_len, avg_doc_len)."""
+        vocab, lists, doc_len, total = {}, [], [], 0
+        for doc, text in enumerate(texts):
+            toks = tokenize(text)
+            doc_len.append(len(toks))
+            total += len(toks)
+            tf = {}
+            for t in toks:
+                tf[t] = tf.get(t, 0) + 1
+            for t, c in tf.items():
+                tid = vocab.setdefault(t, len(vocab))
+                if tid == len(lists):
+                    lists.append([])
+                lists[tid].append((doc, c))
+        post_off = np.zeros(len(lists) + 1, np.uint64)
+        post_off[1:] = np.cumsum([len(x) for x in lists], dtype=np.uint64)
+        flat = [p for x in lists for p in x]
+        post_doc = np.array([d for d, _ in flat], np.uint32)
+        post_tf = np.array([c for _, c in flat], np.uint32)
+        avg = f32(total) / f32(len(texts)) if len(texts) else f32(1.0)
+        return vocab, post_off, post_doc, post_tf, np.array(doc_len, np.uint32), avg
+
+    @classmethod
+    def from_texts(cls, texts, device=0):
+        vocab, post_off, post_doc, post_tf, doc_len, avg = cls.postings_from_texts(texts)
+        return cls.from_postings(len(texts), post_off, post_doc, post_tf, doc_len, avg, device, vocab)
+
+    def query_terms(self, text):
+        """(term id, idf) of the query's known tokens, in token order (repeats kept, unknown tokens skipped: bm25.rs:81-90)"""
+        if self.vocab is None:
+            raise N.LeannError(1, "Bm25Index.query_terms: the index was made from postings, it has no term dictionary")
+        out = []
+        for t in tokenize(text):
+            tid = self.vocab.get(t)
+            if tid is None:
+                continue
+            out.append((tid, idf(self.n_docs, int(self.post_off[tid + 1]) - int(self.post_off[tid]))))
+        return out
+
+    def idf_of(self, term_ids):
+        return np.array([idf(self.n_docs, int(self.post_off[t + 1]) - int(self.post_off[t])) for t in term_ids], np.float32)
+
+    @staticmethod
+    def pack_queries(queries):
+        """list of [(term id, idf), ...] -> (q_off, q_term, q_idf)"""
+        q_off = np.zeros(len(queries) + 1, np.uint32)
+        q_off[1:] = np.cumsum([len(q) for q in queries], dtype=np.uint64)
+        q_term = np.array([t for q in queries for t, _ in q], np.uint32)
+        q_idf = np.array([w for q in queries for _, w in q], np.float32)
+        return q_off, q_term, q_idf
+
+    def _queries(self, queries):
+        if isinstance(queries, tuple) and len(queries) == 3:
+            q_off, q_term, q_idf = (np.ascontiguousarray(a, t) for a, t in zip(queries, (np.uint32, np.uint32, np.float32)))
+        else:
+            q_off, q_term, q_idf = self.pack_queries([self.query_terms(q) if isinstance(q, str) else q for q in queries])
+        return len(q_off) - 1, q_off, q_term, q_idf
+
+    @property
+    def slots(self):
+        return int(N.lib().leann_bm25_slots(self._h))
+
+    def __len__(self):
+        return int(N.lib().leann_bm25_len(self._h))
+
+    def search_batch(self, queries, top_k):
+        """Bm25Scorer::search per query.  queries: texts, lists of (term id, idf), or packed (q_off, q_term, q_idf).
+        Returns pos [nq x top_k] u32, scores [nq x top_k] f32, counts [nq], n_positive [nq], min_max [nq x 2]."""
+        nq, q_off, q_term, q_idf = self._queries(queries)
+        pos = np.full((nq, top_k), 0xFFFFFFFF, np.uint32)
+        sc = np.full((nq, top_k), -np.inf, np.float32)
+        cnt, npos, mm = np.zeros(nq, np.uint32), np.zeros(nq, np.uint32), np.zeros((nq, 2), np.float32)
+        N.check(N.lib().leann_bm25_search_batch(self._h, nq, _p(q_off, C.c_uint32), _p(q_term, C.c_uint32), _p(q_idf, C.c_float), top_k,
+                                                _p(pos, C.c_uint32), _p(sc, C.c_float), _p(cnt, C.c_uint32), _p(npos, C.c_uint32),
+                                                _p(mm, C.c_float)))
+        return pos, sc, cnt, npos, mm
+
+    def search_batch_device(self, queries, top_k, stream=None, out=None):
+        """search_batch with the results left in HBM: DeviceArrays (pos u32 [nq x top_k], scores f32, counts u32 [nq],
+        n_positive u32 [nq], min_max f32 [nq x 2]); `out` reuses the arrays of an earlier call of the same shape."""
+        nq, q_off, q_term, q_idf = self._queries(queries)
+        if out is None:
+            out = (DeviceArray((nq, top_k), np.uint32), DeviceArray((nq, top_k), np.float32), DeviceArray(nq, np.uint32),
+                   DeviceArray(nq, np.uint32), DeviceArray((nq, 2), np.float32))
+        N.check(N.lib().leann_bm25_search_batch_device(self._h, nq, _p(q_off, C.c_uint32), _p(q_term, C.c_uint32), _p(q_idf, C.c_float), top_k,
+                                                       out[0].ptr, out[1].ptr, out[2].ptr, out[3].ptr, out[4].ptr, stream))
+        return out
+
+    def hybrid_rerank_device(self, queries, d_keys, d_dists, d_counts, fetch_k, alpha, compat_polarity, top_k, stream=None):
+        """The hybrid leg on lists in HBM (DeviceArrays or raw pointers: keys u64 / dists f32 [nq x fetch_k], counts u32 [nq]).
+        Returns DeviceArrays (keys [nq x top_k] u64, scores f32, counts u32)."""
+        nq, q_off, q_term, q_idf = self._queries(queries)
+        ptr = lambda a: a.ptr if isinstance(a, DeviceArray) else a  # noqa: E731
+        ok, os_, oc = DeviceArray((nq, top_k), np.uint64), DeviceArray((nq, top_k), np.float32), DeviceArray(nq, np.uint32)
+        N.check(N.lib().leann_bm25_hybrid_rerank_device(self._h, nq, _p(q_off, C.c_uint32), _p(q_term, C.c_uint32), _p(q_idf, C.c_float),
+                                                        ptr(d_keys), ptr(d_dists), ptr(d_counts), fetch_k, alpha,
+                                                        1 if compat_polarity else 0, top_k, ok.ptr, os_.ptr, oc.ptr, stream))
+        return ok, os_, oc
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lib().leann_bm25_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

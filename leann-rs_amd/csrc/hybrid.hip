@@ -21,8 +21,7 @@
 #include "../../include/leann_backend.h"
 #include "internal.h"
 
-#define HYB_MAX_FETCH 256
-#define HYB_MAX_MERGED (2 * HYB_MAX_FETCH)
+#include "hybrid_rerank.cuh" // the rerank body, shared with the dense-accumulator caller in bm25.hip
 
 __global__ void __launch_bounds__(256) hybrid_rerank_kernel(const uint64_t *__restrict__ keys, const float *__restrict__ dists,
                                                             const uint32_t *__restrict__ counts, uint32_t fetch_k,
@@ -30,93 +29,10 @@ __global__ void __launch_bounds__(256) hybrid_rerank_kernel(const uint64_t *__re
                                                             const uint32_t *__restrict__ bm_count, uint32_t bm_stride, uint64_t n_docs,
                                                             float alpha, int compat, uint32_t top_k, uint64_t *__restrict__ out_keys,
                                                             float *__restrict__ out_scores, uint32_t *__restrict__ out_counts) {
-    __shared__ uint64_t m_key[HYB_MAX_MERGED];
-    __shared__ float m_v[HYB_MAX_MERGED];
-    __shared__ float m_score[HYB_MAX_MERGED];
-    __shared__ uint64_t s_sort[HYB_MAX_MERGED];
-    __shared__ uint32_t s_inj[HYB_MAX_FETCH];
-    __shared__ uint32_t s_minv, s_maxv, s_minb, s_maxb, s_m;
-    const uint32_t q = blockIdx.x, tid = threadIdx.x;
-    const uint32_t n = min(counts[q], fetch_k);
-    const uint32_t P = min(bm_count[q], bm_stride);
-    const uint32_t top = min(P, fetch_k); // bm25_top = the first fetch_k positives (searcher.rs:154)
-    const uint32_t *bp = bm_pos + (size_t)q * bm_stride;
-    const float *bs = bm_score + (size_t)q * bm_stride;
-    if (tid == 0) { s_minv = 0xFFFFFFFFu; s_maxv = 0u; s_minb = 0xFFFFFFFFu; s_maxb = 0u; }
-    for (uint32_t i = tid; i < n; i += 256) {
-        const float d = dists[(size_t)q * fetch_k + i];
-        m_key[i] = keys[(size_t)q * fetch_k + i];
-        m_v[i] = compat ? d : 1.0f - d;
-    }
-    __syncthreads();
-    // BM25-only hits: positives of bm25_top that the backend did not return, appended in bm25_top order with vector score 0.0
-    for (uint32_t t = tid; t < top; t += 256) {
-        const uint64_t pos = bp[t];
-        uint32_t found = 0;
-        for (uint32_t i = 0; i < n; i++) found |= (m_key[i] == pos);
-        s_inj[t] = found ? 0u : 1u;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t m = n;
-        for (uint32_t t = 0; t < top; t++)
-            if (s_inj[t]) { m_key[m] = bp[t]; m_v[m] = 0.0f; m++; }
-        s_m = m;
-    }
-    __syncthreads();
-    const uint32_t m = s_m;
-    // f32::max / f32::min folds (bm25.rs:140-147, :152-154) — order-independent for non-NaN values
-    for (uint32_t i = tid; i < m; i += 256) {
-        const uint32_t o = f32_orderable(m_v[i]);
-        atomicMin(&s_minv, o);
-        atomicMax(&s_maxv, o);
-    }
-    for (uint32_t t = tid; t < P; t += 256) {
-        const uint32_t o = f32_orderable(bs[t]);
-        atomicMin(&s_minb, o);
-        atomicMax(&s_maxb, o);
-    }
-    if (tid == 0 && (uint64_t)P < n_docs) { // every passage without a term of the query scores 0.0
-        const uint32_t z = f32_orderable(0.0f);
-        atomicMin(&s_minb, z);
-        atomicMax(&s_maxb, z);
-    }
-    __syncthreads();
-    const float min_v = orderable_f32(s_minv), max_v = orderable_f32(s_maxv);
-    const float min_b = orderable_f32(s_minb), max_b = orderable_f32(s_maxb);
-    const float v_range = fmaxf(max_v - min_v, 1e-6f), b_range = fmaxf(max_b - min_b, 1e-6f);
-    const float one_minus_alpha = 1.0f - alpha;
-    for (uint32_t i = tid; i < HYB_MAX_MERGED; i += 256) {
-        uint64_t sk = ~0ull;
-        if (i < m) {
-            const uint64_t key = m_key[i];
-            float bm = 0.0f; // bm25_scores[idx], 0.0 beyond the vector (bm25.rs:158)
-            for (uint32_t t = 0; t < P; t++)
-                if ((uint64_t)bp[t] == key) bm = bs[t];
-            const float norm_vec = (m_v[i] - min_v) / v_range;
-            const float norm_b = (bm - min_b) / b_range;
-            const float t1 = alpha * norm_vec, t2 = one_minus_alpha * norm_b;
-            const float sc = t1 + t2;
-            m_score[i] = sc;
-            sk = ((uint64_t)(~f32_orderable(sc)) << 32) | i; // ascending = score descending, ties in list order: Rust's stable sort_by
-        }
-        s_sort[i] = sk;
-    }
-    int npow = 2;
-    while (npow < (int)m) npow <<= 1;
-    bitonic_sort_lds(s_sort, npow); // (entries >= m are ~0 and npow <= HYB_MAX_MERGED)
-    const uint32_t nout = min(m, top_k);
-    for (uint32_t j = tid; j < top_k; j += 256) {
-        if (j < nout) {
-            const uint32_t i = (uint32_t)s_sort[j];
-            out_keys[(size_t)q * top_k + j] = m_key[i];
-            out_scores[(size_t)q * top_k + j] = m_score[i];
-        } else {
-            out_keys[(size_t)q * top_k + j] = ~0ull;
-            out_scores[(size_t)q * top_k + j] = -INFINITY;
-        }
-    }
-    if (tid == 0) out_counts[q] = nout;
+    const uint32_t q = blockIdx.x;
+    // positives beyond the stride are not there to be read: P = min(count, stride)
+    const HybSparseBm bm{bm_pos + (size_t)q * bm_stride, bm_score + (size_t)q * bm_stride, min(bm_count[q], bm_stride), n_docs};
+    hybrid_rerank_body(bm, keys, dists, counts, fetch_k, alpha, compat, top_k, out_keys, out_scores, out_counts, q);
 }
 
 extern "C" int leann_hybrid_rerank_device(const uint64_t *d_keys, const float *d_dists, const uint32_t *d_counts, size_t nq, size_t fetch_k,

@@ -26,6 +26,8 @@ struct SearchArgs {
     std::optional<std::string> query_prompt_template, embedding_mode, query_vector_file;
     std::string device = getenv("LEANN_DEVICES") ? getenv("LEANN_DEVICES") : "0"; // "0", or a list / range = sharded (leann_backend.h)
     bool device_filter = false;
+    bool bm25_device = true;
+    std::optional<std::string> queries_file;
 };
 
 static void usage_search() {
@@ -48,6 +50,9 @@ static void usage_search() {
          "      --query-vector-file <FILE>     (additive) raw f32 query embedding instead of embedding the query text\n"
          "      --device <SPEC>                (additive) HIP device ordinal, or a list / range (\"0-7\") = index sharded over several GPUs [env: LEANN_DEVICES] [default: 0]\n"
          "      --device-filter                (additive) evaluate --filter inside the GPU traversal instead of 5x over-fetch + post-filter\n"
+         "      --queries-file <FILE>          (additive) one query per line instead of <QUERY>: the batch is searched in one backend call and,\n"
+         "                                     with --hybrid, one device BM25 + rerank call; prints a JSON array with one result array per query\n"
+         "      --bm25 <WHERE>                 (additive) where hybrid mode scores BM25: device (inverted index in HBM) or host; same output [default: device] [possible values: device, host]\n"
          "  -h, --help                         Print help");
 }
 
@@ -87,12 +92,14 @@ static int run_search(int argc, char **argv) {
         else if (name == "--embedding-mode") a.embedding_mode = val();
         else if (name == "--query-vector-file") a.query_vector_file = val();
         else if (name == "--device") a.device = val();
+        else if (name == "--queries-file") a.queries_file = val();
+        else if (name == "--bm25") { std::string w = val(); if (w != "device" && w != "host") throw Error("invalid value '" + w + "' for '--bm25 <WHERE>' [possible values: device, host]"); a.bm25_device = w == "device"; }
         else if (name == "-v" || name == "--verbose" || name == "-q" || name == "--quiet") {}
         else if (!s.empty() && s[0] == '-' && s.size() > 1) throw Error("unexpected argument '" + s + "' found");
         else if (!have_query) { a.query = s; have_query = true; }
         else throw Error("unexpected argument '" + s + "' found");
     }
-    if (!have_query) throw Error("the following required arguments were not provided:\n  <QUERY>");
+    if (!have_query && !a.queries_file) throw Error("the following required arguments were not provided:\n  <QUERY>");
 
     // search.rs:75-88
     std::string index_name;
@@ -141,6 +148,42 @@ static int run_search(int argc, char **argv) {
         return EmbeddingProvider(mode, meta.dimensions).embed_with_template({text}, query_template)[0];
     };
 
+    auto results_json = [](const std::vector<SearchResult> &rs) { // search.rs:211-223
+        lj::Value arr = lj::Value::array();
+        for (auto &r : rs) {
+            lj::Value o = lj::Value::object();
+            o["id"] = lj::Value::string(r.id);
+            o["score"] = lj::Value::number((double)r.score); // f32 widened, like serde_json's From<f32>
+            o["text"] = lj::Value::string(r.text);
+            o["metadata"] = r.metadata;
+            arr.a->push_back(o);
+        }
+        return arr;
+    };
+    if (a.queries_file) { // additive: IndexSearcher::search_batch_with_options; hybrid mode is what --hybrid says, for every query
+        if (is_pruned) throw Error("--queries-file needs an index with an ANN graph (not a pruned one)");
+        std::vector<std::string> texts;
+        {
+            std::istringstream ss(read_file(*a.queries_file));
+            for (std::string line; std::getline(ss, line);) {
+                if (!line.empty() && line.back() == '\r') line.pop_back();
+                texts.push_back(line);
+            }
+        }
+        IndexSearcher searcher = IndexSearcher::load(index_path, meta, a.device.c_str());
+        std::vector<std::vector<float>> embeddings;
+        for (auto &t : texts) embeddings.push_back(embed_query(t));
+        SearchOptions opts(a.top_k, a.complexity);
+        if (filter) opts.with_filter(*filter);
+        if (filter && a.device_filter) opts.with_device_filter(*a.filter);
+        if (a.hybrid) opts.with_hybrid("", a.hybrid_alpha);
+        opts.with_compat_polarity(a.compat_polarity).with_bm25_device(a.bm25_device);
+        lj::Value all = lj::Value::array();
+        for (auto &rs : searcher.search_batch_with_options(embeddings, texts, opts)) all.a->push_back(results_json(rs));
+        printf("%s\n", lj::to_string_pretty(all).c_str());
+        return 0;
+    }
+
     std::vector<SearchResult> results;
     auto graph_search = [&]() {
         IndexSearcher searcher = IndexSearcher::load(index_path, meta, a.device.c_str());
@@ -150,7 +193,7 @@ static int run_search(int argc, char **argv) {
         if (filter) opts.with_filter(*filter);
         if (filter && a.device_filter) opts.with_device_filter(*a.filter);
         if (use_hybrid) opts.with_hybrid(a.query, a.hybrid_alpha);
-        opts.with_compat_polarity(a.compat_polarity);
+        opts.with_compat_polarity(a.compat_polarity).with_bm25_device(a.bm25_device);
         results = searcher.search_with_options(q, opts);
     };
     // A pruned index (search.rs:151-167) recomputes embeddings at query time.  The reference scans every passage through the provider
@@ -177,17 +220,8 @@ static int run_search(int argc, char **argv) {
         graph_search();
     }
 
-    if (a.format == "json") { // search.rs:211-223
-        lj::Value arr = lj::Value::array();
-        for (auto &r : results) {
-            lj::Value o = lj::Value::object();
-            o["id"] = lj::Value::string(r.id);
-            o["score"] = lj::Value::number((double)r.score); // f32 widened, like serde_json's From<f32>
-            o["text"] = lj::Value::string(r.text);
-            o["metadata"] = r.metadata;
-            arr.a->push_back(o);
-        }
-        printf("%s\n", lj::to_string_pretty(arr).c_str());
+    if (a.format == "json") {
+        printf("%s\n", lj::to_string_pretty(results_json(results)).c_str());
     } else { // search.rs:225-256
         printf("\nSearch results for '%s' (top %zu):\n\n", a.query.c_str(), results.size());
         for (size_t i = 0; i < results.size(); i++) {

@@ -183,32 +183,54 @@ inline std::vector<std::string> tokenize(const std::string &text) { // [a-zA-Z0-
 class Bm25Scorer {
   public:
     static constexpr float K1 = 1.2f, B = 0.75f; // bm25.rs:9-10
+    // bm25.rs:33-74.  The reference keeps one term -> tf map per passage and probes every one of them per query token; here the same
+    // counts are kept inverted — a term dictionary and, per term, its (passage, tf) postings in ascending passage order — built in the
+    // same single pass.  doc_freq of a term is the length of its list.
     static Bm25Scorer build(const std::vector<std::string> &documents) {
         Bm25Scorer s;
         s.num_docs_ = documents.size();
         size_t total = 0;
-        for (auto &doc : documents) {
-            auto toks = tokenize(doc);
+        for (size_t doc = 0; doc < documents.size(); doc++) {
+            auto toks = tokenize(documents[doc]);
             s.doc_lengths_.push_back(toks.size());
             total += toks.size();
-            std::unordered_map<std::string, size_t> tf;
-            for (auto &t : toks) if (tf[t]++ == 0) s.doc_freq_[t]++;
-            s.term_freqs_.push_back(std::move(tf));
+            for (auto &t : toks) {
+                auto it = s.term_ids_.find(t);
+                if (it == s.term_ids_.end()) {
+                    it = s.term_ids_.emplace(t, (uint32_t)s.postings_.size()).first;
+                    s.postings_.emplace_back();
+                }
+                auto &list = s.postings_[it->second];
+                if (!list.empty() && list.back().first == (uint32_t)doc) list.back().second++;
+                else list.emplace_back((uint32_t)doc, 1u);
+            }
         }
         s.avg_doc_len_ = s.num_docs_ > 0 ? (float)total / (float)s.num_docs_ : 1.0f;
         return s;
     }
+    float idf(uint32_t term) const {
+        float df = (float)postings_[term].size();
+        return std::log(((float)num_docs_ - df + 0.5f) / (df + 0.5f) + 1.0f); // :88
+    }
+    // the query's known tokens in token order (a repeated token twice, bm25.rs:81; unknown ones skipped, :84-86) as (term id, idf)
+    std::vector<std::pair<uint32_t, float>> query_terms(const std::string &query) const {
+        std::vector<std::pair<uint32_t, float>> out;
+        for (auto &token : tokenize(query)) {
+            auto it = term_ids_.find(token);
+            if (it == term_ids_.end() || postings_[it->second].empty()) continue;
+            out.emplace_back(it->second, idf(it->second));
+        }
+        return out;
+    }
+    // Walks the posting list of each token instead of probing every passage: per passage the same additions in the same (token) order
+    // as bm25.rs:77-106, hence the same bits.
     std::vector<float> score_query(const std::string &query) const {
         std::vector<float> scores(num_docs_, 0.0f);
-        for (auto &token : tokenize(query)) {
-            auto it = doc_freq_.find(token);
-            float df = it == doc_freq_.end() ? 0.0f : (float)it->second;
-            if (df == 0.0f) continue;
-            float idf = std::log(((float)num_docs_ - df + 0.5f) / (df + 0.5f) + 1.0f); // :88
-            for (size_t doc = 0; doc < num_docs_; doc++) {
-                auto jt = term_freqs_[doc].find(token);
-                float tf = jt == term_freqs_[doc].end() ? 0.0f : (float)jt->second;
-                if (tf == 0.0f) continue;
+        for (auto &qt : query_terms(query)) {
+            const float idf = qt.second;
+            for (auto &p : postings_[qt.first]) {
+                const size_t doc = p.first;
+                float tf = (float)p.second;
                 float doc_len = (float)doc_lengths_[doc];
                 float norm = 1.0f - B + B * (doc_len / avg_doc_len_);     // :97
                 float score = idf * (tf * (K1 + 1.0f)) / (tf + K1 * norm); // :100
@@ -226,13 +248,29 @@ class Bm25Scorer {
         if (scored.size() > top_k) scored.resize(top_k);
         return scored;
     }
+    size_t num_docs() const { return num_docs_; }
+    size_t num_terms() const { return postings_.size(); }
+    float avg_doc_len() const { return avg_doc_len_; }
+    const std::unordered_map<std::string, uint32_t> &term_ids() const { return term_ids_; }
+    // the inverted index as CSR arrays (leann_bm25_create): post_off [n_terms + 1], post_doc / post_tf, doc_len [n_docs]
+    void export_csr(std::vector<uint64_t> &post_off, std::vector<uint32_t> &post_doc, std::vector<uint32_t> &post_tf,
+                    std::vector<uint32_t> &doc_len) const {
+        post_off.assign(1, 0);
+        post_doc.clear();
+        post_tf.clear();
+        for (auto &list : postings_) {
+            for (auto &p : list) { post_doc.push_back(p.first); post_tf.push_back(p.second); }
+            post_off.push_back(post_doc.size());
+        }
+        doc_len.assign(doc_lengths_.begin(), doc_lengths_.end());
+    }
 
   private:
-    std::unordered_map<std::string, size_t> doc_freq_;
+    std::unordered_map<std::string, uint32_t> term_ids_;
+    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> postings_; // per term: (passage, tf), passages ascending
     size_t num_docs_ = 0;
     float avg_doc_len_ = 1.0f;
     std::vector<size_t> doc_lengths_;
-    std::vector<std::unordered_map<std::string, size_t>> term_freqs_;
 };
 
 // bm25.rs:135-170 — min-max normalise both lists, alpha blend, stable sort descending
@@ -451,11 +489,15 @@ struct SearchOptions {
     // true (default) reproduces that faithfully; false is the corrected mode: the ANN hits enter the blend as similarities 1 - dist
     // (BM25-only hits keep the 0.0 of searcher.rs:160-165).  `leann search --compat-polarity true|false`.
     bool compat_polarity = true;
+    // Additive: the BM25 half of hybrid mode runs on the device (leann_bm25, csrc/bm25.hip) when the searcher has a backend and
+    // fetch_k <= 256; false — or no device — scores on the host.  Same bits either way.  `leann search --bm25 device|host`.
+    bool bm25_device = true;
     SearchOptions(size_t k, size_t c) : top_k(k), complexity(c) {}
     SearchOptions &with_device_filter(std::string key) { device_filter = true; filter_key = std::move(key); return *this; }
     SearchOptions &with_filter(MetadataFilter f) { filter = std::move(f); return *this; }
     SearchOptions &with_hybrid(std::string q, float alpha) { hybrid = true; hybrid_alpha = alpha; query_text = std::move(q); return *this; }
     SearchOptions &with_compat_polarity(bool on) { compat_polarity = on; return *this; }
+    SearchOptions &with_bm25_device(bool on) { bm25_device = on; return *this; }
 };
 
 inline std::vector<std::string> read_id_map(const std::string &index_path, const PassageStore &passages) {
@@ -486,6 +528,7 @@ class IndexSearcher {
         leann_backend *h = nullptr;
         check(leann_backend_open(index_path.c_str(), backend, meta.dimensions, device, &h));
         s.backend_.reset(h, leann_backend_close);
+        s.bm25_device_id_ = (int)std::strtol(device ? device : "0", nullptr, 10); // a list / range: its first device holds the result lists
         return s;
     }
     // passages + id map only, no backend: assemble_results on recorded backend output (CPU tests)
@@ -542,17 +585,63 @@ class IndexSearcher {
             // The reference re-reads every passage and rebuilds the BM25 tables per query (:149-151, :213-224);
             // the index is immutable while open, so the tables are built once and kept —
             // scores are identical.
-            if (!opts.compat_polarity)
-                for (auto &r : vector_results) r.second = 1.0f - r.second; // corrected polarity (N1): similarity, larger = better
             const Bm25Scorer &scorer = bm25();
-            auto bm25_scores = scorer.score_query(*opts.query_text);
-            auto bm25_top = scorer.search(*opts.query_text, fetch_k);
-            std::unordered_set<size_t> have;
-            for (auto &r : vector_results) have.insert(r.first);
-            for (auto &b : bm25_top)
-                if (!have.count(b.first)) vector_results.emplace_back(b.first, 0.0f);
-            vector_results = hybrid_rerank(vector_results, bm25_scores, opts.hybrid_alpha);
+            leann_bm25 *dev = device_bm25_applies(opts, fetch_k) ? bm25_device(scorer) : nullptr;
+            if (host_log_debug()) fprintf(stderr, "DEBUG leann: BM25 scored on the %s\n", dev ? "device" : "host");
+            if (dev) {
+                vector_results = device_hybrid(dev, scorer, {*opts.query_text}, {vector_results}, fetch_k, opts)[0];
+            } else {
+                if (!opts.compat_polarity)
+                    for (auto &r : vector_results) r.second = 1.0f - r.second; // corrected polarity (N1): similarity, larger = better
+                auto bm25_scores = scorer.score_query(*opts.query_text);
+                auto bm25_top = scorer.search(*opts.query_text, fetch_k);
+                std::unordered_set<size_t> have;
+                for (auto &r : vector_results) have.insert(r.first);
+                for (auto &b : bm25_top)
+                    if (!have.count(b.first)) vector_results.emplace_back(b.first, 0.0f);
+                vector_results = hybrid_rerank(vector_results, bm25_scores, opts.hybrid_alpha);
+            }
         }
+        return finish_results(vector_results, opts);
+    }
+    // search_with_options for many queries (hybrid mode, no metadata filter inside the traversal): one batched backend search and ONE
+    // leann_bm25_hybrid_rerank_device call for the whole batch; per query the result of search_with_options.
+    std::vector<std::vector<SearchResult>> search_batch_with_options(const std::vector<std::vector<float>> &query_embeddings,
+                                                                     const std::vector<std::string> &query_texts,
+                                                                     const SearchOptions &opts) const {
+        const size_t nq = query_embeddings.size(), dims = leann_backend_dims(backend_.get());
+        if (query_texts.size() != nq) throw Error("search_batch_with_options: one query text per embedding is required");
+        const size_t fetch_k = opts.top_k * 5;
+        leann_bm25 *dev = (opts.hybrid && device_bm25_applies(opts, fetch_k)) ? bm25_device(bm25()) : nullptr;
+        std::vector<std::vector<SearchResult>> out;
+        if (!opts.hybrid || (opts.filter && opts.device_filter) || !dev) { // nothing to batch: the single-query path, query by query
+            for (size_t i = 0; i < nq; i++) {
+                SearchOptions o = opts;
+                if (opts.hybrid) o.query_text = query_texts[i];
+                out.push_back(search_with_options(query_embeddings[i], o));
+            }
+            return out;
+        }
+        std::vector<float> q(nq * dims);
+        for (size_t i = 0; i < nq; i++) {
+            if (query_embeddings[i].size() != dims)
+                throw Error("query embedding has " + std::to_string(query_embeddings[i].size()) + " dimensions, index has " + std::to_string(dims));
+            std::copy(query_embeddings[i].begin(), query_embeddings[i].end(), q.begin() + i * dims);
+        }
+        std::vector<uint64_t> keys(nq * fetch_k);
+        std::vector<float> dists(nq * fetch_k);
+        std::vector<uint32_t> counts(nq);
+        check(leann_backend_search_batch(backend_.get(), q.data(), nq, fetch_k, opts.complexity, keys.data(), dists.data(), counts.data()));
+        std::vector<std::vector<std::pair<size_t, float>>> lists(nq);
+        for (size_t i = 0; i < nq; i++)
+            for (size_t j = 0; j < counts[i]; j++) lists[i].emplace_back((size_t)keys[i * fetch_k + j], dists[i * fetch_k + j]);
+        if (host_log_debug()) fprintf(stderr, "DEBUG leann: BM25 scored on the device (batch of %zu)\n", nq);
+        auto reranked = device_hybrid(dev, bm25(), query_texts, lists, fetch_k, opts);
+        for (size_t i = 0; i < nq; i++) out.push_back(finish_results(reranked[i], opts));
+        return out;
+    }
+    // :171-207 — id map, passage fetch, post-filter, top_k cut
+    std::vector<SearchResult> finish_results(const std::vector<std::pair<size_t, float>> &vector_results, const SearchOptions &opts) const {
         std::vector<SearchResult> results;
         for (auto &r : vector_results) {
             if (results.size() >= opts.top_k) break;
@@ -593,6 +682,77 @@ class IndexSearcher {
         if (!bm25_) bm25_ = std::make_shared<Bm25Scorer>(Bm25Scorer::build(get_all_texts()));
         return *bm25_;
     }
+    static bool host_log_debug() {
+        const char *e = getenv("LEANN_LOG");
+        return e && !strcmp(e, "debug");
+    }
+    // The device call takes what the reference's arithmetic is pinned for: fetch_k <= 256 and alpha in [0, 1].  The reference itself
+    // accepts any f32 alpha (searcher.rs:57-59, bm25.rs:163), NaN included: such a query is scored on the host, as before.
+    bool device_bm25_applies(const SearchOptions &opts, size_t fetch_k) const {
+        return opts.bm25_device && backend_ && fetch_k >= 1 && fetch_k <= 256 && opts.hybrid_alpha >= 0.0f && opts.hybrid_alpha <= 1.0f;
+    }
+    // the scorer's inverted index on the device, created on first use and shared by every copy of this searcher; null when there is no
+    // device, no passage, or the handle could not be created (logged once): BM25 is then scored on the host, same bits
+    leann_bm25 *bm25_device(const Bm25Scorer &scorer) const {
+        std::lock_guard<std::mutex> lk(*bm25_mu_);
+        if (bm25_dev_->handle || bm25_dev_->tried) return bm25_dev_->handle.get();
+        bm25_dev_->tried = true;
+        int ndev = 0;
+        if (scorer.num_docs() == 0 || leann_device_count(&ndev) != LEANN_OK || ndev < 1) return nullptr;
+        std::vector<uint64_t> off;
+        std::vector<uint32_t> doc, tf, len;
+        scorer.export_csr(off, doc, tf, len);
+        leann_bm25 *raw = nullptr;
+        if (leann_bm25_create(scorer.num_docs(), scorer.num_terms(), off.data(), doc.data(), tf.data(), len.data(), scorer.avg_doc_len(),
+                              bm25_device_id_, &raw) != LEANN_OK) {
+            fprintf(stderr, "WARN BM25 index not created on the device, scoring on the host: %s\n", leann_last_error());
+            return nullptr;
+        }
+        bm25_dev_->handle.reset(raw, leann_bm25_close);
+        return raw;
+    }
+    struct DeviceBuf { // HBM block on the BM25 handle's device, freed on scope exit
+        void *p = nullptr;
+        DeviceBuf(int device, size_t bytes) { check(leann_device_malloc(device, std::max<size_t>(bytes, 16), &p)); }
+        ~DeviceBuf() { if (p) leann_device_free(p); }
+        DeviceBuf(const DeviceBuf &) = delete;
+        DeviceBuf &operator=(const DeviceBuf &) = delete;
+    };
+    // searcher.rs:146-169 for a batch on the device: backend lists (key, DISTANCE) up, merged + reranked lists (all of them) down
+    std::vector<std::vector<std::pair<size_t, float>>> device_hybrid(leann_bm25 *dev, const Bm25Scorer &scorer,
+                                                                     const std::vector<std::string> &texts,
+                                                                     const std::vector<std::vector<std::pair<size_t, float>>> &lists,
+                                                                     size_t fetch_k, const SearchOptions &opts) const {
+        const size_t nq = lists.size(), out_k = 2 * fetch_k; // the merged list has at most fetch_k + fetch_k entries
+        std::vector<uint32_t> q_off(1, 0), q_term, counts(nq);
+        std::vector<float> q_idf;
+        std::vector<uint64_t> keys(nq * fetch_k, ~0ull);
+        std::vector<float> dists(nq * fetch_k, INFINITY);
+        for (size_t i = 0; i < nq; i++) {
+            for (auto &t : scorer.query_terms(texts[i])) { q_term.push_back(t.first); q_idf.push_back(t.second); }
+            q_off.push_back((uint32_t)q_term.size());
+            counts[i] = (uint32_t)std::min(lists[i].size(), fetch_k);
+            for (size_t j = 0; j < counts[i]; j++) { keys[i * fetch_k + j] = lists[i][j].first; dists[i * fetch_k + j] = lists[i][j].second; }
+        }
+        const int d = bm25_device_id_;
+        DeviceBuf dk(d, keys.size() * 8), dd(d, dists.size() * 4), dc(d, nq * 4), ok(d, nq * out_k * 8), os(d, nq * out_k * 4), oc(d, nq * 4);
+        check(leann_device_upload(dk.p, keys.data(), keys.size() * 8));
+        check(leann_device_upload(dd.p, dists.data(), dists.size() * 4));
+        check(leann_device_upload(dc.p, counts.data(), nq * 4));
+        check(leann_bm25_hybrid_rerank_device(dev, nq, q_off.data(), q_term.data(), q_idf.data(), (const uint64_t *)dk.p, (const float *)dd.p,
+                                              (const uint32_t *)dc.p, fetch_k, opts.hybrid_alpha, opts.compat_polarity ? 1 : 0, out_k,
+                                              (uint64_t *)ok.p, (float *)os.p, (uint32_t *)oc.p, nullptr));
+        std::vector<uint64_t> rk(nq * out_k);
+        std::vector<float> rs(nq * out_k);
+        std::vector<uint32_t> rc(nq);
+        check(leann_device_download(rk.data(), ok.p, rk.size() * 8));
+        check(leann_device_download(rs.data(), os.p, rs.size() * 4));
+        check(leann_device_download(rc.data(), oc.p, nq * 4));
+        std::vector<std::vector<std::pair<size_t, float>>> out(nq);
+        for (size_t i = 0; i < nq; i++)
+            for (size_t j = 0; j < rc[i]; j++) out[i].emplace_back((size_t)rk[i * out_k + j], rs[i * out_k + j]);
+        return out;
+    }
     // one pass over the passage metadata per distinct filter (the index is immutable while open); bit i = position i.  The bitmap is
     // registered on the device once (leann_backend_filter_create) and reused by every query under the same filter.
     struct RegisteredFilter {
@@ -626,6 +786,12 @@ class IndexSearcher {
     std::vector<std::string> id_map_;
     std::shared_ptr<std::map<std::string, RegisteredFilter>> filters_ = std::make_shared<std::map<std::string, RegisteredFilter>>();
     mutable std::shared_ptr<Bm25Scorer> bm25_;
+    struct Bm25Device { // the scorer's postings in HBM; one per loaded index, shared by its copies like the mutex that guards it
+        std::shared_ptr<leann_bm25> handle;
+        bool tried = false;
+    };
+    std::shared_ptr<Bm25Device> bm25_dev_ = std::make_shared<Bm25Device>();
+    int bm25_device_id_ = 0;
     std::shared_ptr<std::mutex> bm25_mu_ = std::make_shared<std::mutex>();
 };
 
