@@ -141,6 +141,40 @@ int leann_backend_build(int backend, const float *vectors, size_t n, size_t dims
 int leann_backend_add(int backend, const float *vectors, size_t n, size_t dims, size_t start_id,
                       const char *index_path_stem);
 
+/* ---- removing passages (additive; the reference can only append: `leann update`) -------------------------------------------------
+ * leann_backend_remove marks keys as removed.  Keys are global (key_offset included); positions are never renumbered — the id map
+ * above this ABI is positional —, so leann_backend_len stays the number of POSITIONS and leann_backend_live_len counts the rest.  An
+ * unknown key -> LEANN_ERR_INVALID naming it, and nothing is applied; a key that is already removed is ignored and not counted in
+ * *n_removed (may be NULL).  From then on EVERY leann_backend_search* entry point excludes removed positions: the walks run the
+ * filtered kernel under live AND the caller's bitmap (so an unfiltered search then has the filtered search's semantics: top-k among
+ * the evaluated nodes), the exact paths compact live AND allow.  A leann_filter registered before a later removal is refused with
+ * LEANN_ERR_INVALID ("filter predates a removal; register it again").
+ * leann_backend_consolidate repairs the graph on the device: every live node that named a removed one is re-linked
+ * through that node's neighbours (FreshDiskANN Alg. 4) and pruned by the rule the build used; lists of removed nodes are cleared and
+ * a removed entry point is replaced.  Afterwards no live list names a removed position, unfiltered walks use the plain kernel again,
+ * exact and filtered paths keep ANDing the live mask.  A recompute-on handle (no f32 rows to prune on) -> LEANN_ERR_UNSUPPORTED: its
+ * removals stay tombstones answered by the filtered walk.  A one-process composite handle routes each key to the shard that owns its
+ * range and consolidates every shard; the ranks of an RCCL group remove from / consolidate their own shard handles.
+ * Like open / build, remove and consolidate are NOT concurrent with searches on the same handle.  A handle without removals takes
+ * exactly the code paths it took before these calls existed.
+ * leann_backend_removed_bitmap: bit i&7 of byte i>>3 set = position i is removed (ceil(len/8) bytes); *n_pending (may be NULL) =
+ * removed positions that live lists still name — 0 after a consolidate.
+ * Persistence: leann_backend_save writes the removals beside the index file as "<stem minus .leann>.tombstones" ("LEANNTB1", u64 n,
+ * u64 removed, u64 n_pending, the bitmap) or deletes a stale one when nothing is removed; leann_backend_open reads and validates it
+ * (length against n, popcount against the count, zero padding bits; LEANN_ERR_FORMAT otherwise); leann_backend_add extends it with
+ * zero bits; sharded save / open carry one per shard file.  The sidecar's name drops the index file's extension, so an HNSW and a
+ * DiskANN index under ONE stem would share it: keep one backend per stem.  The index file layout is unchanged (a DiskANN file built
+ * with the one-stage prune records that in a header byte that was padding, so that consolidation repairs with the build's rule).
+ * leann_backend_remove_from_index is the file twin, like leann_backend_add: open -> remove -> consolidate -> save. */
+int leann_backend_remove(leann_backend *h, const uint64_t *keys, size_t n, size_t *n_removed);
+int leann_backend_consolidate(leann_backend *h);
+size_t leann_backend_live_len(const leann_backend *h);
+int leann_backend_removed_bitmap(const leann_backend *h, uint8_t *out /* ceil(len/8) */, size_t *n_pending);
+int leann_backend_remove_from_index(int backend, const uint64_t *keys, size_t n, size_t dims, const char *index_path_stem);
+/* the sidecar's writer and validator on their own (no handle, no device): `bitmap` / `bitmap_out` hold ceil(n/8) bytes */
+int leann_tombstones_write(const char *path, const uint8_t *bitmap, uint64_t n, uint64_t n_pending);
+int leann_tombstones_read(const char *path, uint64_t n_expected, uint8_t *bitmap_out, uint64_t *n_removed, uint64_t *n_pending);
+
 /* ---- roofline accounting -------------------------------------------------------
  * Totals accumulated over every search call on the handle since the last reset. */
 typedef struct {

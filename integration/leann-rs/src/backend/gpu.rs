@@ -55,6 +55,16 @@ extern "C" {
                            complexity: usize, stem: *const c_char) -> c_int;
     fn leann_backend_add(backend: c_int, vectors: *const f32, n: usize, dims: usize, start_id: usize,
                          stem: *const c_char) -> c_int;
+    // removals (additive): tombstones + on-device graph repair; keys are global positions, never renumbered
+    #[allow(dead_code)]
+    fn leann_backend_remove(h: *mut LeannBackend, keys: *const u64, n: usize, n_removed: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn leann_backend_consolidate(h: *mut LeannBackend) -> c_int;
+    #[allow(dead_code)]
+    fn leann_backend_live_len(h: *const LeannBackend) -> usize;
+    #[allow(dead_code)]
+    fn leann_backend_removed_bitmap(h: *const LeannBackend, out: *mut u8, n_pending: *mut usize) -> c_int;
+    fn leann_backend_remove_from_index(backend: c_int, keys: *const u64, n: usize, dims: usize, stem: *const c_char) -> c_int;
 }
 
 fn last_error() -> anyhow::Error {
@@ -139,6 +149,16 @@ pub fn add_to_index(backend: c_int, embeddings: &[Vec<f32>], index_path: &Path, 
     let flat = flatten(embeddings, dimensions)?;
     let stem = CString::new(index_path.to_string_lossy().as_bytes())?;
     let rc = unsafe { leann_backend_add(backend, flat.as_ptr(), embeddings.len(), dimensions, start_id, stem.as_ptr()) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    Ok(())
+}
+
+/// Remove passages (by position) from the index on disk: open -> remove -> consolidate -> save.  Positions keep their numbers.
+pub fn remove_from_index(backend: c_int, keys: &[u64], index_path: &Path, dimensions: usize) -> anyhow::Result<()> {
+    let stem = CString::new(index_path.to_string_lossy().as_bytes())?;
+    let rc = unsafe { leann_backend_remove_from_index(backend, keys.as_ptr(), keys.len(), dimensions, stem.as_ptr()) };
     if rc != 0 {
         return Err(last_error());
     }

@@ -211,6 +211,28 @@ class BackendSearcher:
     def dims(self):
         return int(N.lib().leann_backend_dims(self._h))
 
+    # -- removals (additive) -------------------------------------------------------
+    def remove(self, keys):
+        """mark keys (global positions) as removed; every search excludes them from now on.  Returns how many were newly removed."""
+        k = np.ascontiguousarray(keys, np.uint64).reshape(-1)
+        n = C.c_size_t(0)
+        N.check(N.lib().leann_backend_remove(self._h, _p(k, u64p), k.shape[0], C.byref(n)))
+        return int(n.value)
+
+    def consolidate(self):
+        """repair the graph on the device so that no live list names a removed position"""
+        N.check(N.lib().leann_backend_consolidate(self._h))
+
+    def live_len(self):
+        return int(N.lib().leann_backend_live_len(self._h))
+
+    def removed_bitmap(self):
+        """(bitmap [ceil(len/8)] uint8, bit set = removed; number of removed positions live lists still name)"""
+        bm = np.zeros(max((self.len() + 7) // 8, 1), np.uint8)
+        pend = C.c_size_t(0)
+        N.check(N.lib().leann_backend_removed_bitmap(self._h, _p(bm, u8p), C.byref(pend)))
+        return bm[: (self.len() + 7) // 8], int(pend.value)
+
     # -- extras -------------------------------------------------------------------------------
     def stats(self, reset=False):
         s = N.SearchStats()
@@ -302,6 +324,12 @@ class BackendBuilder:
         X = np.ascontiguousarray(embeddings, np.float32)
         N.check(N.lib().leann_backend_add(int(self.backend_type), _p(X, f32p), X.shape[0], dimensions,
                                           start_id, os.fsencode(str(index_path))))
+
+    def remove_from_index(self, keys, index_path, dimensions):
+        """the file twin of BackendSearcher.remove + consolidate: open -> remove -> consolidate -> save"""
+        k = np.ascontiguousarray(keys, np.uint64).reshape(-1)
+        N.check(N.lib().leann_backend_remove_from_index(int(self.backend_type), _p(k, u64p), k.shape[0], dimensions,
+                                                        os.fsencode(str(index_path))))
 
 
 

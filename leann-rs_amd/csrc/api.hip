@@ -200,6 +200,7 @@ void leann_internal_free_graph(leann_backend *h) {
     (void)hipFree(h->gpool2_lock);
     (void)hipFree(h->Wf32);
     for (auto &kv : h->proj_scratch) (void)hipFree(kv.second.first);
+    leann_internal_free_removed(h);
 }
 
 extern "C" void leann_backend_close(leann_backend *h) {
@@ -459,6 +460,8 @@ extern "C" int leann_backend_search_filtered_batch_device(const leann_backend *h
     a.out_stats = d_stats;
     a.allow = d_allow;
     a.allow_stride = allow_stride;
+    if (h->d_live) // removals (consolidate.hip): the walk runs under live AND the caller's bitmap until the graph has been repaired
+        if (int rc = leann_internal_live_allow(h, d_allow, allow_stride, nq, true, st, &a.allow, &a.allow_stride)) return rc;
 #ifdef LEANN_STAMPS
     if (const unsigned long long e = leann_knobs().stamp_buf) { // diagnostic build: [nq x 8] u64 device buffer address in the environment
         a.out_nexp = reinterpret_cast<uint32_t *>(e);
@@ -480,6 +483,7 @@ static int search_filtered_batch_host(const leann_backend *hc, const float *quer
                                       const uint8_t *allow, size_t allow_stride, uint64_t *keys, float *dists, uint32_t *counts, int mode,
                                       const leann_filter *flt = nullptr);
 int leann_internal_compact_allow(const uint8_t *d_allow, size_t n, uint32_t **d_list, size_t *n_list, hipStream_t st);
+int leann_internal_and_live_inplace(const leann_backend *h, uint8_t *d_bitmap);
 void leann_internal_scratch_release(void *p);
 
 // Registered filters: a server that answers many queries under the same metadata filter uploads and compacts the bitmap once
@@ -506,6 +510,7 @@ extern "C" int leann_backend_filter_create(const leann_backend *hc, const uint8_
             f->n_allowed += part->n_allowed;
         }
         (void)hipSetDevice(hc->device);
+        f->epoch = hc->removal_epoch;
         *out = f;
         return LEANN_OK;
     }
@@ -524,7 +529,9 @@ extern "C" int leann_backend_filter_create(const leann_backend *hc, const uint8_
         delete f;
         return LEANN_ERR_DEVICE;
     }
-    int rc = f->n ? leann_internal_compact_allow(f->d_allow, f->n, &f->d_list, &f->n_allowed, nullptr) : LEANN_OK;
+    f->epoch = hc->removal_epoch;
+    int rc = leann_internal_and_live_inplace(hc, f->d_allow); // removed positions are never allowed: the bitmap and the list hold live ones only
+    if (rc == LEANN_OK && f->n) rc = leann_internal_compact_allow(f->d_allow, f->n, &f->d_list, &f->n_allowed, nullptr);
     if (rc != LEANN_OK) {
         (void)hipFree(f->d_allow);
         delete f;
@@ -553,6 +560,14 @@ extern "C" int leann_backend_search_filter_batch(const leann_backend *hc, const 
         filter->parts.empty() != (hc->sharded == nullptr)) { // (a filter registered on a sharded handle holds one sub-filter per shard, and only those)
         leann_set_error("leann_backend_search_filter_batch: null / foreign filter (made for %zu rows, the index has %zu) or bad mode %d",
                         filter ? filter->n : (size_t)0, hc ? (size_t)hc->g.n : (size_t)0, mode);
+        return LEANN_ERR_INVALID;
+    }
+    bool stale = filter->epoch != hc->removal_epoch;
+    if (hc->sharded)
+        for (size_t g = 0; g < filter->parts.size() && g < leann_internal_sharded_count(hc->sharded); g++)
+            stale = stale || filter->parts[g]->epoch != leann_internal_sharded_shard(hc->sharded, g)->removal_epoch;
+    if (stale) {
+        leann_set_error("leann_backend_search_filter_batch: filter predates a removal; register it again");
         return LEANN_ERR_INVALID;
     }
     return search_filtered_batch_host(hc, queries, nq, top_k, complexity, nullptr, 0, keys, dists, counts, mode, filter);
@@ -609,6 +624,8 @@ extern "C" int leann_backend_search_filtered_exact_batch_device(const leann_back
         HIP_CHECK_RET(hipMemsetAsync(d_counts, 0, nq * 4, st));
         return LEANN_OK;
     }
+    if (h->d_live) // removals: only live rows are compacted
+        if (int rc = leann_internal_live_allow(h, d_allow, allow_stride, nq, false, st, &d_allow, &allow_stride)) return rc;
     return leann_internal_filtered_exact(h->g.X, h->g.n, h->g.d, h->g.ld, d_queries, nq, top_k, d_allow, allow_stride, h->key_offset, d_keys,
                                          d_dists, d_counts, st);
 }
@@ -740,9 +757,16 @@ static int search_filtered_batch_host_impl(const leann_backend *hc, const float 
             return fail(LEANN_ERR_UNSUPPORTED);
         }
         if (hipMemsetAsync(w->d_stats, 0, nq * 16, st) != hipSuccess) return fail(LEANN_ERR_DEVICE);
-        rc = leann_internal_filtered_exact(h->g.X, h->g.n, h->g.d, h->g.ld, w->d_q, nq, top_k, w->d_allow, allow_stride, h->key_offset,
+        const uint8_t *ea = w->d_allow;
+        size_t es = allow_stride;
+        if (h->d_live) rc = leann_internal_live_allow(h, ea, es, nq, false, st, &ea, &es);
+        if (rc) return fail(rc);
+        rc = leann_internal_filtered_exact(h->g.X, h->g.n, h->g.d, h->g.ld, w->d_q, nq, top_k, ea, es, h->key_offset,
                                            w->d_keys, w->d_dists, w->d_counts, st);
     } else {
+        // removals: a registered filter holds live positions only (leann_backend_filter_create); any other walk runs under live AND allow
+        if (h->d_live && !flt) rc = leann_internal_live_allow(h, a.allow, a.allow_stride, nq, true, st, &a.allow, &a.allow_stride);
+        if (rc) return fail(rc);
         rc = leann_internal_launch_search(h, a, st);
     }
     if (rc) return fail(rc);
@@ -1057,6 +1081,7 @@ int leann_internal_from_host(int backend, size_t n, size_t dims, uint32_t M, uin
     h->g.max_level = max_level;
     h->g.entry = entry;
     h->n_upper_lists = n_upper_lists;
+    if (const char *e = getenv("LEANN_VAMANA_TWO_STAGE")) h->two_stage = strcmp(e, "0") != 0; // the prune form consolidation repairs with
     // every allocation lands in the handle at once, so that one leann_backend_close frees whatever a failure leaves behind
     auto fail = [&](const char *what) {
         leann_set_error("leann_backend_from_arrays: %s failed: %s", what, hipGetErrorString(hipGetLastError()));

@@ -49,7 +49,9 @@ struct FileHeader {
     uint32_t feat_h; // version 2: feature width (multiple of 4); 0 in version 1
     uint64_t n_upper_lists;
     uint32_t row_bytes; // version 2
-    uint8_t pad[60];
+    uint8_t one_stage; // DiskANN: 1 = built with the paper's one-stage RobustPrune (LEANN_VAMANA_TWO_STAGE=0), so that delete consolidation
+                       // repairs with the rule the build used; 0 (what every earlier file holds here) = the default two-stage form
+    uint8_t pad[59];
 };
 #pragma pack(pop)
 static_assert(sizeof(FileHeader) == 128, "index file header is 128 bytes");
@@ -80,6 +82,7 @@ int leann_internal_save_to(const leann_backend *h, const std::string &path) {
     hd.version = feat ? 2 : 1; hd.kind = (uint32_t)h->kind; hd.n = n; hd.d = (uint32_t)d; hd.M = h->g.M; hd.M0 = h->g.M0;
     hd.max_level = h->g.max_level; hd.entry = h->g.entry; hd.efc = h->efc; hd.alpha = h->alpha;
     hd.n_upper_lists = h->n_upper_lists;
+    hd.one_stage = (h->kind == LEANN_BACKEND_DISKANN && !h->two_stage) ? 1 : 0;
     hd.feat_h = h->g.feat_h;
     hd.row_bytes = feat ? (uint32_t)leann_internal_feat_file_row_bytes(h->g) : h->g.row_bytes;
     bool ok = fwrite(&hd, sizeof(hd), 1, f) == 1;
@@ -115,8 +118,13 @@ int leann_internal_save_to(const leann_backend *h, const std::string &path) {
     }
     ok = (fclose(f) == 0) && ok;
     if (!ok) { (void)remove(tmp.c_str()); leann_set_error("short write to %s", tmp.c_str()); return LEANN_ERR_IO; }
+    // Removals travel beside the file ("<stem>.tombstones").  With removals the sidecar goes first: a crash between the two steps then
+    // leaves new tombstones beside the old graph, which is safe (n_pending is counted again on open), where a repaired graph without
+    // its tombstones would hand the removed rows back through the exact paths.  Without removals a stale sidecar goes last.
+    if (h->n_removed)
+        if (int rc2 = leann_internal_tombstones_save(h, path)) { (void)remove(tmp.c_str()); return rc2; }
     if (rename(tmp.c_str(), path.c_str()) != 0) { (void)remove(tmp.c_str()); leann_set_error("cannot move %s into place", tmp.c_str()); return LEANN_ERR_IO; }
-    return LEANN_OK;
+    return h->n_removed ? (int)LEANN_OK : leann_internal_tombstones_save(h, path);
 }
 
 extern "C" int leann_backend_save(const leann_backend *h, const char *index_path_stem) {
@@ -210,7 +218,11 @@ static int load_own_file(const std::string &path, int backend, size_t dims, int 
         std::string msg = leann_last_error();
         leann_set_error("Failed to load index: %s (%s)", msg.c_str(), path.c_str());
     }
-    if (rc == LEANN_OK) { (*out)->efc = hd.efc ? hd.efc : 64; (*out)->alpha = hd.alpha; }
+    if (rc == LEANN_OK) { (*out)->efc = hd.efc ? hd.efc : 64; (*out)->alpha = hd.alpha; (*out)->two_stage = hd.one_stage ? 0u : 1u; }
+    if (rc == LEANN_OK) { // removals made before the save (consolidate.hip); a sidecar that does not fit the file is refused
+        rc = leann_internal_tombstones_load(*out, path);
+        if (rc) { leann_backend_close(*out); *out = nullptr; *why = "bad tombstone sidecar"; }
+    }
     return rc;
 }
 

@@ -72,7 +72,28 @@ struct leann_backend {
     // spot, a lone caller is answered directly; 1 = configured by leann_backend_set_coalescing; 2 = switched off by it
     int coalesce_mode = 0;
     std::atomic<int> singles_in_flight{0};
+    // removals (consolidate.hip): positions are never renumbered; a removed position keeps its row and is masked out of every search.
+    // removed: host bitmap (bit set = removed), empty until the first removal.  d_live: its complement on the device (padding bits 0),
+    // null until the first removal — a handle without removals takes none of the code paths below.  n_pending: removed positions a live
+    // list still names (0 after leann_backend_consolidate: unfiltered walks then run the plain kernel again).  removal_epoch counts
+    // the leann_backend_remove calls that removed something; a registered filter remembers the epoch it was made in.
+    std::vector<uint8_t> removed;
+    uint8_t *d_live = nullptr;
+    size_t n_removed = 0, n_pending = 0;
+    uint64_t removal_epoch = 0;
+    uint32_t two_stage = 1; // Vamana: the RobustPrune form the build used (LEANN_VAMANA_TWO_STAGE when the handle was made)
+    std::map<hipStream_t, std::pair<uint8_t *, size_t>> live_scratch; // per stream: live AND the caller's bitmap(s)
 };
+// Removals (consolidate.hip).  leann_internal_live_allow: the bitmap a search on `h` has to run under — the caller's (may be null)
+// ANDed with the live mask into the stream's scratch; *out = d_allow unchanged for a handle without removals.  `walk`: the caller is
+// the graph walk, which needs no mask of its own once no live list names a removed position.
+int leann_internal_live_allow(leann_backend *h, const uint8_t *d_allow, size_t allow_stride, size_t nq, bool walk, hipStream_t st,
+                              const uint8_t **out, size_t *out_stride);
+int leann_internal_set_removed(leann_backend *h, const uint8_t *bitmap, size_t n_removed); // adopt a bitmap (open): device mask + n_pending
+void leann_internal_free_removed(leann_backend *h);
+std::string leann_internal_tombstone_file(const std::string &index_file);
+int leann_internal_tombstones_save(const leann_backend *h, const std::string &index_file); // writes the sidecar, or removes a stale one
+int leann_internal_tombstones_load(leann_backend *h, const std::string &index_file);
 
 // LEANN_LOG=error|warn|info|debug (default warn) -> stderr, "LEVEL leann_hip: message" (the reference logs through tracing, cli/mod.rs:38-43)
 enum { LEANN_LOG_ERROR = 0, LEANN_LOG_WARN = 1, LEANN_LOG_INFO = 2, LEANN_LOG_DEBUG = 3 };
@@ -97,6 +118,7 @@ struct leann_filter {
     size_t n = 0, n_allowed = 0;
     uint8_t *d_allow = nullptr;
     uint32_t *d_list = nullptr; // scratch-pool block (scan.hip), held for the filter's lifetime
+    uint64_t epoch = 0;         // the handle's removal_epoch when the filter was made (its bitmap holds live positions only)
     std::vector<leann_filter *> parts;
 };
 // how a sharded search filters: a bitmap over GLOBAL positions on the first device (sliced per shard at byte boundaries), or one

@@ -341,15 +341,68 @@ static int run_build(int argc, char **argv) {
     return 0;
 }
 
+// leann delete <index> --ids a,b,c | --ids-file F   (additive; the reference can only append)
+// Passage ids are mapped to positions through ids.txt and removed from the ANN index (leann_backend_remove_from_index: tombstones +
+// graph repair, persisted beside the index file).  The passages, ids and meta files are not rewritten: positions keep their numbers.
+static int run_delete(int argc, char **argv) {
+    std::string index_name, device;
+    std::vector<std::string> ids;
+    auto add_ids = [&](const std::string &text, char sep) {
+        std::istringstream ss(text);
+        for (std::string t; std::getline(ss, t, sep);) {
+            if (!t.empty() && t.back() == '\r') t.pop_back();
+            if (!t.empty()) ids.push_back(t);
+        }
+    };
+    for (int i = 0; i < argc; i++) {
+        std::string s = argv[i];
+        auto val = [&]() -> std::string { if (i + 1 >= argc) throw Error("a value is required for '" + s + "' but none was supplied"); return argv[++i]; };
+        if (s == "-h" || s == "--help") { puts("Remove passages from an index\n\nUsage: leann delete <INDEX> --ids a,b,c | --ids-file <FILE>"); return 0; }
+        else if (s == "--ids") add_ids(val(), ',');
+        else if (s == "--ids-file") add_ids(read_file(val()), '\n');
+        else if (s == "-i" || s == "--index") index_name = val();
+        else if (!s.empty() && s[0] == '-' && s.size() > 1) throw Error("unexpected argument '" + s + "' found");
+        else if (index_name.empty()) index_name = s;
+        else throw Error("unexpected argument '" + s + "' found");
+    }
+    if (index_name.empty()) throw Error("the following required arguments were not provided:\n  <INDEX>");
+    if (ids.empty()) throw Error("no passage ids given: pass --ids a,b,c or --ids-file <FILE>");
+    std::string index_dir = find_index(index_name);
+    std::string index_path = index_dir + "/documents.leann";
+    IndexMeta meta = IndexMeta::load(index_path + ".meta.json");
+    int backend = meta.backend_name == "hnsw" ? LEANN_BACKEND_HNSW : meta.backend_name == "diskann" ? LEANN_BACKEND_DISKANN : -1;
+    if (backend < 0) throw Error("Unknown backend: " + meta.backend_name);
+    PassageStore passages = PassageStore::open(index_path);
+    std::vector<std::string> id_map = read_id_map(index_path, passages);
+    std::unordered_map<std::string, uint64_t> pos;
+    for (size_t i = 0; i < id_map.size(); i++) pos.emplace(id_map[i], (uint64_t)i);
+    std::vector<uint64_t> keys;
+    for (auto &id : ids) {
+        auto it = pos.find(id);
+        if (it == pos.end()) throw Error("unknown passage id '" + id + "' in index '" + index_name + "'");
+        keys.push_back(it->second);
+    }
+    check(leann_backend_remove_from_index(backend, keys.data(), keys.size(), meta.dimensions, index_path.c_str()));
+    leann_backend *h = nullptr;
+    check(leann_backend_open(index_path.c_str(), backend, meta.dimensions, "0", &h));
+    const size_t live = leann_backend_live_len(h);
+    leann_backend_close(h);
+    std::sort(keys.begin(), keys.end());
+    const size_t distinct = (size_t)(std::unique(keys.begin(), keys.end()) - keys.begin());
+    printf("Index '%s': removed %zu passages, %zu live\n", index_name.c_str(), distinct, live);
+    return 0;
+}
+
 int main(int argc, char **argv) {
     try {
         if (argc < 2 || !strcmp(argv[1], "-h") || !strcmp(argv[1], "--help")) {
-            puts("LEANN search path on MI355X\n\nUsage: leann <COMMAND>\n\nCommands:\n  search  Query an index\n  build   Build an index from a passages JSONL (synthetic embeddings)\n");
+            puts("LEANN search path on MI355X\n\nUsage: leann <COMMAND>\n\nCommands:\n  search  Query an index\n  build   Build an index from a passages JSONL (synthetic embeddings)\n  delete  Remove passages from an index\n");
             return argc < 2 ? 2 : 0;
         }
         if (!strcmp(argv[1], "--version") || !strcmp(argv[1], "-V")) { printf("leann %s\n", leann_version()); return 0; }
         if (!strcmp(argv[1], "search")) return run_search(argc - 2, argv + 2);
         if (!strcmp(argv[1], "build")) return run_build(argc - 2, argv + 2);
+        if (!strcmp(argv[1], "delete")) return run_delete(argc - 2, argv + 2);
         throw Error(std::string("unrecognized subcommand '") + argv[1] + "'");
     } catch (const std::exception &e) {
         fprintf(stderr, "Error: %s\n", e.what());

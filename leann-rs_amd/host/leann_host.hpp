@@ -529,6 +529,12 @@ class IndexSearcher {
         check(leann_backend_open(index_path.c_str(), backend, meta.dimensions, device, &h));
         s.backend_.reset(h, leann_backend_close);
         s.bm25_device_id_ = (int)std::strtol(device ? device : "0", nullptr, 10); // a list / range: its first device holds the result lists
+        // removed positions (leann_backend_remove / `leann delete`), read once per handle: the backend never returns them, but BM25
+        // is scored over every passage of the store and would bring them back through the hybrid branch
+        if (leann_backend_live_len(h) != leann_backend_len(h)) {
+            s.removed_.assign((leann_backend_len(h) + 7) / 8, 0);
+            check(leann_backend_removed_bitmap(h, s.removed_.data(), nullptr));
+        }
         return s;
     }
     // passages + id map only, no backend: assemble_results on recorded backend output (CPU tests)
@@ -598,7 +604,7 @@ class IndexSearcher {
                 std::unordered_set<size_t> have;
                 for (auto &r : vector_results) have.insert(r.first);
                 for (auto &b : bm25_top)
-                    if (!have.count(b.first)) vector_results.emplace_back(b.first, 0.0f);
+                    if (!have.count(b.first) && !is_removed(b.first)) vector_results.emplace_back(b.first, 0.0f); // (no BM25-only hit at a removed position)
                 vector_results = hybrid_rerank(vector_results, bm25_scores, opts.hybrid_alpha);
             }
         }
@@ -645,6 +651,7 @@ class IndexSearcher {
         std::vector<SearchResult> results;
         for (auto &r : vector_results) {
             if (results.size() >= opts.top_k) break;
+            if (is_removed(r.first)) continue; // (the device BM25 path injects inside the kernel: masked here, like the host path's injection)
             std::string id = r.first < id_map_.size() ? id_map_[r.first] : std::to_string(r.first); // :180-184
             try {
                 Passage p = passages_.get(id);
@@ -677,6 +684,7 @@ class IndexSearcher {
     bool is_empty() const { return len() == 0; }
 
   private:
+    bool is_removed(size_t pos) const { return (pos >> 3) < removed_.size() && ((removed_[pos >> 3] >> (pos & 7)) & 1); }
     const Bm25Scorer &bm25() const {
         std::lock_guard<std::mutex> lk(*bm25_mu_);
         if (!bm25_) bm25_ = std::make_shared<Bm25Scorer>(Bm25Scorer::build(get_all_texts()));
@@ -784,6 +792,7 @@ class IndexSearcher {
     PassageStore passages_;
     std::shared_ptr<leann_backend> backend_;
     std::vector<std::string> id_map_;
+    std::vector<uint8_t> removed_; // bitmap of removed positions; empty when nothing is removed
     std::shared_ptr<std::map<std::string, RegisteredFilter>> filters_ = std::make_shared<std::map<std::string, RegisteredFilter>>();
     mutable std::shared_ptr<Bm25Scorer> bm25_;
     struct Bm25Device { // the scorer's postings in HBM; one per loaded index, shared by its copies like the mutex that guards it
