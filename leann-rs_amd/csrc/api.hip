@@ -254,8 +254,8 @@ static uint32_t pick_hash_bits(uint32_t ef) {
     return b;
 }
 
-template <typename K>
-static int launch_one(K kernel, int nthreads, size_t lds, const GraphView &g, const SearchArgs &a, hipStream_t st) {
+using SearchKernel = void (*)(GraphView, SearchArgs); // every traversal kernel of search.cuh
+static int launch_one(SearchKernel kernel, int nthreads, size_t lds, const GraphView &g, const SearchArgs &a, hipStream_t st) {
     if (lds > 64 * 1024)
         HIP_CHECK_RET(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     hipLaunchKernelGGL(kernel, dim3(a.nq), dim3(nthreads), lds, st, g, a);
@@ -280,15 +280,11 @@ template <int T, int R, int NW>
 static int launch_search_NW(const GraphView &g, const SearchArgs &a, hipStream_t st) {
     size_t lds;
     if (int rc = search_lds_checked(g, a, &lds, NW)) return rc;
+    SearchKernel k = a.allow ? beam_search_filtered_kernel<T, R, NW> : a.q_rows ? beam_search_kernel<T, R, NW, true> : beam_search_kernel<T, R, NW, false>;
     if constexpr (NW != 8)
-        if (wide_graph(g)) {
-            if (a.allow) return launch_one(wide_beam_search_filtered_kernel<T, R, NW>, NW * 64, lds, g, a, st);
-            if (a.q_rows) return launch_one(wide_beam_search_kernel<T, R, NW, true>, NW * 64, lds, g, a, st);
-            return launch_one(wide_beam_search_kernel<T, R, NW, false>, NW * 64, lds, g, a, st);
-        }
-    if (a.allow) return launch_one(beam_search_filtered_kernel<T, R, NW>, NW * 64, lds, g, a, st);
-    if (a.q_rows) return launch_one(beam_search_kernel<T, R, NW, true>, NW * 64, lds, g, a, st);
-    return launch_one(beam_search_kernel<T, R, NW, false>, NW * 64, lds, g, a, st);
+        if (wide_graph(g))
+            k = a.allow ? wide_beam_search_filtered_kernel<T, R, NW> : a.q_rows ? wide_beam_search_kernel<T, R, NW, true> : wide_beam_search_kernel<T, R, NW, false>;
+    return launch_one(k, NW * 64, lds, g, a, st);
 }
 
 // Waves per query: 4 for throughput batches (4 workgroups per CU hide each other's dependent hops);
@@ -308,37 +304,19 @@ template <int T, int R>
 static int launch_search_feat(const GraphView &g, const SearchArgs &a, hipStream_t st) {
     size_t lds;
     if (int rc = search_lds_checked(g, a, &lds, a.nq <= 512 ? 16 : 4)) return rc;
-    const bool wide = wide_graph(g);
-    if (T == 1 && g.feat_h == 256 && !leann_knobs().no_feat256) { // four rows per wave instruction
-        if (wide) {
-            if (a.nq <= 512) {
-                if (a.allow) return launch_one(wide_beam_search_feat256_filtered_kernel<1, 16>, 16 * 64, lds, g, a, st);
-                return launch_one(wide_beam_search_feat256_kernel<1, 16>, 16 * 64, lds, g, a, st);
-            }
-            if (a.allow) return launch_one(wide_beam_search_feat256_filtered_kernel<LEANN_FEAT_G, 4>, 4 * 64, lds, g, a, st);
-            return launch_one(wide_beam_search_feat256_kernel<LEANN_FEAT_G, 4>, 4 * 64, lds, g, a, st);
-        }
-        if (a.nq <= 512) {
-            if (a.allow) return launch_one(beam_search_feat256_filtered_kernel<1, 16>, 16 * 64, lds, g, a, st);
-            return launch_one(beam_search_feat256_kernel<1, 16>, 16 * 64, lds, g, a, st);
-        }
-        if (a.allow) return launch_one(beam_search_feat256_filtered_kernel<LEANN_FEAT_G, 4>, 4 * 64, lds, g, a, st);
-        return launch_one(beam_search_feat256_kernel<LEANN_FEAT_G, 4>, 4 * 64, lds, g, a, st);
-    }
-    if (wide) {
-        if (a.nq <= 512) {
-            if (a.allow) return launch_one(wide_beam_search_feat_filtered_kernel<T, R, 16>, 16 * 64, lds, g, a, st);
-            return launch_one(wide_beam_search_feat_kernel<T, R, 16>, 16 * 64, lds, g, a, st);
-        }
-        if (a.allow) return launch_one(wide_beam_search_feat_filtered_kernel<T, R, 4>, 4 * 64, lds, g, a, st);
-        return launch_one(wide_beam_search_feat_kernel<T, R, 4>, 4 * 64, lds, g, a, st);
-    }
-    if (a.nq <= 512) {
-        if (a.allow) return launch_one(beam_search_feat_filtered_kernel<T, R, 16>, 16 * 64, lds, g, a, st);
-        return launch_one(beam_search_feat_kernel<T, R, 16>, 16 * 64, lds, g, a, st);
-    }
-    if (a.allow) return launch_one(beam_search_feat_filtered_kernel<T, R, 4>, 4 * 64, lds, g, a, st);
-    return launch_one(beam_search_feat_kernel<T, R, 4>, 4 * 64, lds, g, a, st);
+    const bool wide = wide_graph(g), filt = a.allow != nullptr, small = a.nq <= 512; // small batches: 16 waves per query, else 4
+    SearchKernel k;
+    if (T == 1 && g.feat_h == 256 && !leann_knobs().no_feat256) // four rows per wave instruction
+        k = wide ? (small ? (filt ? wide_beam_search_feat256_filtered_kernel<1, 16> : wide_beam_search_feat256_kernel<1, 16>)
+                          : (filt ? wide_beam_search_feat256_filtered_kernel<LEANN_FEAT_G, 4> : wide_beam_search_feat256_kernel<LEANN_FEAT_G, 4>))
+                 : (small ? (filt ? beam_search_feat256_filtered_kernel<1, 16> : beam_search_feat256_kernel<1, 16>)
+                          : (filt ? beam_search_feat256_filtered_kernel<LEANN_FEAT_G, 4> : beam_search_feat256_kernel<LEANN_FEAT_G, 4>));
+    else
+        k = wide ? (small ? (filt ? wide_beam_search_feat_filtered_kernel<T, R, 16> : wide_beam_search_feat_kernel<T, R, 16>)
+                          : (filt ? wide_beam_search_feat_filtered_kernel<T, R, 4> : wide_beam_search_feat_kernel<T, R, 4>))
+                 : (small ? (filt ? beam_search_feat_filtered_kernel<T, R, 16> : beam_search_feat_kernel<T, R, 16>)
+                          : (filt ? beam_search_feat_filtered_kernel<T, R, 4> : beam_search_feat_kernel<T, R, 4>));
+    return launch_one(k, small ? 16 * 64 : 4 * 64, lds, g, a, st);
 }
 
 // recompute-on mode: queries [nq x dims] -> g = W q [nq x feat_h] into the stream's scratch (f32 MFMA, k-ordered chains)
@@ -419,32 +397,36 @@ extern "C" int leann_backend_search_batch_device(const leann_backend *hc, const 
                                                       d_counts, d_stats, stream);
 }
 
-// Filtered traversal (SURVEY.md §8f rank 3): the allow-bitmap is evaluated inside the kernel instead of the
-// reference's fetch_k = 5*top_k over-fetch + post-filter (src/index/searcher.rs:129-133,:190-194).
-extern "C" int leann_backend_search_filtered_batch_device(const leann_backend *hc, const float *d_queries, size_t nq,
-                                                          size_t top_k, size_t complexity, const uint8_t *d_allow,
-                                                          size_t allow_stride, uint64_t *d_keys, float *d_dists,
-                                                          uint32_t *d_counts, uint32_t *d_stats, void *stream) {
-    leann_backend *h = const_cast<leann_backend *>(hc);
-    if (!h || !d_queries || !d_keys || !d_dists || !d_counts || top_k == 0) {
-        leann_set_error("leann_backend_search_batch_device: null/zero argument");
-        return LEANN_ERR_INVALID;
-    }
-    if (d_allow && allow_stride && allow_stride < (h->g.n + 7) / 8) {
-        leann_set_error("filtered search: allow_stride %zu is smaller than the %zu-byte bitmap", allow_stride, (size_t)(h->g.n + 7) / 8);
-        return LEANN_ERR_INVALID;
-    }
+// The search on a plain handle (internal.h): what the filter means for this index, the live mask of removals (consolidate.hip), then
+// the graph walk or the exact scan of the allowed rows (scan.hip).
+int leann_internal_search_plain(leann_backend *h, const float *d_queries, size_t nq, size_t top_k, size_t complexity, const SearchFilter &f,
+                                uint64_t *d_keys, float *d_dists, uint32_t *d_counts, uint32_t *d_stats, hipStream_t st) {
+    if (int rc = leann_internal_check_allow_stride(f, h->g.n)) return rc;
     if (nq == 0) return LEANN_OK;
-    HIP_CHECK_RET(hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
+    if (f.exact && h->g.feat_h) {
+        leann_set_error("exact filtered search needs stored vectors; this index recomputes them from features (use leann_recompute_search_batch_device with an allow mask)");
+        return LEANN_ERR_UNSUPPORTED;
+    }
     if (h->g.n == 0) {
         HIP_CHECK_RET(hipMemsetAsync(d_counts, 0, nq * 4, st));
         return LEANN_OK;
     }
-    if (h->sharded) { // composite handle: fan out, gather, merge (shard.hip); d_stats stays [nq x 4]: summed over the shards
-        ShardFilterArgs fa;
-        fa.d_allow = d_allow; fa.allow_stride = allow_stride;
-        return leann_internal_sharded_search(h->sharded, d_queries, nq, top_k, complexity, fa, d_keys, d_dists, d_counts, d_stats, st, nullptr);
+    // Removals: a registered filter holds live positions only (leann_backend_filter_create) and is never masked again.  Any other walk
+    // runs under live AND the caller's bitmap — without a bitmap, under the live mask until the graph has been repaired —, and an
+    // exact answer compacts live AND allow.
+    const leann_filter *reg = f.registered;
+    const uint8_t *allow = reg ? reg->d_allow : f.d_allow;
+    size_t allow_stride = reg ? 0 : f.allow_stride;
+    if (!reg)
+        if (int rc = leann_internal_live_allow(h, allow, allow_stride, nq, !f.exact, st, &allow, &allow_stride)) return rc;
+    if (f.exact) {
+        if (!allow) { leann_set_error("exact filtered search: no filter given"); return LEANN_ERR_INVALID; }
+        if (d_stats) HIP_CHECK_RET(hipMemsetAsync(d_stats, 0, nq * 16, st)); // no walk: no evaluations / hops to count
+        if (reg) // the compacted list of allowed rows exists already
+            return leann_internal_filtered_exact_list(h->g.X, h->g.d, h->g.ld, d_queries, nq, top_k, reg->d_list, reg->n_allowed, h->key_offset,
+                                                      d_keys, d_dists, d_counts, st);
+        return leann_internal_filtered_exact(h->g.X, h->g.n, h->g.d, h->g.ld, d_queries, nq, top_k, allow, allow_stride, h->key_offset, d_keys,
+                                             d_dists, d_counts, st);
     }
     SearchArgs a{};
     a.queries = d_queries;
@@ -458,10 +440,8 @@ extern "C" int leann_backend_search_filtered_batch_device(const leann_backend *h
     a.out_dists = d_dists;
     a.out_counts = d_counts;
     a.out_stats = d_stats;
-    a.allow = d_allow;
+    a.allow = allow;
     a.allow_stride = allow_stride;
-    if (h->d_live) // removals (consolidate.hip): the walk runs under live AND the caller's bitmap until the graph has been repaired
-        if (int rc = leann_internal_live_allow(h, d_allow, allow_stride, nq, true, st, &a.allow, &a.allow_stride)) return rc;
 #ifdef LEANN_STAMPS
     if (const unsigned long long e = leann_knobs().stamp_buf) { // diagnostic build: [nq x 8] u64 device buffer address in the environment
         a.out_nexp = reinterpret_cast<uint32_t *>(e);
@@ -469,6 +449,29 @@ extern "C" int leann_backend_search_filtered_batch_device(const leann_backend *h
     }
 #endif
     return leann_internal_launch_search(h, a, st);
+}
+// a device-pointer entry point: the composite handle fans out, gathers and merges (shard.hip; d_stats stays [nq x 4]: summed over the shards)
+static int search_device(leann_backend *h, const float *d_queries, size_t nq, size_t top_k, size_t complexity, const SearchFilter &f,
+                         uint64_t *d_keys, float *d_dists, uint32_t *d_counts, uint32_t *d_stats, hipStream_t st) {
+    HIP_CHECK_RET(hipSetDevice(h->device));
+    if (h->sharded) return leann_internal_sharded_search(h->sharded, d_queries, nq, top_k, complexity, f, d_keys, d_dists, d_counts, d_stats, st, nullptr);
+    return leann_internal_search_plain(h, d_queries, nq, top_k, complexity, f, d_keys, d_dists, d_counts, d_stats, st);
+}
+
+// Filtered traversal (SURVEY.md §8f rank 3): the allow-bitmap is evaluated inside the kernel instead of the
+// reference's fetch_k = 5*top_k over-fetch + post-filter (src/index/searcher.rs:129-133,:190-194).
+extern "C" int leann_backend_search_filtered_batch_device(const leann_backend *hc, const float *d_queries, size_t nq,
+                                                          size_t top_k, size_t complexity, const uint8_t *d_allow,
+                                                          size_t allow_stride, uint64_t *d_keys, float *d_dists,
+                                                          uint32_t *d_counts, uint32_t *d_stats, void *stream) {
+    leann_backend *h = const_cast<leann_backend *>(hc);
+    if (!h || !d_queries || !d_keys || !d_dists || !d_counts || top_k == 0) {
+        leann_set_error("leann_backend_search_batch_device: null/zero argument");
+        return LEANN_ERR_INVALID;
+    }
+    SearchFilter f;
+    f.d_allow = d_allow; f.allow_stride = allow_stride;
+    return search_device(h, d_queries, nq, top_k, complexity, f, d_keys, d_dists, d_counts, d_stats, (hipStream_t)stream);
 }
 
 // BackendSearcher::search batched over host pointers.
@@ -482,9 +485,6 @@ enum { FILTER_WALK = 0, FILTER_EXACT = 1, FILTER_AUTO = 2 };
 static int search_filtered_batch_host(const leann_backend *hc, const float *queries, size_t nq, size_t top_k, size_t complexity,
                                       const uint8_t *allow, size_t allow_stride, uint64_t *keys, float *dists, uint32_t *counts, int mode,
                                       const leann_filter *flt = nullptr);
-int leann_internal_compact_allow(const uint8_t *d_allow, size_t n, uint32_t **d_list, size_t *n_list, hipStream_t st);
-int leann_internal_and_live_inplace(const leann_backend *h, uint8_t *d_bitmap);
-void leann_internal_scratch_release(void *p);
 
 // Registered filters: a server that answers many queries under the same metadata filter uploads and compacts the bitmap once
 // (the host-pointer calls above re-send N/8 bytes and re-compact them for every query: 1.25 MB at 10M rows).
@@ -588,9 +588,6 @@ extern "C" int leann_backend_search_filtered_exact_batch(const leann_backend *hc
     }
     return search_filtered_batch_host(hc, queries, nq, top_k, 0, allow, allow_stride, keys, dists, counts, FILTER_EXACT);
 }
-int leann_internal_filtered_exact(const float *d_rows, size_t n, size_t dims, size_t ld, const float *d_queries, size_t nq, size_t top_k,
-                                  const uint8_t *d_allow, size_t allow_stride, uint64_t key_offset, uint64_t *d_keys, float *d_dists,
-                                  uint32_t *d_counts, hipStream_t st);
 extern "C" int leann_backend_search_filtered_exact_batch_device(const leann_backend *hc, const float *d_queries, size_t nq, size_t top_k,
                                                                 const uint8_t *d_allow, size_t allow_stride, uint64_t *d_keys,
                                                                 float *d_dists, uint32_t *d_counts, void *stream) {
@@ -599,35 +596,9 @@ extern "C" int leann_backend_search_filtered_exact_batch_device(const leann_back
         leann_set_error("leann_backend_search_filtered_exact_batch_device: null/zero argument");
         return LEANN_ERR_INVALID;
     }
-    if (h->sharded) { // every shard scans its own allowed rows; lists merged by (dist, key)
-        if (allow_stride && allow_stride < (h->g.n + 7) / 8) {
-            leann_set_error("filtered search: allow_stride %zu is smaller than the %zu-byte bitmap", allow_stride, (size_t)(h->g.n + 7) / 8);
-            return LEANN_ERR_INVALID;
-        }
-        if (nq == 0) return LEANN_OK;
-        ShardFilterArgs fa;
-        fa.d_allow = d_allow; fa.allow_stride = allow_stride; fa.exact = true;
-        return leann_internal_sharded_search(h->sharded, d_queries, nq, top_k, 0, fa, d_keys, d_dists, d_counts, nullptr, (hipStream_t)stream, nullptr);
-    }
-    if (h->g.feat_h) {
-        leann_set_error("exact filtered search needs stored vectors; this index recomputes them from features (use leann_recompute_search_batch_device with an allow mask)");
-        return LEANN_ERR_UNSUPPORTED;
-    }
-    if (allow_stride && allow_stride < (h->g.n + 7) / 8) {
-        leann_set_error("filtered search: allow_stride %zu is smaller than the %zu-byte bitmap", allow_stride, (size_t)(h->g.n + 7) / 8);
-        return LEANN_ERR_INVALID;
-    }
-    if (nq == 0) return LEANN_OK;
-    HIP_CHECK_RET(hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    if (h->g.n == 0) {
-        HIP_CHECK_RET(hipMemsetAsync(d_counts, 0, nq * 4, st));
-        return LEANN_OK;
-    }
-    if (h->d_live) // removals: only live rows are compacted
-        if (int rc = leann_internal_live_allow(h, d_allow, allow_stride, nq, false, st, &d_allow, &allow_stride)) return rc;
-    return leann_internal_filtered_exact(h->g.X, h->g.n, h->g.d, h->g.ld, d_queries, nq, top_k, d_allow, allow_stride, h->key_offset, d_keys,
-                                         d_dists, d_counts, st);
+    SearchFilter f; // (a composite handle: every shard scans its own allowed rows; lists merged by (dist, key))
+    f.d_allow = d_allow; f.allow_stride = allow_stride; f.exact = true;
+    return search_device(h, d_queries, nq, top_k, 0, f, d_keys, d_dists, d_counts, nullptr, (hipStream_t)stream);
 }
 static int search_filtered_batch_host_impl(const leann_backend *hc, const float *queries, size_t nq, size_t top_k, size_t complexity,
                                       const uint8_t *allow, size_t allow_stride, uint64_t *keys, float *dists, uint32_t *counts, int mode,
@@ -645,11 +616,7 @@ static int search_filtered_batch_host_impl(const leann_backend *hc, const float 
         leann_set_error("leann_backend_search_batch: null argument");
         return LEANN_ERR_INVALID;
     }
-    if (nq == 0 || top_k == 0) {
-        for (size_t i = 0; i < nq; i++) counts[i] = 0;
-        return LEANN_OK;
-    }
-    if (h->g.n == 0) {
+    if (nq == 0 || top_k == 0 || h->g.n == 0) { // nothing to search: answered on the host, no workspace, no device call
         for (size_t i = 0; i < nq; i++) counts[i] = 0;
         return LEANN_OK;
     }
@@ -701,12 +668,7 @@ static int search_filtered_batch_host_impl(const leann_backend *hc, const float 
         return fail(LEANN_ERR_DEVICE);
     hipStream_t st = w->stream;
     if (allow) {
-        const size_t nbytes = (h->g.n + 7) / 8;
-        if (allow_stride && allow_stride < nbytes) {
-            leann_set_error("filtered search: allow_stride %zu is smaller than the %zu-byte bitmap", allow_stride, nbytes);
-            return fail(LEANN_ERR_INVALID);
-        }
-        const size_t total = allow_stride ? allow_stride * nq : nbytes;
+        const size_t total = allow_stride ? allow_stride * nq : (h->g.n + 7) / 8;
         void *pa = w->d_allow;
         if (grow(&pa, w->cap_allow, total, 1)) { w->d_allow = (uint8_t *)pa; return fail(LEANN_ERR_DEVICE); }
         w->d_allow = (uint8_t *)pa;
@@ -720,55 +682,18 @@ static int search_filtered_batch_host_impl(const leann_backend *hc, const float 
         leann_set_error("H2D copy of queries failed");
         return fail(LEANN_ERR_DEVICE);
     }
-    SearchArgs a{};
-    a.queries = zc_in ? reinterpret_cast<const float *>(w->pin) : w->d_q;
-    a.ldq = (uint32_t)d;
-    a.nq = (uint32_t)nq;
-    a.k = (uint32_t)top_k;
-    a.ef = (uint32_t)std::max(leann_internal_effective_complexity(h, complexity), top_k);
-    a.key_offset = h->key_offset;
-    a.out_keys = zero_copy ? reinterpret_cast<uint64_t *>(w->pin + o_keys) : w->d_keys;
-    a.out_dists = zero_copy ? reinterpret_cast<float *>(w->pin + o_dists) : w->d_dists;
-    a.out_counts = zero_copy ? reinterpret_cast<uint32_t *>(w->pin + o_counts) : w->d_counts;
-    a.out_stats = zero_copy ? reinterpret_cast<uint32_t *>(w->pin + o_stats) : w->d_stats;
-    a.allow = flt ? flt->d_allow : (allow ? w->d_allow : nullptr);
-    a.allow_stride = flt ? 0 : allow_stride;
-    if (h->sharded) { // composite handle: the same decision (exact / walk) for every shard, per-shard lists merged by (dist, key)
-        ShardFilterArgs fa;
-        fa.exact = exact;
-        if (flt) fa.sub = flt->parts.data();
-        else { fa.d_allow = a.allow; fa.allow_stride = a.allow_stride; }
-        if (flt && flt->parts.size() != leann_internal_sharded_count(h->sharded)) {
-            leann_set_error("registered filter was not made for this sharded handle");
-            return fail(LEANN_ERR_INVALID);
-        }
-        rc = leann_internal_sharded_search(h->sharded, w->d_q, nq, top_k, complexity, fa, w->d_keys, w->d_dists, w->d_counts, w->d_stats, st, nullptr);
-    } else if (exact && flt) {
-        if (h->g.feat_h) {
-            leann_set_error("exact filtered search needs stored vectors; this index recomputes them from features");
-            return fail(LEANN_ERR_UNSUPPORTED);
-        }
-        if (hipMemsetAsync(w->d_stats, 0, nq * 16, st) != hipSuccess) return fail(LEANN_ERR_DEVICE);
-        rc = leann_internal_filtered_exact_list(h->g.X, h->g.d, h->g.ld, w->d_q, nq, top_k, flt->d_list, flt->n_allowed, h->key_offset,
-                                                w->d_keys, w->d_dists, w->d_counts, st);
-    } else if (exact) {
-        if (h->g.feat_h) {
-            leann_set_error("exact filtered search needs stored vectors; this index recomputes them from features");
-            return fail(LEANN_ERR_UNSUPPORTED);
-        }
-        if (hipMemsetAsync(w->d_stats, 0, nq * 16, st) != hipSuccess) return fail(LEANN_ERR_DEVICE);
-        const uint8_t *ea = w->d_allow;
-        size_t es = allow_stride;
-        if (h->d_live) rc = leann_internal_live_allow(h, ea, es, nq, false, st, &ea, &es);
-        if (rc) return fail(rc);
-        rc = leann_internal_filtered_exact(h->g.X, h->g.n, h->g.d, h->g.ld, w->d_q, nq, top_k, ea, es, h->key_offset,
-                                           w->d_keys, w->d_dists, w->d_counts, st);
-    } else {
-        // removals: a registered filter holds live positions only (leann_backend_filter_create); any other walk runs under live AND allow
-        if (h->d_live && !flt) rc = leann_internal_live_allow(h, a.allow, a.allow_stride, nq, true, st, &a.allow, &a.allow_stride);
-        if (rc) return fail(rc);
-        rc = leann_internal_launch_search(h, a, st);
-    }
+    // one search: the same decision (exact / walk) for a plain handle and for every shard of a composite one
+    SearchFilter f;
+    f.exact = exact;
+    if (flt) f.registered = flt;
+    else if (allow) { f.d_allow = w->d_allow; f.allow_stride = allow_stride; }
+    const float *d_q = zc_in ? reinterpret_cast<const float *>(w->pin) : w->d_q;
+    uint64_t *d_keys = zero_copy ? reinterpret_cast<uint64_t *>(w->pin + o_keys) : w->d_keys;
+    float *d_dists = zero_copy ? reinterpret_cast<float *>(w->pin + o_dists) : w->d_dists;
+    uint32_t *d_counts = zero_copy ? reinterpret_cast<uint32_t *>(w->pin + o_counts) : w->d_counts;
+    uint32_t *d_stats = zero_copy ? reinterpret_cast<uint32_t *>(w->pin + o_stats) : w->d_stats;
+    rc = h->sharded ? leann_internal_sharded_search(h->sharded, d_q, nq, top_k, complexity, f, d_keys, d_dists, d_counts, d_stats, st, nullptr)
+                    : leann_internal_search_plain(h, d_q, nq, top_k, complexity, f, d_keys, d_dists, d_counts, d_stats, st);
     if (rc) return fail(rc);
     std::vector<uint32_t> hstats(ns * nq * 4);
     if (zero_copy) {
@@ -807,7 +732,7 @@ static int search_filtered_batch_host_impl(const leann_backend *hc, const float 
     }
     if (n_lost) { // search.cuh: the last visited-table level filled up (not reachable with the pools ensure_gpool sizes)
         leann_set_error("search: %zu of %zu queries ran out of visited-set space at complexity %zu; lower the complexity", n_lost, nq,
-                        (size_t)a.ef);
+                        std::max(leann_internal_effective_complexity(h, complexity), top_k));
         return LEANN_ERR_OVERFLOW;
     }
     return LEANN_OK;

@@ -1,8 +1,8 @@
 // consolidate.hip — removing passages from a graph index.
 //
 // leann_backend_remove marks positions as removed (tombstones): nothing moves, positions are never renumbered, and every search
-// entry point masks them out (api.hip, through leann_internal_live_allow).  While live lists still name removed positions the
-// unfiltered walk has to run the filtered kernel; leann_backend_consolidate repairs the graph so that it need not:
+// masks them out (api.hip: leann_internal_search_plain, through leann_internal_live_allow).  While live lists still name removed
+// positions the unfiltered walk has to run the filtered kernel; leann_backend_consolidate repairs the graph so that it need not:
 //
 //   per level, 1. mark    every live node whose list names a removed id goes onto a work list;
 //              2. repair  one workgroup per work-list entry p re-links p through its removed neighbours (FreshDiskANN Alg. 4):
@@ -25,10 +25,6 @@
 #include <string>
 #include <sys/stat.h>
 #include <vector>
-
-int leann_internal_filtered_exact(const float *d_rows, size_t n, size_t dims, size_t ld, const float *d_queries, size_t nq, size_t top_k,
-                                  const uint8_t *d_allow, size_t allow_stride, uint64_t key_offset, uint64_t *d_keys, float *d_dists,
-                                  uint32_t *d_counts, hipStream_t st);
 
 __device__ __forceinline__ bool bit_live(const uint8_t *__restrict__ live, uint32_t id) { return (live[id >> 3] >> (id & 7)) & 1; }
 

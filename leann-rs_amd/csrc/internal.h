@@ -85,8 +85,8 @@ struct leann_backend {
     std::map<hipStream_t, std::pair<uint8_t *, size_t>> live_scratch; // per stream: live AND the caller's bitmap(s)
 };
 // Removals (consolidate.hip).  leann_internal_live_allow: the bitmap a search on `h` has to run under — the caller's (may be null)
-// ANDed with the live mask into the stream's scratch; *out = d_allow unchanged for a handle without removals.  `walk`: the caller is
-// the graph walk, which needs no mask of its own once no live list names a removed position.
+// ANDed with the live mask into the stream's scratch; *out = d_allow unchanged for a handle without removals.  `walk`: the search is
+// the graph walk, which needs no mask of its own once no live list names a removed position.  One caller: leann_internal_search_plain.
 int leann_internal_live_allow(leann_backend *h, const uint8_t *d_allow, size_t allow_stride, size_t nq, bool walk, hipStream_t st,
                               const uint8_t **out, size_t *out_stride);
 int leann_internal_set_removed(leann_backend *h, const uint8_t *bitmap, size_t n_removed); // adopt a bitmap (open): device mask + n_pending
@@ -121,21 +121,42 @@ struct leann_filter {
     uint64_t epoch = 0;         // the handle's removal_epoch when the filter was made (its bitmap holds live positions only)
     std::vector<leann_filter *> parts;
 };
-// how a sharded search filters: a bitmap over GLOBAL positions on the first device (sliced per shard at byte boundaries), or one
-// registered sub-filter per shard; `exact`: scan the allowed rows of every shard instead of walking its graph
-struct ShardFilterArgs {
+// How one search call filters — the same description for every entry point, for a plain handle and for a composite one.
+// Nothing set: no filter.  d_allow: a device bitmap over the handle's positions (a composite handle: GLOBAL positions on its first
+// device, sliced per shard at byte boundaries); allow_stride == 0: one bitmap for the batch, else bytes from one query's to the next.
+// registered: a leann_filter of this handle instead (a composite handle's holds one sub-filter per shard).  exact: scan the allowed
+// rows instead of walking the graph.
+struct SearchFilter {
     const uint8_t *d_allow = nullptr;
     size_t allow_stride = 0;
-    const leann_filter *const *sub = nullptr;
+    const leann_filter *registered = nullptr;
     bool exact = false;
 };
-int leann_internal_sharded_search(leann_sharded *s, const float *d_queries, size_t nq, size_t top_k, size_t complexity, const ShardFilterArgs &fa,
+inline int leann_internal_check_allow_stride(const SearchFilter &f, size_t n) { // per-query bitmaps of n positions must not overlap
+    if (f.d_allow && f.allow_stride && f.allow_stride < (n + 7) / 8) {
+        leann_set_error("filtered search: allow_stride %zu is smaller than the %zu-byte bitmap", f.allow_stride, (n + 7) / 8);
+        return LEANN_ERR_INVALID;
+    }
+    return LEANN_OK;
+}
+// THE search on a plain (non-sharded) handle — every entry point, and every shard of a composite handle, ends here (api.hip).  The
+// caller has selected h's device; queries and outputs are device-accessible; d_stats [nq x 4] may be null.  Stream-ordered on `st`.
+// (hidden: the library exports no name for it)
+__attribute__((visibility("hidden"))) int leann_internal_search_plain(leann_backend *h, const float *d_queries, size_t nq, size_t top_k, size_t complexity, const SearchFilter &f,
+                                uint64_t *d_keys, float *d_dists, uint32_t *d_counts, uint32_t *d_stats, hipStream_t st);
+int leann_internal_sharded_search(leann_sharded *s, const float *d_queries, size_t nq, size_t top_k, size_t complexity, const SearchFilter &f,
                                   uint64_t *d_keys, float *d_dists, uint32_t *d_counts, uint32_t *d_stats, hipStream_t st, uint64_t *ticket);
 int leann_internal_sharded_save(const leann_sharded *s, const char *index_path_stem);
 uint64_t leann_internal_sharded_lo(const leann_sharded *s, size_t g);
 int leann_internal_filtered_exact_list(const float *d_rows, size_t dims, size_t ld, const float *d_queries, size_t nq, size_t top_k,
                                        const uint32_t *d_list, size_t m, uint64_t key_offset, uint64_t *d_keys, float *d_dists,
                                        uint32_t *d_counts, hipStream_t st);
+int leann_internal_filtered_exact(const float *d_rows, size_t n, size_t dims, size_t ld, const float *d_queries, size_t nq, size_t top_k,
+                                  const uint8_t *d_allow, size_t allow_stride, uint64_t key_offset, uint64_t *d_keys, float *d_dists,
+                                  uint32_t *d_counts, hipStream_t st);
+int leann_internal_compact_allow(const uint8_t *d_allow, size_t n, uint32_t **d_list, size_t *n_list, hipStream_t st);
+int leann_internal_and_live_inplace(const leann_backend *h, uint8_t *d_bitmap);
+void leann_internal_scratch_release(void *p);
 extern "C" void leann_sharded_close(leann_sharded *s);
 
 int leann_internal_launch_search(leann_backend *h, SearchArgs a, hipStream_t st);

@@ -524,15 +524,17 @@ extern "C" int leann_sharded_attach(leann_backend *local, const void *unique_id1
 // The traversal is queued behind `stream`; exchange and merge run on the handle's own stream.  ticket == nullptr: `stream` also waits
 // for the merge (results are ordered on `stream`).
 int leann_internal_sharded_search(leann_sharded *s, const float *d_queries, size_t nq, size_t top_k, size_t complexity,
-                                  const ShardFilterArgs &fa, uint64_t *d_keys, float *d_dists, uint32_t *d_counts,
+                                  const SearchFilter &f, uint64_t *d_keys, float *d_dists, uint32_t *d_counts,
                                   uint32_t *d_stats, hipStream_t st, uint64_t *ticket) {
     if (!s || !d_queries || !d_keys || !d_dists || !d_counts || top_k == 0) { leann_set_error("sharded search: null/zero argument"); return LEANN_ERR_INVALID; }
-    const uint8_t *d_allow = fa.d_allow;
-    const size_t allow_stride = fa.allow_stride;
+    const uint8_t *d_allow = f.d_allow;
+    const size_t allow_stride = f.allow_stride;
     const size_t G = s->rccl ? (size_t)s->world : s->shards.size();
     if (G * top_k > 12288) { leann_set_error("sharded search: shards x top_k = %zu x %zu exceeds the merge kernel's 12288 entries", G, top_k); return LEANN_ERR_INVALID; }
-    if (s->rccl && (fa.sub || fa.exact)) { leann_set_error("sharded search over RCCL: registered / exact filters are a one-process feature"); return LEANN_ERR_UNSUPPORTED; }
+    if (s->rccl && (f.registered || f.exact)) { leann_set_error("sharded search over RCCL: registered / exact filters are a one-process feature"); return LEANN_ERR_UNSUPPORTED; }
     if (d_allow && s->rccl && (s->shards[0].lo & 7)) { leann_set_error("sharded filtered search: the shard does not start at a multiple of 8"); return LEANN_ERR_UNSUPPORTED; }
+    if (f.registered && f.registered->parts.size() != s->shards.size()) { leann_set_error("registered filter was not made for this sharded handle"); return LEANN_ERR_INVALID; }
+    if (int rc = leann_internal_check_allow_stride(f, s->total_rows)) return rc;
     if (nq == 0) return LEANN_OK;
     std::lock_guard<std::mutex> lk(s->mu); // enqueue phase only; the work itself is asynchronous
     HIP_CHECK_RET(hipSetDevice(s->primary));
@@ -549,9 +551,10 @@ int leann_internal_sharded_search(leann_sharded *s, const float *d_queries, size
         if (int rc = grow_dev((void **)&sl.local, &sl.cap_local, blk)) return rc;
         if (sl.used) HIP_CHECK_RET(hipStreamWaitEvent(st, sl.done, 0)); // the all-gather that last read this slot's block has finished
         ShardDev &sd = s->shards[0];
-        int rc = leann_backend_search_filtered_batch_device(sd.h, d_queries, nq, top_k, complexity, d_allow ? d_allow + sd.lo / 8 : nullptr,
-                                                            allow_stride, (uint64_t *)(sl.local + koff), (float *)(sl.local + doff),
-                                                            (uint32_t *)(sl.local + coff), d_stats, st);
+        SearchFilter fg = f;
+        if (d_allow) fg.d_allow = d_allow + sd.lo / 8;
+        int rc = leann_internal_search_plain(sd.h, d_queries, nq, top_k, complexity, fg, (uint64_t *)(sl.local + koff), (float *)(sl.local + doff),
+                                             (uint32_t *)(sl.local + coff), d_stats, st);
         if (rc) return rc;
         HIP_CHECK_RET(hipEventRecord(sd.ev[tk & 1], st));
         HIP_CHECK_RET(hipStreamWaitEvent(s->xstream, sd.ev[tk & 1], 0));
@@ -590,18 +593,11 @@ int leann_internal_sharded_search(leann_sharded *s, const float *d_queries, size
             uint64_t *ok = (uint64_t *)(blkp + koff);
             float *od = (float *)(blkp + doff);
             uint32_t *oc = (uint32_t *)(blkp + coff);
-            int rc;
-            if (fa.exact && stats_g) HIP_CHECK_RET(hipMemsetAsync(stats_g, 0, nq * 16, sd.st)); // no walk: no evaluations / hops to count
-            if (fa.sub && fa.exact) // registered filter, answered exactly: the shard's compacted list of allowed rows is scanned
-                rc = sd.h->g.feat_h ? (leann_set_error("exact filtered search needs stored vectors; this index recomputes them from features"), (int)LEANN_ERR_UNSUPPORTED)
-                                    : leann_internal_filtered_exact_list(sd.h->g.X, sd.h->g.d, sd.h->g.ld, q, nq, top_k, fa.sub[g]->d_list, fa.sub[g]->n_allowed,
-                                                                         sd.h->key_offset, ok, od, oc, sd.st);
-            else if (fa.sub) // registered filter inside the walk: the sub-filter's bitmap lives on the shard's device already
-                rc = leann_backend_search_filtered_batch_device(sd.h, q, nq, top_k, complexity, fa.sub[g]->d_allow, 0, ok, od, oc, stats_g, sd.st);
-            else if (fa.exact)
-                rc = leann_backend_search_filtered_exact_batch_device(sd.h, q, nq, top_k, allow_g, allow_stride, ok, od, oc, sd.st);
-            else
-                rc = leann_backend_search_filtered_batch_device(sd.h, q, nq, top_k, complexity, allow_g, allow_stride, ok, od, oc, stats_g, sd.st);
+            SearchFilter fg; // the shard's filter: its sub-filter, or its slice of the bitmap(s)
+            fg.exact = f.exact;
+            if (f.registered) fg.registered = f.registered->parts[g];
+            else { fg.d_allow = allow_g; fg.allow_stride = allow_stride; }
+            int rc = leann_internal_search_plain(sd.h, q, nq, top_k, complexity, fg, ok, od, oc, stats_g, sd.st);
             if (rc) { (void)hipSetDevice(s->primary); return rc; }
             if (remote) HIP_CHECK_RET(hipMemcpyPeerAsync(sl.gather + g * blk, s->primary, sd.d_out, sd.device, blk, sd.st));
             if (remote && d_stats) HIP_CHECK_RET(hipMemcpyPeerAsync(sl.stats + g * nq * 4, s->primary, sd.d_stats, sd.device, nq * 16, sd.st));
@@ -627,7 +623,7 @@ int leann_internal_sharded_search(leann_sharded *s, const float *d_queries, size
 
 extern "C" int leann_sharded_search_batch_device(const leann_sharded *s, const float *d_queries, size_t nq, size_t top_k, size_t complexity,
                                                  uint64_t *d_keys, float *d_dists, uint32_t *d_counts, uint32_t *d_stats, void *stream) {
-    return leann_internal_sharded_search(const_cast<leann_sharded *>(s), d_queries, nq, top_k, complexity, ShardFilterArgs{}, d_keys, d_dists, d_counts,
+    return leann_internal_sharded_search(const_cast<leann_sharded *>(s), d_queries, nq, top_k, complexity, SearchFilter{}, d_keys, d_dists, d_counts,
                                          d_stats, (hipStream_t)stream, nullptr);
 }
 uint64_t leann_internal_sharded_lo(const leann_sharded *s, size_t g) { return s && g < s->shards.size() ? s->shards[g].lo : 0; }
@@ -649,7 +645,7 @@ extern "C" int leann_sharded_search_batch_device_async(const leann_sharded *s, c
                                                        size_t complexity, uint64_t *d_keys, float *d_dists, uint32_t *d_counts,
                                                        uint32_t *d_stats, void *stream, uint64_t *ticket) {
     if (!ticket) { leann_set_error("leann_sharded_search_batch_device_async: null ticket"); return LEANN_ERR_INVALID; }
-    return leann_internal_sharded_search(const_cast<leann_sharded *>(s), d_queries, nq, top_k, complexity, ShardFilterArgs{}, d_keys, d_dists, d_counts,
+    return leann_internal_sharded_search(const_cast<leann_sharded *>(s), d_queries, nq, top_k, complexity, SearchFilter{}, d_keys, d_dists, d_counts,
                                          d_stats, (hipStream_t)stream, ticket);
 }
 // `stream` waits for the exchange + merge of `ticket`.  At most two tickets may be outstanding (two result slots rotate): wait for
