@@ -11,7 +11,7 @@ HDRS     := $(wildcard $(CSRC)/*.cuh) $(wildcard $(CSRC)/*.h) include/leann_back
 HOST     := leann-rs_amd/host
 CXXFLAGS := -O2 -std=c++17 -ffp-contract=off -Wall -Wextra -Wno-unused-parameter
 
-all: $(CSRC)/libleann_hip.so oracle $(HOST)/leann $(HOST)/host_selftest $(HOST)/host_selftest_asan $(HOST)/serve_bench
+all: $(CSRC)/libleann_hip.so oracle $(HOST)/leann $(HOST)/host_selftest $(HOST)/host_selftest_asan $(HOST)/serve_bench $(HOST)/row_screen_selftest
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -36,11 +36,15 @@ $(HOST)/host_selftest_asan: $(HOST)/host_selftest.cpp $(HOST)/leann_host.hpp $(H
 	g++ -O1 -g -std=c++17 -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -o $@ \
 	    $(HOST)/host_selftest.cpp -L$(CSRC) -lleann_hip -Wl,-rpath,'$$ORIGIN/../csrc' -Wl,-rpath,/opt/rocm/lib
 
+# the row screen's bound (csrc/row_screen.h) against the canonical distance, on the CPU: no GPU, no library
+$(HOST)/row_screen_selftest: $(HOST)/row_screen_selftest.cpp $(CSRC)/row_screen.h
+	g++ $(CXXFLAGS) -o $@ $(HOST)/row_screen_selftest.cpp -lm
+
 oracle:
 	$(MAKE) -s -C oracle
 
 clean:
-	rm -f $(CSRC)/*.o $(CSRC)/*.so $(HOST)/leann $(HOST)/host_selftest $(HOST)/host_selftest_asan $(HOST)/serve_bench
+	rm -f $(CSRC)/*.o $(CSRC)/*.so $(HOST)/leann $(HOST)/host_selftest $(HOST)/host_selftest_asan $(HOST)/serve_bench $(HOST)/row_screen_selftest
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

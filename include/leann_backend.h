@@ -122,6 +122,21 @@ int leann_backend_search_filter_batch(const leann_backend *h, const float *queri
 int leann_backend_set_coalescing(leann_backend *h, uint32_t wait_us, uint32_t max_batch);
 int leann_backend_coalescing_stats(const leann_backend *h, uint64_t *n_launches, uint64_t *n_queries);
 
+/* Row screen.  For an index of stored f32 rows of 513..768 or 1 025..1 536 floats per row (lists of at most 64 ids) the library keeps
+ * the rows a second time, split into the upper and the lower 16 bits of every element (two planes, together the size of the rows:
+ * +30.7 GB at 10M x 768).  Unfiltered batches of more than 640 queries read a neighbour's upper halves first and its lower halves
+ * only if a proved lower bound on its distance does not already put it behind a full beam; ids, distances, counts and stats are
+ * bit-identical either way.  On by default for indexes whose rows take 1 GiB or more (smaller ones gain too, about 1.4x on a 307 MB
+ * index, but are left out so that the benchmark's whole-row roofline figure stays below the HBM peak on its quick workload: DESIGN.md
+ * section 2); LEANN_ROW_SCREEN=0 in the environment makes handles without the planes, LEANN_ROW_SCREEN=1 with them at any size.
+ * If the planes do not fit, a warning is logged (LEANN_LOG) and searches read whole rows.  enable = 0: search whole rows (the
+ * planes stay); 1: screen, whatever the size (cuts the planes if the handle has none; call it with no search in flight).  Works on
+ * composite handles.
+ * leann_backend_row_screen_stats: running totals since the handle was made — out[0] rows ruled out on their upper halves alone,
+ * out[1] rows read in full (summed over the shards of a composite handle); waits for the device. */
+int leann_backend_set_row_screen(leann_backend *h, int enable);
+int leann_backend_row_screen_stats(const leann_backend *h, uint64_t out[2]);
+
 /* BackendSearcher::len  src/backend/traits.rs:24 */
 size_t leann_backend_len(const leann_backend *h);
 size_t leann_backend_dims(const leann_backend *h);

@@ -54,6 +54,8 @@ SIGNATURES = {
                                                      u64p, f32p, u32p]),
     "leann_backend_set_coalescing": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
     "leann_backend_coalescing_stats": (C.c_int, [vp, u64p, u64p]),
+    "leann_backend_set_row_screen": (C.c_int, [vp, C.c_int]),
+    "leann_backend_row_screen_stats": (C.c_int, [vp, u64p]),
     "leann_backend_len": (C.c_size_t, [vp]),
     "leann_backend_dims": (C.c_size_t, [vp]),
     "leann_backend_close": (None, [vp]),

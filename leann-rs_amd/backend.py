@@ -200,6 +200,15 @@ class BackendSearcher:
         N.check(N.lib().leann_backend_coalescing_stats(self._h, C.byref(a), C.byref(b)))
         return {"launches": a.value, "queries": b.value}
 
+    def set_row_screen(self, enable=True):
+        """split-plane row screen of large unfiltered batches on / off (results are bit-identical either way)"""
+        N.check(N.lib().leann_backend_set_row_screen(self._h, 1 if enable else 0))
+
+    def row_screen_stats(self):
+        out = (C.c_uint64 * 2)()
+        N.check(N.lib().leann_backend_row_screen_stats(self._h, out))
+        return {"ruled_out": int(out[0]), "read_in_full": int(out[1])}
+
     def len(self):
         return int(N.lib().leann_backend_len(self._h))
 

@@ -28,7 +28,7 @@ extern "C" void leann_set_error(const char *fmt, ...) {
     va_end(ap);
 }
 extern "C" const char *leann_last_error(void) { return g_err; }
-void leann_log(int level, const char *fmt, ...) {
+bool leann_log_enabled(int level) {
     static const int threshold = [] {
         const char *e = getenv("LEANN_LOG");
         if (!e) return (int)LEANN_LOG_WARN;
@@ -37,7 +37,10 @@ void leann_log(int level, const char *fmt, ...) {
         if (!strcasecmp(e, "debug") || !strcasecmp(e, "trace")) return (int)LEANN_LOG_DEBUG;
         return (int)LEANN_LOG_WARN;
     }();
-    if (level > threshold) return;
+    return level <= threshold;
+}
+void leann_log(int level, const char *fmt, ...) {
+    if (!leann_log_enabled(level)) return;
     static const char *names[] = {"ERROR", "WARN", "INFO", "DEBUG"};
     char buf[1024];
     va_list ap;
@@ -65,6 +68,7 @@ static LeannKnobs *read_knobs_from_env() {
     k->no_tiled = flag("LEANN_RECOMPUTE_NO_TILED");
     k->hnsw_reference_ef = flag("LEANN_HNSW_REFERENCE_EF");
     k->force_remote = flag("LEANN_DEBUG_FORCE_REMOTE");
+    if (const char *e = getenv("LEANN_ROW_SCREEN")) k->row_screen = (!strcmp(e, "0") || !strcasecmp(e, "off")) ? 0 : (!strcmp(e, "1") || !strcasecmp(e, "on")) ? 2 : 1;
     if (const char *e = getenv("LEANN_COALESCE")) k->coalesce_off = !strcmp(e, "off") || !strcmp(e, "0");
     if (const char *e = getenv("LEANN_STAMP_BUF")) k->stamp_buf = strtoull(e, nullptr, 0);
     return k;
@@ -201,6 +205,7 @@ void leann_internal_free_graph(leann_backend *h) {
     (void)hipFree(h->Wf32);
     for (auto &kv : h->proj_scratch) (void)hipFree(kv.second.first);
     leann_internal_free_removed(h);
+    leann_internal_free_planes(h);
 }
 
 extern "C" void leann_backend_close(leann_backend *h) {
@@ -290,13 +295,29 @@ static int launch_search_NW(const GraphView &g, const SearchArgs &a, hipStream_t
 // Waves per query: 4 for throughput batches (4 workgroups per CU hide each other's dependent hops);
 // 16 for small batches, where the chip is mostly idle and the per-hop row fetch is the critical path —
 // all ~40 new rows of a hop are then in flight at once (results are identical: same order, same sums).
+// Rows in flight per wave of the screen kernels: a hi-plane row is half a row's bytes (768-d: 4, 1 536-d: 2 as for whole rows).
+#ifndef LEANN_SCREEN_R3
+#define LEANN_SCREEN_R3 4
+#endif
+#ifndef LEANN_SCREEN_R6
+#define LEANN_SCREEN_R6 2
+#endif
+// `screen`: the handle's split planes are in place (a.x_hi / a.x_lo): the plain throughput form takes the row-screen kernel.  The
+// latency forms, the filtered and the construction searches read whole rows as before.
 template <int T, int R>
-static int launch_search_T(const GraphView &g, const SearchArgs &a, hipStream_t st) {
+static int launch_search_T(const GraphView &g, const SearchArgs &a, hipStream_t st, bool screen = false) {
     int nw = a.nq <= 384 ? 16 : a.nq <= 640 ? 8 : 4; // 10M x 768, ef = 56: 16 waves win up to 256 queries, 8 at 512, 4 from 768 on (scripts/exp/batch_sweep.py)
     if (const int v = leann_knobs().nw) nw = v;
     if (nw >= 8 && wide_graph(g)) nw = 16; // (no 8-wave wide kernels)
     if (nw >= 16) return launch_search_NW<T, R, 16>(g, a, st);
     if (nw >= 8) return launch_search_NW<T, R, 8>(g, a, st);
+    if constexpr (T == 3 || T == 6) {
+        if (screen && !a.allow && !a.q_rows && !wide_graph(g)) {
+            size_t lds;
+            if (int rc = search_lds_checked(g, a, &lds, 4)) return rc;
+            return launch_one(beam_search_screen_kernel<T, T == 3 ? LEANN_SCREEN_R3 : LEANN_SCREEN_R6>, 256, lds, g, a, st);
+        }
+    }
     return launch_search_NW<T, R, 4>(g, a, st);
 }
 
@@ -375,12 +396,14 @@ int leann_internal_launch_search(leann_backend *h, SearchArgs a, hipStream_t st)
     set_pool_args(h, a);
     const GraphView &g = h->g;
     int T = (int)((g.ld + 255) / 256);
+    const bool screen = h->row_screen.load(std::memory_order_relaxed) != 0 && leann_internal_planes_ready(h) && leann_internal_screen_shape(g);
+    if (screen) { a.x_hi = h->x_hi; a.x_lo = h->x_lo; a.ldp = h->ldp; a.screen_ctr = h->screen_ctr; }
     switch (T) {
         case 1: return launch_search_T<1, 4>(g, a, st);
         case 2: return launch_search_T<2, 4>(g, a, st);
-        case 3: return launch_search_T<3, 4>(g, a, st);
+        case 3: return launch_search_T<3, 4>(g, a, st, screen);
         case 4: return launch_search_T<4, 3>(g, a, st);
-        case 5: case 6: return launch_search_T<6, 2>(g, a, st);
+        case 5: case 6: return launch_search_T<6, 2>(g, a, st, screen);
         case 7: case 8: return launch_search_T<8, 2>(g, a, st);
         case 9: case 10: case 11: case 12: return launch_search_T<12, 1>(g, a, st); // 3 072-d: text-embedding-3-large (embedding/models.rs:113)
         case 13: case 14: case 15: case 16: return launch_search_T<16, 1>(g, a, st);
@@ -1059,6 +1082,7 @@ int leann_internal_from_host(int backend, size_t n, size_t dims, uint32_t M, uin
             return fail("upload of the graph arrays");
     }
     if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize"); // the fills above are null-stream work; searches run on non-blocking streams
+    leann_internal_sync_planes(h);
     *out = h;
     return LEANN_OK;
 }

@@ -691,7 +691,7 @@ static int alloc_graph_arrays(leann_backend *h, uint64_t level_seed) {
 static constexpr uint64_t LEVEL_SEED = 0x5EED0003ull;
 
 static int build_device_impl(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld, size_t graph_degree, size_t complexity,
-                             int device, uint64_t key_offset, int take_copy, leann_backend **out);
+                             int device, uint64_t key_offset, int take_copy, leann_backend **out, bool planes);
 // Lists hold at most 128 ids: HNSW graph_degree M in [2, 64] (level 0 keeps 2 M), DiskANN R in [2, 128].  Checked before any device work.
 static int check_degree(int backend, size_t graph_degree, size_t complexity) {
     const size_t maxdeg = backend == LEANN_BACKEND_HNSW ? 64 : 128;
@@ -702,18 +702,23 @@ static int check_degree(int backend, size_t graph_degree, size_t complexity) {
     }
     return LEANN_OK;
 }
-extern "C" int leann_backend_build_device(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld,
-                                          size_t graph_degree, size_t complexity, int device, uint64_t key_offset,
-                                          int take_copy, leann_backend **out) {
+// `planes`: cut the row screen's split planes (planes.hip) for the new handle — not for one that is only saved and closed again
+static int build_device_guarded(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld, size_t graph_degree, size_t complexity,
+                                int device, uint64_t key_offset, int take_copy, leann_backend **out, bool planes) {
     try { // host-side bookkeeping of the builder allocates (insertion order, level tables): nothing may be thrown across the C ABI
-        return build_device_impl(backend, d_vectors, n, dims, ld, graph_degree, complexity, device, key_offset, take_copy, out);
+        return build_device_impl(backend, d_vectors, n, dims, ld, graph_degree, complexity, device, key_offset, take_copy, out, planes);
     } catch (const std::exception &e) {
         leann_set_error("build: %s", e.what());
         return LEANN_ERR_DEVICE;
     }
 }
+extern "C" int leann_backend_build_device(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld,
+                                          size_t graph_degree, size_t complexity, int device, uint64_t key_offset,
+                                          int take_copy, leann_backend **out) {
+    return build_device_guarded(backend, d_vectors, n, dims, ld, graph_degree, complexity, device, key_offset, take_copy, out, true);
+}
 static int build_device_impl(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld, size_t graph_degree, size_t complexity,
-                             int device, uint64_t key_offset, int take_copy, leann_backend **out) {
+                             int device, uint64_t key_offset, int take_copy, leann_backend **out, bool planes) {
     if (!out || (n && !d_vectors) || dims == 0 || dims > 4096 || ld < dims || (ld & 3) || n >= (1ull << 31)) {
         leann_set_error("leann_backend_build_device: invalid arguments (n=%zu dims=%zu ld=%zu)", n, dims, ld);
         return LEANN_ERR_INVALID;
@@ -761,6 +766,7 @@ static int build_device_impl(int backend, const float *d_vectors, size_t n, size
     int rc = alloc_graph_arrays(h, LEVEL_SEED);
     if (rc == LEANN_OK && n) rc = build_on_device(h, 0, 0);
     if (rc) { leann_backend_close(h); return rc; }
+    if (planes) leann_internal_sync_planes(h);
     *out = h;
     return LEANN_OK;
 }
@@ -795,7 +801,7 @@ extern "C" int leann_backend_build(int backend, const float *vectors, size_t n, 
         }
     }
     leann_backend *h = nullptr;
-    int rc = leann_backend_build_device(backend, dX, n, dims, ld, graph_degree, complexity, 0, 0, 0, &h);
+    int rc = build_device_guarded(backend, dX, n, dims, ld, graph_degree, complexity, 0, 0, 0, &h, false);
     if (rc) { (void)hipFree(dX); return rc; }
     h->owns_rows = true; // dX now belongs to the handle
     rc = leann_backend_save(h, index_path_stem);
@@ -875,7 +881,7 @@ extern "C" int leann_backend_add(int backend, const float *vectors, size_t n, si
         h->g.X = nullptr;
         h->owns_rows = false;
         leann_backend_close(h);
-        rc = leann_backend_build_device(backend, dX, nt, dims, ld, M, efc, 0, 0, 0, &h);
+        rc = build_device_guarded(backend, dX, nt, dims, ld, M, efc, 0, 0, 0, &h, false);
         if (rc) { (void)hipFree(dX); return rc; }
         h->owns_rows = true;
         if (tomb_n) rc = leann_internal_set_removed(h, tomb.data(), tomb_n);

@@ -31,6 +31,9 @@ struct LeannKnobs {
     int hash_bits = 0;      // LEANN_DEBUG_HASH_BITS: force the LDS visited table to 2^bits slots (6..15; 0 = automatic)
     int nw = 0;             // LEANN_DEBUG_NW: waves per query (0 = by batch size)
     int gpool_bits = 0, gpool2_bits = 0; // LEANN_DEBUG_GPOOL_BITS / _GPOOL2_BITS (0 = default sizes)
+    int row_screen = 1;              // LEANN_ROW_SCREEN: what handles made from now on do about the row screen (planes.hip): 0 = off, no
+                                     // split planes (A/B runs); 1 = automatic (default): planes for indexes whose rows outgrow the caches;
+                                     // 2 (LEANN_ROW_SCREEN=1) = planes whatever the size
     bool no_feat256 = false, no_zero_copy = false, no_emit = false, fused_v1 = false, no_list = false, no_tiled = false;
     bool force_remote = false;       // LEANN_DEBUG_FORCE_REMOTE: sharded searches treat EVERY shard as if it sat on another device (staging
                                      // buffers + peer copies, with source = destination device) — exercises that branch on a one-GPU box
@@ -83,7 +86,21 @@ struct leann_backend {
     uint64_t removal_epoch = 0;
     uint32_t two_stage = 1; // Vamana: the RobustPrune form the build used (LEANN_VAMANA_TWO_STAGE when the handle was made)
     std::map<hipStream_t, std::pair<uint8_t *, size_t>> live_scratch; // per stream: live AND the caller's bitmap(s)
+    // Row screen (planes.hip, row_screen.h): the f32 rows a second time as two planes of 16-bit halves, [n x ldp] u16 each, owned by the
+    // handle whoever owns X; planes_src / planes_n / planes_ld name the rows they were cut from.  screen_ctr: device totals
+    // {rows ruled out, rows read in full}.  row_screen: 0 off, 1 automatic, 2 on whatever the size (LeannKnobs::row_screen when the
+    // handle is made; leann_backend_set_row_screen switches between 0 and 2).
+    uint16_t *x_hi = nullptr, *x_lo = nullptr;
+    uint32_t ldp = 0, planes_ld = 0;
+    const float *planes_src = nullptr;
+    uint64_t planes_n = 0;
+    unsigned long long *screen_ctr = nullptr;
+    std::atomic<int> row_screen{leann_knobs().row_screen};
 };
+bool leann_internal_screen_shape(const GraphView &g);      // the row widths and list lengths the screen kernel is compiled for
+void leann_internal_sync_planes(leann_backend *h);          // (re)build the planes of a plain handle; logs and returns on failure
+bool leann_internal_planes_ready(const leann_backend *h);   // planes present and cut from the rows h->g names now
+void leann_internal_free_planes(leann_backend *h);
 // Removals (consolidate.hip).  leann_internal_live_allow: the bitmap a search on `h` has to run under — the caller's (may be null)
 // ANDed with the live mask into the stream's scratch; *out = d_allow unchanged for a handle without removals.  `walk`: the search is
 // the graph walk, which needs no mask of its own once no live list names a removed position.  One caller: leann_internal_search_plain.
@@ -98,6 +115,7 @@ int leann_internal_tombstones_load(leann_backend *h, const std::string &index_fi
 // LEANN_LOG=error|warn|info|debug (default warn) -> stderr, "LEVEL leann_hip: message" (the reference logs through tracing, cli/mod.rs:38-43)
 enum { LEANN_LOG_ERROR = 0, LEANN_LOG_WARN = 1, LEANN_LOG_INFO = 2, LEANN_LOG_DEBUG = 3 };
 void leann_log(int level, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+bool leann_log_enabled(int level); // for callers whose message costs something to gather
 // host-side graph arrays -> device index; exactly one of `vectors` (f32 rows [n x dims]) and `feat_rows` (recompute-on rows
 // [n x row_bytes] + Wf32 [feat_h x dims]) is given.  Validates every array against n before anything is uploaded.
 int leann_internal_from_host(int backend, size_t n, size_t dims, uint32_t M, uint32_t M0, uint32_t max_level, uint32_t entry,

@@ -22,6 +22,7 @@
 //     so ids AND distances are bit-identical to the oracle.
 #pragma once
 #include "common.cuh"
+#include "row_screen.h"
 
 struct GraphView {
     const float *X;            // [n x ld] rows, 16-byte aligned, zero padded
@@ -73,6 +74,12 @@ struct SearchArgs {
     uint32_t gpool2_bits, gpool2_tables;
     const uint8_t *allow;     // filtered kernels only: bitmap over local positions (bit i of byte i >> 3) ...
     uint64_t allow_stride;    // ... of query i at allow + i * allow_stride (0: one bitmap shared by the batch)
+    // Row screen (beam_search_screen_kernel only; row_screen.h): the f32 rows a second time as two planes of 16-bit halves,
+    // [n x ldp] u16 each in rs_plane_pos order, and two running totals {rows ruled out on the hi plane alone, rows read in full}.
+    // Behind every older field, so no other kernel's argument offsets move.
+    const uint16_t *x_hi, *x_lo;
+    uint32_t ldp;
+    unsigned long long *screen_ctr;
 };
 
 // The traversal kernels all take (GraphView g, SearchArgs a) by value.  Two dozen of `a`'s fields are needed only by rare paths (visited
@@ -142,6 +149,83 @@ __device__ __forceinline__ void wave_dist_rows(const float4 (&q)[T], const float
             out[r] = 1.0f - wave_tree_sum(lane4_sum(acc));
         }
     }
+}
+
+// ---- the same rows through the split planes (row_screen.h): hi halves first, lo halves only for rows the bound cannot rule out ----
+// Lane l's halves of chunk t as {e0 | e1 << 16, e2 | e3 << 16}: one 16-byte load per interleaved 512-element block, 8 bytes per
+// chunk of the tail (rs_plane_pos).
+__device__ __forceinline__ uint2 plane_tail_load(const uint16_t *__restrict__ row, uint32_t ldp, int c, int lane) {
+    const uint32_t j = 256u * c + 4u * lane;
+    return j < ldp ? *reinterpret_cast<const uint2 *>(row + j) : make_uint2(0u, 0u);
+}
+template <int T>
+__device__ __forceinline__ void plane_row_load(const uint16_t *__restrict__ row, uint32_t ldp, int lane, uint2 (&h)[T]) {
+#pragma unroll
+    for (int p = 0; p < T / 2; p++) {
+        if (512u * (uint32_t)(p + 1) <= ldp) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(row + 512 * p + 8 * lane);
+            h[2 * p] = make_uint2(v.x, v.y);
+            h[2 * p + 1] = make_uint2(v.z, v.w);
+        } else {
+            h[2 * p] = plane_tail_load(row, ldp, 2 * p, lane);
+            h[2 * p + 1] = plane_tail_load(row, ldp, 2 * p + 1, lane);
+        }
+    }
+    if (T & 1) h[T - 1] = plane_tail_load(row, ldp, T - 1, lane);
+}
+// `armed`: the beam is full and `worst` is the distance of its last entry.  out[r] = the canonical distance, bit for bit, of every row
+// read in full; a lower bound on it, strictly above `worst`, of a row ruled out (bit r of the returned mask).
+template <int T, int R>
+__device__ __forceinline__ uint32_t wave_dist_rows_screen(const float4 (&q)[T], const uint16_t *__restrict__ Xhi, const uint16_t *__restrict__ Xlo,
+                                                          uint32_t ldp, const uint32_t (&ids)[R], int nrows, int lane, bool armed, float worst,
+                                                          float E, float (&out)[R]) {
+    uint2 h[R][T], l[R][T];
+#pragma unroll
+    for (int r = 0; r < R; r++)
+        if (r < nrows) plane_row_load<T>(Xhi + (size_t)ids[r] * ldp, ldp, lane, h[r]);
+    uint32_t ruled = 0;
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        if (r < nrows) {
+            float4 s = make_float4(0.f, 0.f, 0.f, 0.f), a = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int t = 0; t < T; t++) {
+                float4 x;
+                x.x = __uint_as_float(h[r][t].x << 16);
+                x.y = __uint_as_float(h[r][t].x & 0xFFFF0000u);
+                x.z = __uint_as_float(h[r][t].y << 16);
+                x.w = __uint_as_float(h[r][t].y & 0xFFFF0000u);
+                fma4(s, q[t], x);
+                a.x = fmaf(fabsf(q[t].x), fabsf(x.x), a.x);
+                a.y = fmaf(fabsf(q[t].y), fabsf(x.y), a.y);
+                a.z = fmaf(fabsf(q[t].z), fabsf(x.z), a.z);
+                a.w = fmaf(fabsf(q[t].w), fabsf(x.w), a.w);
+            }
+            const float lb = rs_lower_bound(wave_tree_sum(rs_lane_bound(lane4_sum(s), lane4_sum(a))), E);
+            out[r] = lb;
+            if (armed && lb > worst) ruled |= 1u << r; // (false for a NaN on either side)
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++)
+        if (r < nrows && !((ruled >> r) & 1u)) plane_row_load<T>(Xlo + (size_t)ids[r] * ldp, ldp, lane, l[r]);
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        if (r < nrows && !((ruled >> r) & 1u)) {
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int t = 0; t < T; t++) {
+                float4 x;
+                x.x = __uint_as_float((h[r][t].x << 16) | (l[r][t].x & 0xFFFFu));
+                x.y = __uint_as_float((h[r][t].x & 0xFFFF0000u) | (l[r][t].x >> 16));
+                x.z = __uint_as_float((h[r][t].y << 16) | (l[r][t].y & 0xFFFFu));
+                x.w = __uint_as_float((h[r][t].y & 0xFFFF0000u) | (l[r][t].y >> 16));
+                fma4(acc, q[t], x);
+            }
+            out[r] = 1.0f - wave_tree_sum(lane4_sum(acc));
+        }
+    }
+    return ruled;
 }
 
 // Same for bf16 feature rows with the inline norm (recompute-on mode).  Lane l owns elements 256t+4l..+3 again
@@ -250,6 +334,7 @@ struct SearchLds {
     uint32_t *s_new;
     uint32_t *misc;  // [1],[2]=next selection (by hop parity) [3]=table full [4]=pool slot [5]=generation
                      // [6]=1 if the target level's seed is allowed (filtered) [8],[9]=n_new (by hop parity)
+                     // [10]=rows the workgroup's waves ruled out on their hi plane (SCREEN); [7], [11]..[15] free
 };
 // kf = result-list length of a filtered search (0: unfiltered)
 // nbuf = 2 for the latency form of the hop loop (NW > 4: s_key / s_new / s_keyR per hop parity), 1 for the throughput form
@@ -266,12 +351,14 @@ __host__ __device__ inline size_t search_lds_bytes(uint32_t ef, uint32_t maxdeg,
 // LW: adjacency-list ids per lane of wave 0 — 1 for lists of <= 64 ids, 2 for wide graphs (<= 128 ids: lane l holds ids l and 64 + l).
 // Phase B compacts the second half behind the first with a second ballot (the unseen ids keep list order), phase E reduces over both
 // keys of a lane and adds a second rank count; phases C and D already loop over n_new.  LW = 1 compiles to the narrow code unchanged.
-template <int T, int R, int NW, bool FEAT, bool FILT = false, bool G16 = false, int LW = 1>
+// SCREEN (throughput form of the plain f32 search only): phase C goes through the split planes (wave_dist_rows_screen).
+template <int T, int R, int NW, bool FEAT, bool FILT = false, bool G16 = false, int LW = 1, bool SCREEN = false>
 __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_t qi, unsigned char *smem) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const auto *const za = lazy_search_args(); // arguments of the rare paths and of the epilogue: read where they are used
     const uint32_t ef = a.ef;
     static_assert(LW == 1 || LW == 2, "lists of at most 128 ids");
+    static_assert(!SCREEN || (NW == 4 && !FEAT && !FILT && !G16 && LW == 1), "the row screen exists in the plain throughput form only");
     const uint32_t maxdeg = g.M0 > g.M ? g.M0 : g.M;
     const uint32_t efp = (ef + 1) & ~1u;
     SearchLds s;
@@ -318,6 +405,15 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
         }
     }
 
+    float rs_E = 0.f;         // SCREEN: the bound's absolute term (row_screen.h (5))
+    uint32_t rs_ruled = 0;    // SCREEN: rows this wave ruled out on their hi plane
+    if constexpr (SCREEN) {
+        float4 qs = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int t = 0; t < T; t++) { qs.x += fabsf(q[t].x); qs.y += fabsf(q[t].y); qs.z += fabsf(q[t].z); qs.w += fabsf(q[t].w); }
+        rs_E = rs_abs_term(wave_tree_sum(lane4_sum(qs)));
+        if (tid == 0) s.misc[10] = 0; // summed over the waves at exit (the level loop's barriers come before)
+    }
     const uint32_t *const adj0_p = g.adj0, *const adjU_p = g.adjU, *const upoff_p = g.upper_off;
     uint32_t n_evals = 1, hops0 = 0, hopsU = 0; // meaningful in wave 0 / lane 0 only
     uint32_t n_vis = 0;
@@ -507,6 +603,26 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
                                     s.s_key[jj[r]] = key;
                                     if (filt_level) s_keyR[jj[r]] = ((abyte[r] >> (ids[r] & 7u)) & 1u) ? key : ~0ull;
                                 }
+                        }
+                    }
+                } else if constexpr (SCREEN) {
+                    const bool armed = wsize == ef_l; // a full beam: its last entry is the distance to beat
+                    const float worst = orderable_f32(uni((uint32_t)(Wc[wsize - 1] >> 32)));
+                    for (uint32_t j0 = wave; j0 < n_new; j0 += NW * R) {
+                        uint32_t ids[R];
+                        float dd[R];
+                        int nrows = 0;
+    #pragma unroll
+                        for (int r = 0; r < R; r++) {
+                            uint32_t j = j0 + r * NW;
+                            if (j < n_new) { ids[r] = s.s_new[j]; nrows = r + 1; }
+                        }
+                        const uint32_t ruled = wave_dist_rows_screen<T, R>(q, za->x_hi, za->x_lo, za->ldp, ids, nrows, lane, armed, worst, rs_E, dd);
+                        rs_ruled += (uint32_t)__popc(ruled);
+                        if (lane == 0) {
+    #pragma unroll
+                            for (int r = 0; r < R; r++)
+                                if (r < nrows) s.s_key[j0 + r * NW] = make_key(dd[r], ids[r]);
                         }
                     }
                 } else
@@ -996,6 +1112,15 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
     // ---- results ------------------------------------------------------------------------------
     __syncthreads();
     if (hbm && tid == 0) atomicExch(&(hbm == 1 ? za->gpool_lock : za->gpool2_lock)[gslot], 0u); // every probe of this workgroup has returned
+    if constexpr (SCREEN) { // the handle's running totals: rows ruled out / rows read in full (every evaluation but the entry's)
+        if (lane == 0 && rs_ruled) atomicAdd(&s.misc[10], rs_ruled);
+        __syncthreads();
+        if (tid == 0) {
+            const uint32_t ruled = s.misc[10];
+            atomicAdd(&za->screen_ctr[0], (unsigned long long)ruled);
+            atomicAdd(&za->screen_ctr[1], (unsigned long long)(n_evals - 1u - ruled));
+        }
+    }
     if (aborted) { // defensive (see the pool comment): the last table level filled up; empty result + stat 3 -> LEANN_ERR_OVERFLOW
         for (uint32_t t = tid; t < za->k; t += NW * 64) {
             za->out_keys[(size_t)qi * za->k + t] = 0xFFFFFFFFFFFFFFFFull;
@@ -1061,6 +1186,23 @@ __global__ void __launch_bounds__(NW * 64, (NW == 4 && T == 2) ? LEANN_T2_OCC : 
     uint32_t qi = blockIdx.x;
     if (qi >= a.nq) return;
     beam_search_one<T, R, NW, false>(g, a, qi, smem);
+}
+// Throughput form (4 waves per query) of the plain search with the split-plane row screen; api.hip launches it only for a handle
+// whose planes are in place (T = 3 and 6: 768-d and 1 536-d rows).
+// Workgroups per CU the compiler is asked to leave registers for: the hi and lo halves of R rows, the query and two sets of
+// accumulators are live together.
+#ifndef LEANN_SCREEN_OCC3
+#define LEANN_SCREEN_OCC3 4
+#endif
+#ifndef LEANN_SCREEN_OCC6
+#define LEANN_SCREEN_OCC6 3
+#endif
+template <int T, int R>
+__global__ void __launch_bounds__(256, T == 3 ? LEANN_SCREEN_OCC3 : LEANN_SCREEN_OCC6) beam_search_screen_kernel(GraphView g, SearchArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t qi = blockIdx.x;
+    if (qi >= a.nq) return;
+    beam_search_one<T, R, 4, false, false, false, 1, true>(g, a, qi, smem);
 }
 // filtered search (allow-bitmap): answers come from the R list
 template <int T, int R, int NW>

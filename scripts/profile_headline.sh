@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_stats -o $ROUND -- python3 $R/bench.py --headline-only --no-cpu-baseline --no-latency > $out/prof_stats.json 2> $out/prof_stats.log
 for c in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do
   tag=$(echo $c | tr ' ' '_')
-  rocprofv3 --pmc $c --kernel-include-regex "beam_search_kernel" --output-format csv -d $out/prof_$tag -o $ROUND -- python3 $R/bench.py --headline-only --no-cpu-baseline --no-latency --steps 4 --warmup 1 > $out/prof_$tag.json 2> $out/prof_$tag.log || echo "pmc pass $c failed"
+  rocprofv3 --pmc $c --kernel-include-regex "beam_search_(screen_)?kernel" --output-format csv -d $out/prof_$tag -o $ROUND -- python3 $R/bench.py --headline-only --no-cpu-baseline --no-latency --steps 4 --warmup 1 > $out/prof_$tag.json 2> $out/prof_$tag.log || echo "pmc pass $c failed"
 done
 rocprofv3 -L 2>/dev/null | grep -i -E "mall|dram|EA0_RDREQ" | head -40 > $out/counters_mem.txt || true
 # keep what scripts/collect_profiles.py reads (gpurun merges at most 64 MiB back): kernel stats, counter collections, and of the
