@@ -25,7 +25,8 @@ __global__ void __launch_bounds__(256) split_planes_kernel(const float *__restri
     }
 }
 
-// the widths the screen kernel is compiled for (api.hip): T = 3 (513..768 floats) and T = 6 (1 025..1 536), lists of at most 64 ids
+// the widths the screen kernel is compiled for (api.hip): T = 3 (513..768 floats) and T = 6, which also takes T = 5 (1 025..1 536
+// floats in all: at T = 5 the sixth chunk lies past ldp and reads as zeros, search.cuh: plane_tail_load), lists of at most 64 ids
 bool leann_internal_screen_shape(const GraphView &g) {
     const uint32_t T = (g.ld + 255) / 256;
     return g.feat_h == 0 && (T == 3 || T == 5 || T == 6) && std::max(g.M0, g.M) <= 64;

@@ -56,7 +56,9 @@ def _same_as_oracle(a, G, Q, k, ef):
     assert a["stats"]["n_hops_upper"] == int(ost[:, 2].sum())
 
 
-@pytest.fixture(scope="module", params=[768, 1536, 700])
+# 1100: T = 5 in the 6-kernel, plane rows of 1152 (two interleaved blocks + a 128-element tail, the sixth chunk reads as zeros);
+# 1280: T = 5 with the tail chunk exactly full; 520: T = 3, plane rows of 576 (one interleaved block + a 64-element tail)
+@pytest.fixture(scope="module", params=[768, 1536, 700, 1100, 1280, 520])
 def clustered(request, la, po, gpu):
     d = request.param
     X = synth(po, 4000, d, n_clusters=2)  # two clusters: beams fill with one cluster's rows, the other's are ruled out

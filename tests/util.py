@@ -46,3 +46,25 @@ def write_gx1(path, kind, X, M, M0, max_level, entry, levels, upper_off, adj0, a
         f.write(adjU.tobytes())
         f.write(X.tobytes())
     return hd
+
+
+def write_gx2(path, kind, d, M, M0, max_level, entry, levels, upper_off, adj0, adjU, rows, feat_h, W, efc=64, alpha=1.2):
+    """a version-2 LEANNGX1 index file (recompute-on: no vectors) written from numpy arrays: rows = uint8 [n, row_bytes] holding
+    feat_h bf16 features, the f32 norm and padding; W = the encoder weights as f32 [feat_h, d]; returns the header bytes"""
+    import struct
+    rows = np.ascontiguousarray(rows, np.uint8)
+    n, row_bytes = rows.shape
+    W = np.ascontiguousarray(W, np.float32)
+    assert W.shape == (feat_h, d) and row_bytes >= 2 * feat_h + 4 and row_bytes % 8 == 0
+    adjU = np.ascontiguousarray(adjU, np.uint32).reshape(-1, M) if np.size(adjU) else np.zeros((0, M), np.uint32)
+    hd = struct.pack("<8sIIQIIIIIIfIQI60x", b"LEANNGX1", 2, kind, n, d, M, M0, max_level, entry, efc, alpha, feat_h, adjU.shape[0], row_bytes)
+    assert len(hd) == 128
+    with open(path, "wb") as f:
+        f.write(hd)
+        f.write(np.ascontiguousarray(levels, np.uint8).tobytes())
+        f.write(np.ascontiguousarray(upper_off, np.uint32).tobytes())
+        f.write(np.ascontiguousarray(adj0, np.uint32).tobytes())
+        f.write(adjU.tobytes())
+        f.write(rows.tobytes())
+        f.write(W.tobytes())
+    return hd
