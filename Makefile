@@ -11,7 +11,8 @@ HDRS     := $(wildcard $(CSRC)/*.cuh) $(wildcard $(CSRC)/*.h) include/leann_back
 HOST     := leann-rs_amd/host
 CXXFLAGS := -O2 -std=c++17 -ffp-contract=off -Wall -Wextra -Wno-unused-parameter
 
-all: $(CSRC)/libleann_hip.so oracle $(HOST)/leann $(HOST)/host_selftest $(HOST)/host_selftest_asan $(HOST)/serve_bench $(HOST)/row_screen_selftest
+all: $(CSRC)/libleann_hip.so oracle $(HOST)/leann $(HOST)/host_selftest $(HOST)/host_selftest_asan $(HOST)/serve_bench $(HOST)/row_screen_selftest \
+     $(HOST)/encode_plan_selftest
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -40,11 +41,18 @@ $(HOST)/host_selftest_asan: $(HOST)/host_selftest.cpp $(HOST)/leann_host.hpp $(H
 $(HOST)/row_screen_selftest: $(HOST)/row_screen_selftest.cpp $(CSRC)/row_screen.h
 	g++ $(CXXFLAGS) -o $@ $(HOST)/row_screen_selftest.cpp -lm
 
+# the column-block plan of the recompute encode kernels (csrc/encode_plan.h) for every dims in 1..4096, on the CPU under
+# AddressSanitizer + UBSan: no GPU, no library
+$(HOST)/encode_plan_selftest: $(HOST)/encode_plan_selftest.cpp $(CSRC)/encode_plan.h
+	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -o $@ \
+	    $(HOST)/encode_plan_selftest.cpp
+
 oracle:
 	$(MAKE) -s -C oracle
 
 clean:
-	rm -f $(CSRC)/*.o $(CSRC)/*.so $(HOST)/leann $(HOST)/host_selftest $(HOST)/host_selftest_asan $(HOST)/serve_bench $(HOST)/row_screen_selftest
+	rm -f $(CSRC)/*.o $(CSRC)/*.so $(HOST)/leann $(HOST)/host_selftest $(HOST)/host_selftest_asan $(HOST)/serve_bench $(HOST)/row_screen_selftest \
+	      $(HOST)/encode_plan_selftest
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

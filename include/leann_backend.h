@@ -269,7 +269,14 @@ int leann_scan_topk_device(const float *d_rows, size_t n, size_t dims, size_t ld
  * tail of src/embedding/candle.rs:165,218-225) resident on the device:
  *     features [n x h] bf16 (borrowed), weights [h x dims] bf16 (copied, re-tiled),
  *     embedding_i = l2_normalize(W^T f_i)  (bf16 MFMA, f32 accumulate)
- * scores = raw dot product, descending, ties -> lower position; allow_mask = early filter (:66-71). */
+ * scores = raw dot product, descending, ties -> lower position; allow_mask = early filter (:66-71).
+ * dims in [1, 4096] (the limit of the stored-vector search); dims > 4096 -> LEANN_ERR_INVALID before any device work.  Up to 768
+ * columns one workgroup tile holds a whole embedding; wider ones are encoded in column blocks — same arithmetic per
+ * column, sums of squares added block after block in a fixed order.  The limit on h depends on the block width: the feature tile
+ * [128 x h] and a ring of three slabs one block wide must fit the 160 KiB of LDS, else LEANN_ERR_INVALID.  dims <= 768 keep their one
+ * block of ceil(dims / 128) tiles (h <= 496 at dims <= 128, falling to h <= 256 at dims = 641..768, as before); dims > 768 take
+ * narrower blocks when the widest does not fit, so h <= 496 at any such width.  Everything built on a handle — the pooled / host / sharded forms,
+ * leann_recompute_encode_device, leann_recompute_search_batch*, leann_recompute_build_index — takes the same widths. */
 typedef struct leann_recompute leann_recompute;
 int leann_recompute_create(const uint16_t *d_features, size_t n, size_t h, const uint16_t *d_weights,
                            size_t dims, int device, uint64_t key_offset, leann_recompute **out);

@@ -409,6 +409,8 @@ __global__ void __launch_bounds__(512) encode_kernel(const uint16_t *__restrict_
     }
 }
 
+#include "recompute_blocked.cuh" // encode_blocked_kernel: the same k-loop over column blocks, for dims > 768
+
 // ------------------------------------------------------------------------------------------------
 struct leann_recompute {
     int device = 0;
@@ -417,7 +419,9 @@ struct leann_recompute {
     uint16_t *Wraw = nullptr;    // owned copy [h x d] (query projection)
     size_t n = 0, h = 0, hp = 0, d = 0, dp = 0, ld = 0;
     uint64_t key_offset = 0;
-    int ct = 0;
+    int ct = 0;                     // dims <= 768: column tiles of the one block (encode_kernel<ct, ..>)
+    EncodeBlocks blocks = {};       // dims > 768: the column blocks of encode_blocked_kernel (encode_plan.h)
+    int ctb_max = 0;                // ... and the widest of them, which sizes the LDS ring
     uint32_t L = 1;                 // token rows per passage (masked mean pooling), 1 | 2 | 4 | 8
     const uint8_t *mask = nullptr;  // borrowed [n x L] attention mask or null (all ones)
     float last_ms[3] = {0, 0, 0}; // encode, score, top-k of the last search call (HIP events)
@@ -455,8 +459,6 @@ static int grow_scratch(void **p, size_t *cap, size_t bytes) {
     *cap = bytes;
     return LEANN_OK;
 }
-
-static size_t encode_lds_bytes(size_t hp, size_t dp, bool fused = false) { return 128 * (hp + 8) * 2 + 3 * (dp + (fused ? 192 : 0)) * 16 * 2 + 6 * 128 * 4; }
 
 // the feature-stationary fused kernel serves the common shape (one token row per passage, h = 256, dims a multiple of 128);
 // LEANN_DEBUG_FUSED_V1 forces the general kernel (tests compare the two)
@@ -496,12 +498,31 @@ static int launch_encode(const leann_recompute *r, uint64_t row0, uint64_t rows,
         HIP_CHECK_RET(hipGetLastError());
         return LEANN_OK;
     }
-    const size_t lds = encode_lds_bytes(r->hp, r->dp, fused);
     // row0 / rows count PASSAGES; the kernel works on token rows (L per passage, tiles of 128 token rows)
     const uint64_t tok0 = row0 * r->L, toks = rows * r->L;
     const unsigned grid = (unsigned)((toks + 127) / 128);
     const uint16_t *F = r->F + tok0 * r->h;
     const uint8_t *mk = r->mask ? r->mask + tok0 : nullptr;
+    if (r->blocks.n) { // dims > 768: column blocks, the LDS ring sized by the widest one
+        const size_t ldsb = encode_lds_bytes(r->hp, (size_t)r->ctb_max * 128, fused);
+        const bool pool = r->L > 1 || r->mask != nullptr;
+#define LAUNCH_BLOCKED(FU, PO)                                                                                                  \
+    do {                                                                                                                        \
+        HIP_CHECK_RET(hipFuncSetAttribute((const void *)encode_blocked_kernel<FU, PO>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
+                                          160 * 1024));                                                                         \
+        hipLaunchKernelGGL((encode_blocked_kernel<FU, PO>), dim3(grid), dim3(512), ldsb, st, F, (uint64_t)toks, (uint32_t)r->h,     \
+                           (uint32_t)r->hp, r->Wp, (uint32_t)r->d, (uint32_t)r->dp, (uint32_t)r->ld, E, Gp, nq, S, (uint32_t)rows,  \
+                           r->L, mk, norms, r->blocks);                                                                         \
+    } while (0)
+        if (fused && pool) LAUNCH_BLOCKED(true, true);
+        else if (fused) LAUNCH_BLOCKED(true, false);
+        else if (pool) LAUNCH_BLOCKED(false, true);
+        else LAUNCH_BLOCKED(false, false);
+#undef LAUNCH_BLOCKED
+        HIP_CHECK_RET(hipGetLastError());
+        return LEANN_OK;
+    }
+    const size_t lds = encode_lds_bytes(r->hp, r->dp, fused);
 #define LAUNCH_ONE(CT, FU, PO)                                                                                            \
     do {                                                                                                                  \
         HIP_CHECK_RET(hipFuncSetAttribute((const void *)encode_kernel<CT, FU, PO>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
@@ -533,8 +554,8 @@ static int launch_encode(const leann_recompute *r, uint64_t row0, uint64_t rows,
 
 extern "C" int leann_recompute_create(const uint16_t *d_features, size_t n, size_t h, const uint16_t *d_weights, size_t dims,
                                       int device, uint64_t key_offset, leann_recompute **out) {
-    if (!out || (n && !d_features) || !d_weights || h == 0 || dims == 0 || dims > 768 || n >= (1ull << 32)) {
-        leann_set_error("leann_recompute_create: invalid arguments (n=%zu h=%zu dims=%zu; dims <= 768)", n, h, dims);
+    if (!out || (n && !d_features) || !d_weights || h == 0 || dims == 0 || dims > LEANN_ENCODE_MAX_DIMS || n >= (1ull << 32)) {
+        leann_set_error("leann_recompute_create: invalid arguments (n=%zu h=%zu dims=%zu; dims <= %d)", n, h, dims, LEANN_ENCODE_MAX_DIMS);
         return LEANN_ERR_INVALID;
     }
     int ndev = 0;
@@ -544,6 +565,12 @@ extern "C" int leann_recompute_create(const uint16_t *d_features, size_t n, size
         return LEANN_ERR_DEVICE;
     }
     HIP_CHECK_RET(hipSetDevice(device));
+    // columns -> blocks of compiled widths (encode_plan.h); the LDS check is on the widest BLOCK, not on dp
+    const EncodePlan plan = encode_plan(h, dims);
+    if (!plan.ok) {
+        leann_set_error("recompute: feature width %zu x dims %zu exceeds the 160 KiB LDS tile", h, dims);
+        return LEANN_ERR_INVALID;
+    }
     leann_recompute *r = new leann_recompute();
     r->device = device;
     r->F = d_features;
@@ -552,16 +579,14 @@ extern "C" int leann_recompute_create(const uint16_t *d_features, size_t n, size
     r->hp = (h + 15) / 16 * 16;
     r->d = dims;
     r->ld = (dims + 3) & ~(size_t)3;
-    int ct = (int)((dims + 127) / 128);
-    if (ct == 5) ct = 6;
-    r->ct = ct;
-    r->dp = (size_t)ct * 128;
-    r->key_offset = key_offset;
-    if (encode_lds_bytes(r->hp, r->dp, true) > 160 * 1024) {
-        delete r;
-        leann_set_error("recompute: feature width %zu x dims %zu exceeds the 160 KiB LDS tile", h, dims);
-        return LEANN_ERR_INVALID;
+    r->dp = plan.dp;
+    r->ctb_max = plan.ctb_max;
+    if (plan.nblk == 1) r->ct = plan.ctb[0];
+    else {
+        r->blocks.n = (uint32_t)plan.nblk;
+        for (int b = 0; b < plan.nblk; b++) r->blocks.set((uint32_t)b, (uint32_t)plan.ctb[b]);
     }
+    r->key_offset = key_offset;
     HIP_CHECK_RET(hipMalloc((void **)&r->Wp, r->hp * r->dp * 2));
     HIP_CHECK_RET(hipMalloc((void **)&r->Wraw, h * dims * 2));
     HIP_CHECK_RET(hipMemcpy(r->Wraw, d_weights, h * dims * 2, hipMemcpyDeviceToDevice));
@@ -593,6 +618,10 @@ extern "C" int leann_recompute_create_host(const uint16_t *features, size_t n, s
                                            int device, uint64_t key_offset, leann_recompute **out) {
     if (!out || (n && !features) || !weights || h == 0 || dims == 0) {
         leann_set_error("leann_recompute_create_host: null/zero argument");
+        return LEANN_ERR_INVALID;
+    }
+    if (dims > LEANN_ENCODE_MAX_DIMS) { // before any device work, as leann_recompute_create
+        leann_set_error("leann_recompute_create_host: invalid arguments (dims=%zu; dims <= %d)", dims, LEANN_ENCODE_MAX_DIMS);
         return LEANN_ERR_INVALID;
     }
     int ndev = 0;
