@@ -245,8 +245,53 @@ int leann_backend_search_filtered_exact_batch_device(const leann_backend *h, con
                                                      size_t nq, size_t top_k, const uint8_t *d_allow,
                                                      size_t allow_stride, uint64_t *d_keys, float *d_dists,
                                                      uint32_t *d_counts, void *stream);
-/* device pointer of the rows (for ground-truth scans) */
+/* device pointer of the rows (for ground-truth scans); NULL for a composite handle and for a handle without f32 rows (bf16 rows) */
 const float *leann_backend_device_rows(const leann_backend *h);
+
+/* ---- row types (additive; DESIGN.md "bf16 rows") ----------------------------------------------------------------------------------
+ * The rows of a stored-vector index are f32 (the default everywhere, and exactly the code paths of before) or bf16, chosen when the
+ * index is made.  With r(x) = f32 -> bf16, round to nearest even (a NaN stays a NaN), and w(b) = b << 16 the exact widening:
+ *     a bf16 index over rows X IS the f32 index over w(r(X)) with the same graph —
+ * every search returns, bit for bit (keys, f32 distance bits, counts, the four per-query stats), what the f32 kernels return on a
+ * leann_backend_from_arrays handle made from the same graph arrays and the rows w(r(X)).  Half the device memory, half the index file
+ * (LEANNGX1 version 3: the header and graph arrays of version 1, then bf16 rows [n x dims]; leann_backend_open detects it), half
+ * the row traffic per evaluation (leann_search_stats.algorithmic_bytes counts dims * 2).
+ * On a bf16 handle: leann_backend_graph_export with vectors != NULL writes w(rows); leann_backend_device_rows returns NULL; removal
+ * (leann_backend_remove, live_len, removed_bitmap, the tombstone sidecar) works; filter mode 2 picks the walk.
+ * LEANN_ERR_UNSUPPORTED with a message naming the way out: exact filtered search and filter mode 1 (use the walk), leann_backend_
+ * consolidate (removals stay tombstones), leann_backend_add and leann_backend_remove_from_index (rebuild; or remove + save),
+ * leann_backend_set_row_screen (no f32 planes exist), leann_backend_open with a device list on a version-3 file (build the shards
+ * and use leann_sharded_from_handles: bf16 shards work, mixing row types -> LEANN_ERR_INVALID).
+ * An unknown row_type -> LEANN_ERR_INVALID before any device work. */
+enum { LEANN_ROWS_F32 = 0, LEANN_ROWS_BF16 = 1, LEANN_ROWS_FEATURES = 2 /* recompute-on: no vectors */ };
+/* the handle's row type (a composite handle: its shards' common type); -1 for NULL */
+int leann_backend_row_type(const leann_backend *h);
+/* host helper, no device: out[i] = r(in[i]) */
+int leann_round_bf16(const float *in, size_t n, uint16_t *out);
+/* leann_backend_build / _build_device / _from_arrays with a row type; LEANN_ROWS_F32 is the existing call, bit for bit.
+ * LEANN_ROWS_BF16: the rows are rounded first and the graph is built by the same builder on w(r(X)), so the index is reproducible
+ * from its file alone.  build_device_rows: may_overwrite != 0 lets the library overwrite d_vectors with w(r(X)) and build on them
+ * in place; 0 takes a transient f32 copy, freed after the build, and the caller's rows come back untouched.  Either way the handle
+ * owns its bf16 rows and keeps no f32 rows (d_vectors need not outlive the call); peak device memory is f32 + bf16 rows
+ * (the f32 rows being the caller's with may_overwrite, else the library's transient copy beside them; the build cuts no row-screen
+ * planes for rows it is about to drop).  The host-pointer build uploads its own copy and builds in place. */
+int leann_backend_build_rows(int backend, const float *vectors, size_t n, size_t dims, size_t graph_degree,
+                             size_t complexity, int row_type, const char *index_path_stem);
+int leann_backend_build_device_rows(int backend, float *d_vectors, size_t n, size_t dims, size_t ld, size_t graph_degree,
+                                    size_t complexity, int device, uint64_t key_offset, int row_type, int may_overwrite,
+                                    leann_backend **out);
+int leann_backend_from_arrays_rows(int backend, const float *vectors, size_t n, size_t dims,
+                                   uint32_t M, uint32_t M0, uint32_t max_level, uint32_t entry,
+                                   const uint8_t *levels, const uint32_t *upper_off,
+                                   const uint32_t *adj0, const uint32_t *adjU, size_t n_upper_lists,
+                                   int device, uint64_t key_offset, int row_type, leann_backend **out);
+/* A new handle with the SAME graph (copied) and the rows of `h` in another type: today F32 -> BF16 only — the migration path of an
+ * existing f32 index (the graph stays the one built on the exact rows; the definition above holds for the result).  `h` is left as
+ * it is.  LEANN_ERR_UNSUPPORTED for a composite handle (convert the shards, then leann_sharded_from_handles), a recompute-on handle
+ * and BF16 -> F32.  Removals of `h` are carried over. */
+int leann_backend_to_rows(const leann_backend *h, int row_type, leann_backend **out);
+/* the rows of a bf16 handle as stored, in element order; LEANN_ERR_UNSUPPORTED for any other handle */
+int leann_backend_rows_export_bf16(const leann_backend *h, uint16_t *out /* [n x dims] */);
 
 /* Deterministic synthetic rows written straight into HBM; bit-identical to
  * oracle/oracle.c:orc_gen_rows. */

@@ -65,6 +65,28 @@ extern "C" {
     #[allow(dead_code)]
     fn leann_backend_removed_bitmap(h: *const LeannBackend, out: *mut u8, n_pending: *mut usize) -> c_int;
     fn leann_backend_remove_from_index(backend: c_int, keys: *const u64, n: usize, dims: usize, stem: *const c_char) -> c_int;
+    // row types (additive): 0 = f32 (the default: the calls above), 1 = bf16 rows — half the device memory and index file; a bf16
+    // index answers bit for bit like the f32 index over the rounded rows.  leann_backend_open detects the type from the file.
+    #[allow(dead_code)]
+    fn leann_backend_row_type(h: *const LeannBackend) -> c_int;
+    #[allow(dead_code)]
+    fn leann_round_bf16(input: *const f32, n: usize, out: *mut u16) -> c_int;
+    #[allow(dead_code)]
+    fn leann_backend_build_rows(backend: c_int, vectors: *const f32, n: usize, dims: usize, graph_degree: usize,
+                                complexity: usize, row_type: c_int, stem: *const c_char) -> c_int;
+    #[allow(dead_code)]
+    fn leann_backend_build_device_rows(backend: c_int, d_vectors: *mut f32, n: usize, dims: usize, ld: usize, graph_degree: usize,
+                                       complexity: usize, device: c_int, key_offset: u64, row_type: c_int, may_overwrite: c_int,
+                                       out: *mut *mut LeannBackend) -> c_int;
+    #[allow(dead_code)]
+    fn leann_backend_from_arrays_rows(backend: c_int, vectors: *const f32, n: usize, dims: usize, m: u32, m0: u32, max_level: u32,
+                                      entry: u32, levels: *const u8, upper_off: *const u32, adj0: *const u32, adj_u: *const u32,
+                                      n_upper_lists: usize, device: c_int, key_offset: u64, row_type: c_int,
+                                      out: *mut *mut LeannBackend) -> c_int;
+    #[allow(dead_code)]
+    fn leann_backend_to_rows(h: *const LeannBackend, row_type: c_int, out: *mut *mut LeannBackend) -> c_int;
+    #[allow(dead_code)]
+    fn leann_backend_rows_export_bf16(h: *const LeannBackend, out: *mut u16) -> c_int;
 }
 
 fn last_error() -> anyhow::Error {

@@ -74,6 +74,16 @@ SIGNATURES = {
     "leann_backend_from_arrays": (C.c_int, [C.c_int, f32p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32,
                                            C.c_uint32, C.c_uint32, u8p, u32p, u32p, u32p, C.c_size_t,
                                            C.c_int, C.c_uint64, C.POINTER(vp)]),
+    "leann_backend_row_type": (C.c_int, [vp]),
+    "leann_round_bf16": (C.c_int, [f32p, C.c_size_t, C.POINTER(C.c_uint16)]),
+    "leann_backend_build_rows": (C.c_int, [C.c_int, f32p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_char_p]),
+    "leann_backend_build_device_rows": (C.c_int, [C.c_int, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                 C.c_size_t, C.c_int, C.c_uint64, C.c_int, C.c_int, C.POINTER(vp)]),
+    "leann_backend_from_arrays_rows": (C.c_int, [C.c_int, f32p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32,
+                                                C.c_uint32, C.c_uint32, u8p, u32p, u32p, u32p, C.c_size_t,
+                                                C.c_int, C.c_uint64, C.c_int, C.POINTER(vp)]),
+    "leann_backend_to_rows": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
+    "leann_backend_rows_export_bf16": (C.c_int, [vp, C.POINTER(C.c_uint16)]),
     "leann_backend_graph_info": (C.c_int, [vp, u64p]),
     "leann_backend_graph_export": (C.c_int, [vp, u8p, u32p, u32p, u32p, f32p]),
     "leann_backend_save": (C.c_int, [vp, C.c_char_p]),

@@ -29,6 +29,21 @@ class BackendType(enum.IntEnum):
         return BackendSearcher.load(self, index_path, dimensions, device)
 
 
+class RowType(enum.IntEnum):
+    """what the rows of a stored-vector index are (include/leann_backend.h "row types"); Features: a recompute-on index, no vectors"""
+    F32 = 0
+    BF16 = 1
+    Features = 2
+
+
+def round_bf16(x):
+    """f32 -> bf16 bits (uint16), round to nearest even, NaN stays NaN: the library's own rounding, on the host"""
+    x = np.ascontiguousarray(x, np.float32)
+    out = np.zeros(x.shape, np.uint16)
+    N.check(N.lib().leann_round_bf16(_p(x, f32p), x.size, out.ctypes.data_as(C.POINTER(C.c_uint16))))
+    return out
+
+
 def _p(a, t):
     return a.ctypes.data_as(t) if a is not None else None
 
@@ -52,7 +67,7 @@ class BackendSearcher:
 
     @classmethod
     def from_arrays(cls, backend_type, vectors, M, M0, max_level, entry, levels, upper_off, adj0, adjU,
-                    device=0, key_offset=0):
+                    device=0, key_offset=0, row_type=RowType.F32):
         vectors = np.ascontiguousarray(vectors, np.float32)
         levels = np.ascontiguousarray(levels, np.uint8)
         upper_off = np.ascontiguousarray(upper_off, np.uint32)
@@ -61,6 +76,12 @@ class BackendSearcher:
         nul = adjU.size // M if adjU.size else 0
         h = C.c_void_p()
         n, d = vectors.shape
+        if int(row_type) != RowType.F32:  # the rows are rounded on the device: the index is the f32 index over the rounded rows
+            N.check(N.lib().leann_backend_from_arrays_rows(
+                int(backend_type), _p(vectors, f32p), n, d, M, M0, max_level, entry, _p(levels, u8p),
+                _p(upper_off, u32p), _p(adj0, u32p), _p(adjU, u32p) if nul else None, nul, device,
+                key_offset, int(row_type), C.byref(h)))
+            return cls(h, backend_type)
         N.check(N.lib().leann_backend_from_arrays(
             int(backend_type), _p(vectors, f32p), n, d, M, M0, max_level, entry, _p(levels, u8p),
             _p(upper_off, u32p), _p(adj0, u32p), _p(adjU, u32p) if nul else None, nul, device,
@@ -69,9 +90,14 @@ class BackendSearcher:
 
     @classmethod
     def build_device(cls, backend_type, d_vectors_ptr, n, dims, ld, graph_degree, complexity, device=0,
-                     key_offset=0, take_copy=False):
-        """Index straight from rows already in HBM (additive API)."""
+                     key_offset=0, take_copy=False, row_type=RowType.F32, may_overwrite=False):
+        """Index straight from rows already in HBM (additive API).  row_type=RowType.BF16: the rows are rounded, the graph is built on
+        the rounded rows and the handle keeps bf16 rows only; may_overwrite lets the rounding happen in the caller's buffer."""
         h = C.c_void_p()
+        if int(row_type) != RowType.F32:
+            N.check(N.lib().leann_backend_build_device_rows(int(backend_type), d_vectors_ptr, n, dims, ld, graph_degree, complexity,
+                                                            device, key_offset, int(row_type), 1 if may_overwrite else 0, C.byref(h)))
+            return cls(h, backend_type)
         N.check(N.lib().leann_backend_build_device(int(backend_type), d_vectors_ptr, n, dims, ld,
                                                    graph_degree, complexity, device, key_offset,
                                                    1 if take_copy else 0, C.byref(h)))
@@ -279,6 +305,21 @@ class BackendSearcher:
         s._borrowed = True
         return s
 
+    def row_type(self):
+        return RowType(N.lib().leann_backend_row_type(self._h))
+
+    def to_rows(self, row_type):
+        """a new searcher with the same graph and this one's rows in another type (f32 -> bf16)"""
+        h = C.c_void_p()
+        N.check(N.lib().leann_backend_to_rows(self._h, int(row_type), C.byref(h)))
+        return BackendSearcher(h, self.backend_type)
+
+    def export_rows_bf16(self):
+        """the rows of a bf16 index as stored: [n x dims] uint16"""
+        out = np.zeros((self.len(), self.dims()), np.uint16)
+        N.check(N.lib().leann_backend_rows_export_bf16(self._h, out.ctypes.data_as(C.POINTER(C.c_uint16))))
+        return out
+
     def device_rows_ptr(self):
         return N.lib().leann_backend_device_rows(self._h)
 
@@ -320,11 +361,15 @@ class BackendBuilder:
     def __init__(self, backend_type):
         self.backend_type = BackendType(backend_type)
 
-    def build(self, embeddings, ids, index_path, dimensions, graph_degree, complexity):
+    def build(self, embeddings, ids, index_path, dimensions, graph_degree, complexity, row_type=RowType.F32):
         """mod.rs:55-79 -> hnsw.rs:96-139 / diskann.rs:70-105.  `ids` is unused, as in the reference."""
         X = np.ascontiguousarray(embeddings, np.float32)
         if X.ndim != 2 or X.shape[1] != dimensions:
             raise LeannError(1, f"embeddings must be [n x {dimensions}]")
+        if int(row_type) != RowType.F32:
+            N.check(N.lib().leann_backend_build_rows(int(self.backend_type), _p(X, f32p), X.shape[0], dimensions,
+                                                     graph_degree, complexity, int(row_type), os.fsencode(str(index_path))))
+            return
         N.check(N.lib().leann_backend_build(int(self.backend_type), _p(X, f32p), X.shape[0], dimensions,
                                             graph_degree, complexity, os.fsencode(str(index_path))))
 

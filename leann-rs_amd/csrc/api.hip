@@ -220,7 +220,7 @@ extern "C" void leann_backend_close(leann_backend *h) {
 }
 extern "C" size_t leann_backend_len(const leann_backend *h) { return h ? (size_t)h->g.n : 0; }
 extern "C" size_t leann_backend_dims(const leann_backend *h) { return h ? (size_t)h->g.d : 0; }
-extern "C" const float *leann_backend_device_rows(const leann_backend *h) { return h && !h->sharded ? h->g.X : nullptr; }
+extern "C" const float *leann_backend_device_rows(const leann_backend *h) { return h && !h->sharded && !leann_internal_bf16(h) ? h->g.X : nullptr; }
 #define NOT_ON_SHARDED(h, what)                                                                                                    \
     do {                                                                                                                           \
         if ((h) && (h)->sharded) {                                                                                                 \
@@ -394,6 +394,7 @@ int leann_internal_launch_search(leann_backend *h, SearchArgs a, hipStream_t st)
     int rc = ensure_gpool(h);
     if (rc) return rc;
     set_pool_args(h, a);
+    if (leann_internal_bf16(h)) return leann_internal_launch_search_bf16(h->g, a, st); // kernels and launcher of their own (search_bf16.hip)
     const GraphView &g = h->g;
     int T = (int)((g.ld + 255) / 256);
     const bool screen = h->row_screen.load(std::memory_order_relaxed) != 0 && leann_internal_planes_ready(h) && leann_internal_screen_shape(g);
@@ -428,6 +429,10 @@ int leann_internal_search_plain(leann_backend *h, const float *d_queries, size_t
     if (nq == 0) return LEANN_OK;
     if (f.exact && h->g.feat_h) {
         leann_set_error("exact filtered search needs stored vectors; this index recomputes them from features (use leann_recompute_search_batch_device with an allow mask)");
+        return LEANN_ERR_UNSUPPORTED;
+    }
+    if (f.exact && leann_internal_bf16(h)) {
+        leann_set_error("exact filtered search scans f32 rows; this index stores bf16 rows (use the filtered walk: mode 0, or mode 2 which picks it)");
         return LEANN_ERR_UNSUPPORTED;
     }
     if (h->g.n == 0) {
@@ -630,7 +635,8 @@ static int search_filtered_batch_host_impl(const leann_backend *hc, const float 
     // exact scan of the allowed rows, or the walk with the filter inside?  FILTER_AUTO (registered filters only: the count is known):
     // exact up to 5 % of the rows / 64k rows for small batches, 1.5 % for large ones, when the index stores vectors
     bool exact = mode == FILTER_EXACT;
-    const bool stored_vectors = hc && !(hc->sharded ? leann_internal_sharded_shard(hc->sharded, 0)->g.feat_h : hc->g.feat_h);
+    const leann_backend *first = hc && hc->sharded ? leann_internal_sharded_shard(hc->sharded, 0) : hc;
+    const bool stored_vectors = first && !first->g.feat_h && !leann_internal_bf16(first); // f32 rows an exact scan can read
     if (mode == FILTER_AUTO && flt && hc && stored_vectors && top_k <= 1024) {
         const double frac = nq <= 64 ? 0.05 : 0.015;
         exact = flt->n_allowed <= std::max<size_t>((size_t)(frac * (double)hc->g.n), nq <= 64 ? 65536 : 0);
@@ -741,13 +747,14 @@ static int search_filtered_batch_host_impl(const leann_backend *hc, const float 
     {
         std::lock_guard<std::mutex> lk(h->mu);
         const GraphView &gv = h->sharded ? leann_internal_sharded_shard(h->sharded, 0)->g : h->g; // (shards share one configuration)
+        const size_t elem_bytes = leann_internal_bf16(h->sharded ? leann_internal_sharded_shard(h->sharded, 0) : h) ? 2 : 4;
         for (size_t i = 0; i < ns * nq; i++) {
             h->stats.n_dist_evals += hstats[i * 4 + 0];
             h->stats.n_hops_base += hstats[i * 4 + 1];
             h->stats.n_hops_upper += hstats[i * 4 + 2];
             h->stats.n_table_overflow += hstats[i * 4 + 3] ? 1 : 0;
             n_lost += hstats[i * 4 + 3] == 3;
-            h->stats.algorithmic_bytes += (uint64_t)hstats[i * 4 + 0] * (gv.feat_h ? (gv.norms ? 2 * (size_t)gv.feat_h + 4 : (size_t)gv.row_bytes) : d * 4) + (uint64_t)hstats[i * 4 + 1] * gv.M0 * 4 +
+            h->stats.algorithmic_bytes += (uint64_t)hstats[i * 4 + 0] * (gv.feat_h ? (gv.norms ? 2 * (size_t)gv.feat_h + 4 : (size_t)gv.row_bytes) : d * elem_bytes) + (uint64_t)hstats[i * 4 + 1] * gv.M0 * 4 +
                                           (uint64_t)hstats[i * 4 + 2] * gv.M * 4;
         }
         h->stats.n_queries += nq;
@@ -998,9 +1005,19 @@ static const char *validate_graph(size_t n, uint32_t M, uint32_t M0, uint32_t ma
 int leann_internal_from_host(int backend, size_t n, size_t dims, uint32_t M, uint32_t M0, uint32_t max_level, uint32_t entry,
                              const uint8_t *levels, const uint32_t *upper_off, const uint32_t *adj0, const uint32_t *adjU,
                              size_t n_upper_lists, const float *vectors, const unsigned char *feat_rows, uint32_t feat_h, uint32_t row_bytes,
-                             const float *Wf32, int device, uint64_t key_offset, leann_backend **out) {
-    const bool feat = feat_rows != nullptr;
-    if (!out || dims == 0 || dims > 4096 || n >= (1ull << 31) || (n && ((!vectors && !feat) || !adj0 || !upper_off)) ||
+                             const float *Wf32, int device, uint64_t key_offset, leann_backend **out, int row_type, const uint16_t *bf16_rows,
+                             const float *d_f32_rows, size_t d_f32_ld) {
+    const bool feat = feat_rows != nullptr, bf16 = row_type == LEANN_ROWS_BF16;
+    if (row_type != LEANN_ROWS_F32 && row_type != LEANN_ROWS_BF16) {
+        leann_set_error("leann_backend_from_arrays: unknown row type %d (LEANN_ROWS_F32 or LEANN_ROWS_BF16)", row_type);
+        return LEANN_ERR_INVALID;
+    }
+    if ((bf16 && (feat || (vectors != nullptr) + (bf16_rows != nullptr) + (d_f32_rows != nullptr) > 1 || (d_f32_rows && d_f32_ld < dims))) ||
+        (!bf16 && (bf16_rows || d_f32_rows))) {
+        leann_set_error("leann_backend_from_arrays: invalid arguments");
+        return LEANN_ERR_INVALID;
+    }
+    if (!out || dims == 0 || dims > 4096 || n >= (1ull << 31) || (n && ((!vectors && !feat && !bf16_rows && !d_f32_rows) || !adj0 || !upper_off)) ||
         (backend != LEANN_BACKEND_HNSW && backend != LEANN_BACKEND_DISKANN) ||
         (feat && (!Wf32 || feat_h == 0 || (feat_h & 3) || feat_h > 1024 || row_bytes < 2 * feat_h + 4 || (row_bytes & 7)))) {
         leann_set_error("leann_backend_from_arrays: invalid arguments");
@@ -1062,6 +1079,9 @@ int leann_internal_from_host(int backend, size_t n, size_t dims, uint32_t M, uin
         }
         if (hipMalloc((void **)&h->Wf32, (size_t)feat_h * dims * 4) != hipSuccess) return fail("hipMalloc(weights)");
         if (hipMemcpy(h->Wf32, Wf32, (size_t)feat_h * dims * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("upload of the weights");
+    } else if (bf16) {
+        const int rc = d_f32_rows ? leann_internal_bf16_adopt_device(h, d_f32_rows, d_f32_ld) : leann_internal_bf16_adopt_host(h, vectors, bf16_rows);
+        if (rc) { leann_backend_close(h); return rc; }
     } else {
         if (hipMalloc((void **)&h->g.X, std::max<size_t>(n * ld, 4) * 4) != hipSuccess) return fail("hipMalloc(rows)");
         if (n) {
@@ -1134,6 +1154,26 @@ extern "C" int leann_backend_graph_export(const leann_backend *h, uint8_t *level
     if (adjU && h->n_upper_lists)
         HIP_CHECK_RET(hipMemcpy(adjU, h->g.adjU, h->n_upper_lists * h->g.M * 4, hipMemcpyDeviceToHost));
     if (vectors && h->g.feat_h) { leann_set_error("graph_export: a recompute-on index holds no vectors"); return LEANN_ERR_UNSUPPORTED; }
+    if (vectors && leann_internal_bf16(h)) {
+        // w(rows): exact.  The bf16 rows land in the SECOND half of the caller's own buffer (n d u16 = half of n d f32) and are widened
+        // in place, front to back: element i is written at bytes 4 i .. 4 i + 3 and read from bytes 2 n d + 2 i, which no earlier
+        // write has reached (4 i + 4 <= 2 n d + 2 i + 2 for every i < n d).
+        const size_t nd = n * (size_t)h->g.d;
+        unsigned char *base = reinterpret_cast<unsigned char *>(vectors);
+        try { // (the device-to-host staging slab is a std::vector)
+            if (int rc = leann_internal_bf16_to_host(h, 0, n, reinterpret_cast<uint16_t *>(base + 2 * nd))) return rc;
+        } catch (const std::exception &e) {
+            leann_set_error("leann_backend_graph_export: %s", e.what());
+            return LEANN_ERR_IO;
+        }
+        for (size_t i = 0; i < nd; i++) {
+            uint16_t b;
+            memcpy(&b, base + 2 * nd + 2 * i, 2);
+            const uint32_t w = (uint32_t)b << 16;
+            memcpy(base + 4 * i, &w, 4);
+        }
+        return LEANN_OK;
+    }
     if (vectors)
         HIP_CHECK_RET(hipMemcpy2D(vectors, (size_t)h->g.d * 4, h->g.X, (size_t)h->g.ld * 4, (size_t)h->g.d * 4, n,
                                   hipMemcpyDeviceToHost));

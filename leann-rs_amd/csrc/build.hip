@@ -702,6 +702,17 @@ static int check_degree(int backend, size_t graph_degree, size_t complexity) {
     }
     return LEANN_OK;
 }
+int leann_internal_check_build_args(int backend, size_t graph_degree, size_t complexity) { // for rows_bf16.hip: before any device work
+    if (backend != LEANN_BACKEND_HNSW && backend != LEANN_BACKEND_DISKANN) {
+        leann_set_error("Unknown backend: %d", backend);
+        return LEANN_ERR_INVALID;
+    }
+    return check_degree(backend, graph_degree, complexity);
+}
+// the device build WITHOUT the row screen's split planes: for a caller that replaces the f32 rows afterwards (rows_bf16.hip) — the
+// planes would be a second full-size copy of rows that are about to go
+int leann_internal_build_device_no_planes(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld, size_t graph_degree,
+                                          size_t complexity, int device, uint64_t key_offset, leann_backend **out);
 // `planes`: cut the row screen's split planes (planes.hip) for the new handle — not for one that is only saved and closed again
 static int build_device_guarded(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld, size_t graph_degree, size_t complexity,
                                 int device, uint64_t key_offset, int take_copy, leann_backend **out, bool planes) {
@@ -716,6 +727,10 @@ extern "C" int leann_backend_build_device(int backend, const float *d_vectors, s
                                           size_t graph_degree, size_t complexity, int device, uint64_t key_offset,
                                           int take_copy, leann_backend **out) {
     return build_device_guarded(backend, d_vectors, n, dims, ld, graph_degree, complexity, device, key_offset, take_copy, out, true);
+}
+int leann_internal_build_device_no_planes(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld, size_t graph_degree,
+                                          size_t complexity, int device, uint64_t key_offset, leann_backend **out) {
+    return build_device_guarded(backend, d_vectors, n, dims, ld, graph_degree, complexity, device, key_offset, 0, out, false);
 }
 static int build_device_impl(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld, size_t graph_degree, size_t complexity,
                              int device, uint64_t key_offset, int take_copy, leann_backend **out, bool planes) {
@@ -829,6 +844,11 @@ extern "C" int leann_backend_add(int backend, const float *vectors, size_t n, si
     if (tomb_n) tomb.resize((n_old + n + 7) / 8, 0);
     if (old->g.feat_h) { // a recompute-on index holds encoder inputs, not vectors: appending needs the passages' features, not their embeddings
         leann_set_error("add_to_index: this index stores no vectors (recompute-on); rebuild it from the encoder inputs (leann_recompute_build_index)");
+        leann_backend_close(old);
+        return LEANN_ERR_UNSUPPORTED;
+    }
+    if (leann_internal_bf16(old)) { // the builder reads f32 rows, and appending f32 rows to rounded ones would break the file's reproducibility
+        leann_set_error("add_to_index: this index stores bf16 rows; appending is not supported, rebuild it (leann_backend_build_rows) from all the rows");
         leann_backend_close(old);
         return LEANN_ERR_UNSUPPORTED;
     }

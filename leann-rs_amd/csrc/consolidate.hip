@@ -417,6 +417,10 @@ static int consolidate_plain(leann_backend *h) {
         leann_set_error("leann_backend_consolidate: a recompute-on index holds no f32 rows to prune on; its removals stay tombstones");
         return LEANN_ERR_UNSUPPORTED;
     }
+    if (leann_internal_bf16(h)) {
+        leann_set_error("leann_backend_consolidate: the repair prunes on f32 rows; this index stores bf16 rows, its removals stay tombstones answered by the filtered walk");
+        return LEANN_ERR_UNSUPPORTED;
+    }
     if (!h->n_removed || !h->d_live || !h->g.n) return LEANN_OK;
     const uint32_t n = (uint32_t)h->g.n;
     CCHECK(hipSetDevice(h->device));
@@ -569,6 +573,11 @@ extern "C" int leann_backend_remove_from_index(int backend, const uint64_t *keys
     leann_backend *h = nullptr;
     int rc = leann_backend_open(index_path_stem, backend, dims, "0", &h);
     if (rc) return rc;
+    if (leann_internal_bf16(h)) { // its consolidate step needs f32 rows: refused before anything changes
+        leann_set_error("leann_backend_remove_from_index: not available on an index of bf16 rows (no graph repair); open it, leann_backend_remove, leann_backend_save: the removals stay tombstones");
+        leann_backend_close(h);
+        return LEANN_ERR_UNSUPPORTED;
+    }
     rc = leann_backend_remove(h, keys, n, nullptr);
     if (rc == LEANN_OK && !h->g.feat_h) rc = leann_backend_consolidate(h); // (recompute-on: the removals stay tombstones)
     if (rc == LEANN_OK) rc = leann_backend_save(h, index_path_stem);

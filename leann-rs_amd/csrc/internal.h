@@ -96,7 +96,25 @@ struct leann_backend {
     uint64_t planes_n = 0;
     unsigned long long *screen_ctr = nullptr;
     std::atomic<int> row_screen{leann_knobs().row_screen};
+    // Row type (rows_bf16.hip): LEANN_ROWS_F32, or LEANN_ROWS_BF16 — then g.X names the handle's own bf16 store, [n x g.row_bytes / 2]
+    // u16 in rs_plane_pos order (g.row_bytes: a multiple of 128, zero padded), g.feat_h stays 0, no f32 rows exist and no planes are
+    // ever cut.  Every path that reads g.X as f32 checks this first.  (A recompute-on handle reports LEANN_ROWS_FEATURES through
+    // leann_backend_row_type; here it is g.feat_h != 0 as before.)
+    int row_type = LEANN_ROWS_F32;
 };
+inline bool leann_internal_bf16(const leann_backend *h) { return h->row_type == LEANN_ROWS_BF16; }
+// bf16 row store (rows_bf16.hip).  _adopt_device: allocate h's store and fill it with r(rows) of f32 device rows [n x ld_src] (h->g.n /
+// d / ld set; h's device current); afterwards h owns the store and names no f32 rows.  _adopt_host: the same from host rows, f32
+// [n x d] (rounded on the device, slab by slab) or bf16 [n x d] in element order (an index file's).  _to_host: rows [r0, r0 + rows)
+// as bf16 [rows x d] in element order.
+int leann_internal_bf16_adopt_device(leann_backend *h, const float *d_src, size_t ld_src);
+int leann_internal_bf16_adopt_host(leann_backend *h, const float *f32_rows, const uint16_t *bf16_rows);
+int leann_internal_bf16_to_host(const leann_backend *h, size_t r0, size_t rows, uint16_t *out);
+int leann_internal_check_build_args(int backend, size_t graph_degree, size_t complexity); // build.hip: backend and list lengths
+// build.hip: leann_backend_build_device (rows borrowed) without cutting the row screen's planes
+int leann_internal_build_device_no_planes(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld, size_t graph_degree,
+                                          size_t complexity, int device, uint64_t key_offset, leann_backend **out);
+int leann_internal_launch_search_bf16(const GraphView &g, const SearchArgs &a, hipStream_t st); // search_bf16.hip
 bool leann_internal_screen_shape(const GraphView &g);      // the row widths and list lengths the screen kernel is compiled for
 void leann_internal_sync_planes(leann_backend *h);          // (re)build the planes of a plain handle; logs and returns on failure
 bool leann_internal_planes_ready(const leann_backend *h);   // planes present and cut from the rows h->g names now
@@ -121,7 +139,10 @@ bool leann_log_enabled(int level); // for callers whose message costs something 
 int leann_internal_from_host(int backend, size_t n, size_t dims, uint32_t M, uint32_t M0, uint32_t max_level, uint32_t entry,
                              const uint8_t *levels, const uint32_t *upper_off, const uint32_t *adj0, const uint32_t *adjU,
                              size_t n_upper_lists, const float *vectors, const unsigned char *feat_rows, uint32_t feat_h, uint32_t row_bytes,
-                             const float *Wf32, int device, uint64_t key_offset, leann_backend **out);
+                             const float *Wf32, int device, uint64_t key_offset, leann_backend **out, int row_type = LEANN_ROWS_F32,
+                             const uint16_t *bf16_rows = nullptr, const float *d_f32_rows = nullptr, size_t d_f32_ld = 0);
+// ^ row_type LEANN_ROWS_BF16: the rows come as host f32 `vectors` (rounded), host `bf16_rows` [n x dims] (an index file's) or device
+//   f32 rows `d_f32_rows` [n x d_f32_ld] (rounded; leann_backend_to_rows) — exactly one of the three.
 int leann_internal_save_to(const leann_backend *h, const std::string &path);
 int leann_internal_parse_device(const char *spec, int *device);
 // sharded handles (shard.hip)

@@ -29,18 +29,7 @@
 #include <mutex>
 #include <utility>
 #include <vector>
-
-
-__host__ __device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
-    uint32_t u;
-#if defined(__HIP_DEVICE_COMPILE__)
-    u = __float_as_uint(f);
-#else
-    memcpy(&u, &f, 4);
-#endif
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40); // NaN stays NaN
-    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
+#include "bf16.h" // f32_to_bf16_rne
 
 // ---- synthetic features / weights: the recompute twin of gen.hip -----------------------------------
 // f_i[k] = bf16(centre_c[k] + sigma * noise_i[k]),  W[k][j] = bf16(gauss(k, j))  (same hash streams as

@@ -266,6 +266,35 @@ __device__ __forceinline__ void wave_dist_rows_feat(const float4 (&q)[T], const 
     }
 }
 
+// bf16 rows (LEANN_ROWS_BF16, rows_bf16.hip): the stored row IS bf16, [n x ldb] u16 in rs_plane_pos order (ldb: dims rounded up to 64
+// elements — whole 128-B lines, zero padded), so a lane's eight halves of a 512-element block come in ONE 16-byte load
+// (plane_row_load).  Widened exactly (b << 16) in registers and summed in the canonical order — lane l owns elements 256t+4l..+3,
+// fma4 over t ascending, lane4_sum, wave_tree_sum, 1 - sum — so the distance is bit for bit the f32 kernels' on the widened rows.
+template <int T, int R>
+__device__ __forceinline__ void wave_dist_rows_bf16(const float4 (&q)[T], const uint16_t *__restrict__ Xb, uint32_t ldb,
+                                                    const uint32_t (&ids)[R], int nrows, int lane, float (&out)[R]) {
+    uint2 v[R][T];
+#pragma unroll
+    for (int r = 0; r < R; r++)
+        if (r < nrows) plane_row_load<T>(Xb + (size_t)ids[r] * ldb, ldb, lane, v[r]);
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        if (r < nrows) {
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int t = 0; t < T; t++) {
+                float4 x;
+                x.x = __uint_as_float(v[r][t].x << 16);
+                x.y = __uint_as_float(v[r][t].x & 0xFFFF0000u);
+                x.z = __uint_as_float(v[r][t].y << 16);
+                x.w = __uint_as_float(v[r][t].y & 0xFFFF0000u);
+                fma4(acc, q[t], x);
+            }
+            out[r] = 1.0f - wave_tree_sum(lane4_sum(acc));
+        }
+    }
+}
+
 // Recompute-on rows of exactly 256 bf16 features (+ inline norm), FOUR passages per wave instruction: the 16 lanes of a DPP row share a
 // passage, lane m of them owns elements 8m..8m+7 and 128+8m..128+8m+7 (two 16-byte loads; each instruction reads a contiguous 256-B
 // half of four rows), and one pass of the DPP ladder reduces four rows at once — against one row per 8-byte wave load and one
@@ -352,13 +381,15 @@ __host__ __device__ inline size_t search_lds_bytes(uint32_t ef, uint32_t maxdeg,
 // Phase B compacts the second half behind the first with a second ballot (the unseen ids keep list order), phase E reduces over both
 // keys of a lane and adds a second rank count; phases C and D already loop over n_new.  LW = 1 compiles to the narrow code unchanged.
 // SCREEN (throughput form of the plain f32 search only): phase C goes through the split planes (wave_dist_rows_screen).
-template <int T, int R, int NW, bool FEAT, bool FILT = false, bool G16 = false, int LW = 1, bool SCREEN = false>
+// BF16 (search_bf16.hip): the rows are bf16 (g.X names them, g.row_bytes apart); phase C and the entry go through wave_dist_rows_bf16.
+template <int T, int R, int NW, bool FEAT, bool FILT = false, bool G16 = false, int LW = 1, bool SCREEN = false, bool BF16 = false>
 __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_t qi, unsigned char *smem) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const auto *const za = lazy_search_args(); // arguments of the rare paths and of the epilogue: read where they are used
     const uint32_t ef = a.ef;
     static_assert(LW == 1 || LW == 2, "lists of at most 128 ids");
     static_assert(!SCREEN || (NW == 4 && !FEAT && !FILT && !G16 && LW == 1), "the row screen exists in the plain throughput form only");
+    static_assert(!BF16 || (!FEAT && !G16 && !SCREEN), "bf16 rows: stored vectors, whole rows");
     const uint32_t maxdeg = g.M0 > g.M ? g.M0 : g.M;
     const uint32_t efp = (ef + 1) & ~1u;
     SearchLds s;
@@ -426,6 +457,7 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
             group_dist_rows_feat256<1>(qa, qb, reinterpret_cast<const char *>(g.X), g.row_bytes, ids, valid, lane, dd, g.norms);
             dd[0] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dd[0]), 15));
         } else if (FEAT) wave_dist_rows_feat<T, 1>(q, reinterpret_cast<const char *>(g.X), g.row_bytes, g.feat_h, ids, 1, lane, dd, g.norms);
+        else if constexpr (BF16) wave_dist_rows_bf16<T, 1>(q, reinterpret_cast<const uint16_t *>(g.X), g.row_bytes >> 1, ids, 1, lane, dd);
         else wave_dist_rows<T, 1>(q, g.X, g.ld, ids, 1, lane, dd);
         best = make_key(dd[0], g.entry); // every wave computes the same value
     }
@@ -642,6 +674,7 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
                         abit = e & 7u;
                     }
                     if (FEAT) wave_dist_rows_feat<T, R>(q, reinterpret_cast<const char *>(g.X), g.row_bytes, g.feat_h, ids, nrows, lane, dd, g.norms);
+                    else if constexpr (BF16) wave_dist_rows_bf16<T, R>(q, reinterpret_cast<const uint16_t *>(g.X), g.row_bytes >> 1, ids, nrows, lane, dd);
                     else wave_dist_rows<T, R>(q, g.X, g.ld, ids, nrows, lane, dd);
                     const unsigned long long amask = FILT ? __ballot((abyte >> abit) & 1u) : 0ull;
                     if (lane == 0) {
@@ -955,6 +988,7 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
                         touch = adj0_p[(size_t)snew[j0 + (uint32_t)(lane >> 1) * NW] * deg + (uint32_t)(lane & 1) * 32u];
 #endif
                     if (FEAT) wave_dist_rows_feat<T, R>(q, reinterpret_cast<const char *>(g.X), g.row_bytes, g.feat_h, ids, nrows, lane, dd, g.norms);
+                    else if constexpr (BF16) wave_dist_rows_bf16<T, R>(q, reinterpret_cast<const uint16_t *>(g.X), g.row_bytes >> 1, ids, nrows, lane, dd);
                     else wave_dist_rows<T, R>(q, g.X, g.ld, ids, nrows, lane, dd);
 #ifndef LEANN_NO_ADJ_TOUCH
                     asm volatile("" ::"v"(touch));

@@ -189,8 +189,8 @@ extern "C" int leann_sharded_from_handles(leann_backend *const *shards, size_t n
     *out = nullptr;
     for (size_t g = 0; g < n_shards; g++) {
         if (!shards[g] || shards[g]->sharded || shards[g]->g.d != shards[0]->g.d || shards[g]->kind != shards[0]->kind ||
-            (shards[g]->g.feat_h != 0) != (shards[0]->g.feat_h != 0)) {
-            leann_set_error("leann_sharded_from_handles: shard %zu is null, itself sharded, or differs from shard 0 in kind / dimensions", g);
+            (shards[g]->g.feat_h != 0) != (shards[0]->g.feat_h != 0) || shards[g]->row_type != shards[0]->row_type) {
+            leann_set_error("leann_sharded_from_handles: shard %zu is null, itself sharded, or differs from shard 0 in kind / dimensions / row type", g);
             return LEANN_ERR_INVALID;
         }
     }

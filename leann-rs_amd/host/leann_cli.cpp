@@ -247,15 +247,23 @@ static int run_search(int argc, char **argv) {
 
 // leann build --index-dir DIR --passages-jsonl FILE [--backend-name hnsw|diskann] [--graph-degree 32]
 //             [--complexity 64] [--dimensions 128] [--embedding-mode synthetic|synthetic-linear] [--recompute] [--pruned]
-//             [--recompute-graph]
+//             [--recompute-graph] [--row-type f32|bf16]
 // --recompute       also write documents.embeddings (only in recompute mode, src/index/builder.rs:105-113), so that the index can be
 //                   pruned later; off by default like the reference (meta.is_recompute = args.recompute)
 // --pruned          no ANN file and no embeddings: the reference's pruned state (brute-force recompute at query time)
 // --recompute-graph (needs --embedding-mode synthetic-linear) graph + compact encoder inputs, no vectors
+// --row-type        what the ANN file stores per element: f32 (default) or bf16 (half the file and device memory; the rows are rounded
+//                   first and the graph is built on the rounded rows, DESIGN.md "bf16 rows")
+static int parse_row_type(const std::string &v) {
+    if (v == "f32") return LEANN_ROWS_F32;
+    if (v == "bf16") return LEANN_ROWS_BF16;
+    throw Error("invalid value '" + v + "' for '--row-type': expected f32 or bf16");
+}
 static int run_build(int argc, char **argv) {
     std::string dir, jsonl, backend_name = "hnsw", mode = "synthetic";
     size_t degree = 32, complexity = 64, dims = 128;
     bool pruned = false, recompute = false, rgraph = false; // is_recompute = args.recompute, default false (src/cli/build.rs:363)
+    int row_type = LEANN_ROWS_F32;
     for (int i = 0; i < argc; i++) {
         std::string s = argv[i];
         auto val = [&]() -> std::string { if (i + 1 >= argc) throw Error("missing value for " + s); return argv[++i]; };
@@ -269,11 +277,13 @@ static int run_build(int argc, char **argv) {
         else if (s == "--pruned") pruned = true;
         else if (s == "--recompute") recompute = true;
         else if (s == "--recompute-graph") { rgraph = true; mode = "synthetic-linear"; }
+        else if (s == "--row-type") row_type = parse_row_type(val());
         else throw Error("unexpected argument '" + s + "' found");
     }
     if (dir.empty() || jsonl.empty()) throw Error("usage: leann build --index-dir DIR --passages-jsonl FILE [...]");
     int backend = backend_name == "hnsw" ? LEANN_BACKEND_HNSW : backend_name == "diskann" ? LEANN_BACKEND_DISKANN : -1;
     if (backend < 0) throw Error("Unknown backend: " + backend_name);
+    if (row_type != LEANN_ROWS_F32 && (pruned || rgraph)) throw Error("--row-type applies to an index of stored vectors, not to --pruned / --recompute-graph");
     EmbeddingProvider provider(mode, dims);
     ::mkdir(dir.c_str(), 0755);
     std::string stem = dir + "/documents.leann";
@@ -319,7 +329,8 @@ static int run_build(int argc, char **argv) {
             std::ofstream ef(with_extension(stem, "embeddings"), std::ios::binary);
             ef.write((const char *)all.data(), (std::streamsize)(all.size() * 4));
         }
-        check(leann_backend_build(backend, all.data(), n, dims, degree, complexity, stem.c_str()));
+        if (row_type == LEANN_ROWS_F32) check(leann_backend_build(backend, all.data(), n, dims, degree, complexity, stem.c_str()));
+        else check(leann_backend_build_rows(backend, all.data(), n, dims, degree, complexity, row_type, stem.c_str()));
     }
     IndexMeta m;
     m.version = "1.0";
@@ -337,7 +348,7 @@ static int run_build(int argc, char **argv) {
     }
     m.save(dir + "/documents.leann.meta.json");
     printf("Indexed %zu passages (%zu dims, backend %s%s) into %s\n", n, dims, backend_name.c_str(),
-           rgraph ? ", recompute-on graph (no vectors)" : pruned ? ", pruned" : "", dir.c_str());
+           rgraph ? ", recompute-on graph (no vectors)" : pruned ? ", pruned" : row_type == LEANN_ROWS_BF16 ? ", bf16 rows" : "", dir.c_str());
     return 0;
 }
 
@@ -393,16 +404,57 @@ static int run_delete(int argc, char **argv) {
     return 0;
 }
 
+// leann convert <index> --row-type bf16   (additive)
+// Rewrites the ANN file of an existing f32 index with bf16 rows: open -> leann_backend_to_rows -> save.  The graph stays the one that
+// was built on the exact rows; removals (the tombstone sidecar) are carried over.  Passages, ids and meta files are not touched: the
+// row type lives in the index file alone.
+static int run_convert(int argc, char **argv) {
+    std::string index_name;
+    int row_type = -1;
+    for (int i = 0; i < argc; i++) {
+        std::string s = argv[i];
+        auto val = [&]() -> std::string { if (i + 1 >= argc) throw Error("a value is required for '" + s + "' but none was supplied"); return argv[++i]; };
+        if (s == "-h" || s == "--help") { puts("Rewrite an index with another row type\n\nUsage: leann convert <INDEX> --row-type bf16"); return 0; }
+        else if (s == "--row-type") row_type = parse_row_type(val());
+        else if (s == "-i" || s == "--index") index_name = val();
+        else if (!s.empty() && s[0] == '-' && s.size() > 1) throw Error("unexpected argument '" + s + "' found");
+        else if (index_name.empty()) index_name = s;
+        else throw Error("unexpected argument '" + s + "' found");
+    }
+    if (index_name.empty()) throw Error("the following required arguments were not provided:\n  <INDEX>");
+    if (row_type < 0) throw Error("the following required arguments were not provided:\n  --row-type <f32|bf16>");
+    std::string index_path = find_index(index_name) + "/documents.leann";
+    IndexMeta meta = IndexMeta::load(index_path + ".meta.json");
+    int backend = meta.backend_name == "hnsw" ? LEANN_BACKEND_HNSW : meta.backend_name == "diskann" ? LEANN_BACKEND_DISKANN : -1;
+    if (backend < 0) throw Error("Unknown backend: " + meta.backend_name);
+    leann_backend *h = nullptr, *b = nullptr;
+    check(leann_backend_open(index_path.c_str(), backend, meta.dimensions, "0", &h));
+    if (leann_backend_row_type(h) == row_type) {
+        leann_backend_close(h);
+        printf("Index '%s': rows are %s already\n", index_name.c_str(), row_type == LEANN_ROWS_BF16 ? "bf16" : "f32");
+        return 0;
+    }
+    int rc = leann_backend_to_rows(h, row_type, &b);
+    if (rc == 0) rc = leann_backend_save(b, index_path.c_str());
+    const size_t n = leann_backend_len(h);
+    if (b) leann_backend_close(b);
+    leann_backend_close(h);
+    check(rc);
+    printf("Index '%s': %zu rows rewritten as %s\n", index_name.c_str(), n, row_type == LEANN_ROWS_BF16 ? "bf16" : "f32");
+    return 0;
+}
+
 int main(int argc, char **argv) {
     try {
         if (argc < 2 || !strcmp(argv[1], "-h") || !strcmp(argv[1], "--help")) {
-            puts("LEANN search path on MI355X\n\nUsage: leann <COMMAND>\n\nCommands:\n  search  Query an index\n  build   Build an index from a passages JSONL (synthetic embeddings)\n  delete  Remove passages from an index\n");
+            puts("LEANN search path on MI355X\n\nUsage: leann <COMMAND>\n\nCommands:\n  search  Query an index\n  build   Build an index from a passages JSONL (synthetic embeddings)\n  delete  Remove passages from an index\n  convert Rewrite an index with another row type (f32 -> bf16)\n");
             return argc < 2 ? 2 : 0;
         }
         if (!strcmp(argv[1], "--version") || !strcmp(argv[1], "-V")) { printf("leann %s\n", leann_version()); return 0; }
         if (!strcmp(argv[1], "search")) return run_search(argc - 2, argv + 2);
         if (!strcmp(argv[1], "build")) return run_build(argc - 2, argv + 2);
         if (!strcmp(argv[1], "delete")) return run_delete(argc - 2, argv + 2);
+        if (!strcmp(argv[1], "convert")) return run_convert(argc - 2, argv + 2);
         throw Error(std::string("unrecognized subcommand '") + argv[1] + "'");
     } catch (const std::exception &e) {
         fprintf(stderr, "Error: %s\n", e.what());
