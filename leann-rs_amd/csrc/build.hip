@@ -14,9 +14,11 @@
 //   3. proposes itself to each selected neighbour; proposals are radix-sorted by (target, dist)
 //      so that every touched list is rewritten by exactly one workgroup: append while there is
 //      room (2M on level 0), otherwise the same heuristic over list ∪ proposals.
-// No atomics decide content, so a build is reproducible run to run.  The sequential restatement
-// lives in oracle/oracle.c (orc_hnsw_build / orc_vamana_build); batched insertion is a different
-// schedule, so graphs are compared by invariants + recall, not bit for bit.
+// No atomics decide content, so a build is reproducible run to run.  The sequential builders live
+// in oracle/oracle.c (orc_hnsw_build / orc_vamana_build); batched insertion is a different schedule,
+// so against them graphs are compared by invariants + recall.  The batched schedule itself is restated
+// in tests/build_ref.py: on rows with exact f32 dot products a build equals it list for list
+// (tests/test_gpu_build_parity.py); inexact rows keep the quality bar.
 #include "common.cuh"
 #include "search.cuh"
 #include "internal.h"
@@ -204,7 +206,8 @@ __device__ __forceinline__ void reverse_merge_one(const float *__restrict__ X, u
     __shared__ float c_d[NC];
     __shared__ __attribute__((aligned(16))) float wstage[Pool<NC>::STAGE];
     __shared__ uint32_t s_sel[64 * Pool<NC>::KS];
-    __shared__ uint32_t s_cnt, s_k, s_len, s_pl;
+    __shared__ uint32_t s_cnt, s_k, s_len, s_pl, s_held;
+    uint32_t *const have = reinterpret_cast<uint32_t *>(tri); // the ids the target holds: list at [0, cap), pending at [128, 128 + P)
     const uint32_t nseg = flush_nodes ? flush_nodes : *nseg_p;
     const uint32_t P = level == 0 ? lv.P : 0u;
     for (uint32_t seg = blockIdx.x; seg < nseg; seg += gridDim.x) {
@@ -214,25 +217,65 @@ __device__ __forceinline__ void reverse_merge_one(const float *__restrict__ X, u
         list_ptr(lv, t, level, &ids, &ds, &cap);
         uint32_t *pid = P ? lv.pend + (size_t)t * P : nullptr;
         float *pdd = P ? lv.pendd + (size_t)t * P : nullptr;
-        if (threadIdx.x == 0) { s_k = 0; s_len = 0; s_pl = 0; }
+        if (threadIdx.x == 0) { s_k = 0; s_len = 0; s_pl = 0; s_held = 0; }
         __syncthreads();
         // proposals of this run (sorted by dist): count up to NC; existing list / pending lengths
         if (!flush_nodes && threadIdx.x < NC) {
             uint32_t i = start + threadIdx.x;
             if (i < num && (uint32_t)(keys[i] >> 32) == t) atomicAdd(&s_k, 1u); // run is contiguous
         }
-        if (threadIdx.x < cap && ids[threadIdx.x] != LEANN_EMPTY) atomicAdd(&s_len, 1u); // lists are compact
-        if (threadIdx.x >= 64 && threadIdx.x < 64 + P && pid[threadIdx.x - 64] != LEANN_EMPTY) atomicAdd(&s_pl, 1u);
+        if (threadIdx.x < cap) {
+            const uint32_t e = ids[threadIdx.x];
+            have[threadIdx.x] = e;
+            if (e != LEANN_EMPTY) atomicAdd(&s_len, 1u); // lists are compact
+        }
+        if (threadIdx.x >= 64 && threadIdx.x < 64 + P) {
+            const uint32_t e = pid[threadIdx.x - 64];
+            have[128 + threadIdx.x - 64] = e;
+            if (e != LEANN_EMPTY) atomicAdd(&s_pl, 1u);
+        }
         __syncthreads();
         const uint32_t len = s_len, pl = s_pl;
         uint32_t k = s_k;
         if (flush_nodes && pl == 0) { __syncthreads(); continue; }
+        if (!flush_nodes) {
+            // The run moves into LDS (c_id / c_d, free until the sorted pool is written), without the proposals whose source the list
+            // or the pending area holds already: a refine pass (LEANN_VAMANA_PASSES) re-links points that are linked, and a source
+            // appended or merged a second time would stand in the list twice.  The order of the others is kept.  k <= NC <= 256:
+            // thread j owns proposal j.
+            const bool mine = threadIdx.x < k;
+            uint32_t src = 0;
+            float dj = 0.f;
+            bool held = false;
+            if (mine) {
+                src = srcs[start + threadIdx.x];
+                dj = orderable_f32((uint32_t)keys[start + threadIdx.x]);
+                for (uint32_t i = 0; i < len; i++) held |= have[i] == src;
+                for (uint32_t i = 0; i < pl; i++) held |= have[128 + i] == src;
+                if (held) atomicAdd(&s_held, 1u);
+            }
+            if (threadIdx.x < NC) skey[threadIdx.x] = (mine && !held) ? 1ull : 0ull;
+            __syncthreads();
+            const uint32_t n_held = s_held;
+            if (mine && !held) {
+                uint32_t pos = threadIdx.x;
+                if (n_held) { // (never in a first pass: its sources are new to the graph)
+                    pos = 0;
+                    for (uint32_t i = 0; i < threadIdx.x; i++) pos += (uint32_t)skey[i];
+                }
+                c_id[pos] = src;
+                c_d[pos] = dj;
+            }
+            k -= n_held;
+            __syncthreads();
+            if (k == 0) continue;
+        }
         const uint32_t room = cap - len;
         if (!flush_nodes && k <= room + (P - pl)) {
             // room in the list (visible at once, closest proposals first), then in the pending area: plain appends in (dist, src) order
             for (uint32_t j = threadIdx.x; j < k; j += 256) {
-                const uint32_t src = srcs[start + j];
-                const float dj = orderable_f32((uint32_t)keys[start + j]);
+                const uint32_t src = c_id[j];
+                const float dj = c_d[j];
                 if (j < room) { ids[len + j] = src; ds[len + j] = dj; }
                 else { pid[pl + j - room] = src; pdd[pl + j - room] = dj; }
             }
@@ -245,7 +288,7 @@ __device__ __forceinline__ void reverse_merge_one(const float *__restrict__ X, u
             uint64_t key = ~0ull;
             if (i < len) key = ((uint64_t)f32_orderable(ds[i]) << 32) | ids[i];
             else if (i < len + pl) key = ((uint64_t)f32_orderable(pdd[i - len]) << 32) | pid[i - len];
-            else if (i < nc) key = ((uint64_t)(uint32_t)keys[start + i - len - pl] << 32) | srcs[start + i - len - pl];
+            else if (i < nc) key = ((uint64_t)f32_orderable(c_d[i - len - pl]) << 32) | c_id[i - len - pl];
             skey[i] = key;
         }
         // bitonic sort of NC keys by (dist, id)

@@ -699,6 +699,106 @@ int orc_graph_search_filtered_batch(const orc_graph *g, const float *Q, uint64_t
     return 0;
 }
 
+/* Construction search (csrc/search.cuh: SearchArgs::target_level / out_expanded / out_nexp): greedy descent from max_level to
+ * target_level + 1, an ef-beam on target_level.  keys64[0..*n_out): the beam, orderable(dist) << 32 | id, ascending;
+ * exp_keys64[0..*n_exp): the first exp_cap nodes expanded on the target level, in expansion order.  A target level above
+ * max_level returns nothing (the kernel's level loop does not run). */
+static void graph_search_level_ctx(const orc_graph *g, const float *q, uint32_t target_level, uint32_t ef, int algo, ctx_t *c,
+                                   uint64_t *keys64, uint32_t *n_out, uint64_t *exp_keys64, uint32_t exp_cap, uint32_t *n_exp) {
+    *n_out = 0;
+    if (n_exp) *n_exp = 0;
+    if (g->n == 0 || ef == 0 || target_level > g->max_level) return;
+    uint64_t best = mk_key(gdist(g, q, g->entry), g->entry);
+    for (uint32_t lv = g->max_level; lv > target_level; lv--) {
+        search_layer(g, q, &best, 1, 1, lv, algo, c);
+        best = c->W[0];
+    }
+    search_layer(g, q, &best, 1, ef, target_level, algo, c);
+    memcpy(keys64, c->W, (size_t)c->nW * 8);
+    *n_out = c->nW;
+    if (exp_keys64 && n_exp) {
+        uint32_t m = c->nexp < exp_cap ? c->nexp : exp_cap;
+        memcpy(exp_keys64, c->exp, (size_t)m * 8);
+        *n_exp = m;
+    }
+}
+int orc_graph_search_level(const orc_graph *g, const float *q, uint32_t target_level, uint32_t ef, int algo,
+                           uint64_t *keys64, uint32_t *n_out, uint64_t *exp_keys64, uint32_t exp_cap, uint32_t *n_exp) {
+    ctx_t *c = ctx_new(g->n, ef);
+    graph_search_level_ctx(g, q, target_level, ef, algo, c, keys64, n_out, exp_keys64, exp_cap, n_exp);
+    ctx_free(c);
+    return 0;
+}
+typedef struct {
+    const orc_graph *g;
+    const uint32_t *rows;
+    uint64_t lo, hi;
+    uint32_t target_level, ef, exp_cap;
+    int algo;
+    uint64_t *keys64, *exp_keys64;
+    uint32_t *counts, *n_exp;
+} level_job;
+static void *level_worker(void *p) {
+    level_job *j = (level_job *)p;
+    ctx_t *c = ctx_new(j->g->n, j->ef);
+    for (uint64_t i = j->lo; i < j->hi; i++)
+        graph_search_level_ctx(j->g, j->g->X + (size_t)j->rows[i] * j->g->ld, j->target_level, j->ef, j->algo, c,
+                               j->keys64 + i * j->ef, j->counts + i, j->exp_keys64 ? j->exp_keys64 + i * j->exp_cap : NULL,
+                               j->exp_cap, j->n_exp ? j->n_exp + i : NULL);
+    ctx_free(c);
+    return NULL;
+}
+/* batch form: query i is the graph's own row rows[i] (SearchArgs::q_rows); keys64 [nq x ef], exp_keys64 [nq x exp_cap] or NULL */
+int orc_graph_search_level_batch(const orc_graph *g, const uint32_t *rows, uint64_t nq, uint32_t target_level, uint32_t ef,
+                                 int algo, uint32_t nthreads, uint64_t *keys64, uint32_t *counts, uint64_t *exp_keys64,
+                                 uint32_t exp_cap, uint32_t *n_exp) {
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > nq) nthreads = nq ? (uint32_t)nq : 1;
+    pthread_t *th = (pthread_t *)malloc(nthreads * sizeof(pthread_t));
+    level_job *jobs = (level_job *)malloc(nthreads * sizeof(level_job));
+    for (uint32_t t = 0; t < nthreads; t++) {
+        level_job j = {g, rows, nq * t / nthreads, nq * (t + 1) / nthreads, target_level, ef, exp_cap, algo, keys64, exp_keys64, counts, n_exp};
+        jobs[t] = j;
+        if (nthreads == 1) level_worker(&jobs[t]);
+        else pthread_create(&th[t], NULL, level_worker, &jobs[t]);
+    }
+    if (nthreads > 1)
+        for (uint32_t t = 0; t < nthreads; t++) pthread_join(th[t], NULL);
+    free(th);
+    free(jobs);
+    return 0;
+}
+
+/* The builder's prune rule (csrc/prune.cuh: prune_core) over a pool given as ids and distances to the point, ascending by
+ * (dist, id): positions kept, in kept order.  alpha == 0: HNSW rule; alpha > 0: RobustPrune, two-stage when alpha > 1 and
+ * two_stage.  Pair distances are 1 - <x_a, x_b> summed in storage order, so it restates the device only for rows whose dot
+ * products are exact in f32; tests/consolidate_ref.py:prune is the same rule in numpy and its cross-check. */
+uint32_t orc_prune(const float *X, uint32_t d, uint32_t ld, const uint32_t *ids, const float *dists, uint32_t nc, uint32_t limit,
+                   float alpha, int two_stage, uint32_t *out_pos) {
+    if (nc == 0 || limit == 0) return 0;
+    const int ts = alpha > 1.0f && two_stage;
+    uint8_t *taken = (uint8_t *)calloc(nc, 1);
+    uint32_t ns = 0;
+    for (int stage = 0; stage < (ts ? 2 : 1) && ns < limit; stage++) {
+        const float a = ts && stage == 0 ? 1.0f : alpha;
+        for (uint32_t i = 0; i < nc && ns < limit; i++) {
+            if (taken[i]) continue;
+            const float *xc = X + (size_t)ids[i] * ld;
+            int good = 1;
+            for (uint32_t s = 0; s < ns && good; s++) {
+                const float *xk = X + (size_t)ids[out_pos[s]] * ld;
+                float dot = 0.0f;
+                for (uint32_t t = 0; t < d; t++) dot += xc[t] * xk[t];
+                const float gd = 1.0f - dot;
+                if (alpha == 0.0f ? (gd < dists[i]) : (a * gd <= dists[i])) good = 0;
+            }
+            if (good) { out_pos[ns++] = i; taken[i] = 1; }
+        }
+    }
+    free(taken);
+    return ns;
+}
+
 /* ---- construction --------------------------------------------------------------------------- */
 static orc_graph *graph_alloc(const float *X, uint64_t n, uint32_t d, uint32_t M, uint32_t M0,
                               const uint8_t *levels_in) {

@@ -103,6 +103,20 @@ int orc_graph_search_filtered_batch(const orc_graph *g, const float *Q, uint64_t
                                     int algo, uint32_t nthreads, const uint8_t *allow, uint64_t allow_stride,
                                     uint64_t *keys, float *dists, uint32_t *counts, uint64_t *stats);
 
+/* Construction search, the twin of SearchArgs::target_level / out_expanded / out_nexp (csrc/search.cuh): greedy descent from
+ * max_level to target_level + 1, then an ef-beam on target_level.  keys64: the beam as orderable(dist) << 32 | id, ascending
+ * (*n_out <= ef); exp_keys64: the first exp_cap nodes expanded on the target level, in expansion order (may be NULL).
+ * target_level > max_level: nothing.  Batch form: query i is the graph's own row rows[i]; keys64 [nq x ef], exp_keys64 [nq x exp_cap]. */
+int orc_graph_search_level(const orc_graph *g, const float *q, uint32_t target_level, uint32_t ef, int algo,
+                           uint64_t *keys64, uint32_t *n_out, uint64_t *exp_keys64, uint32_t exp_cap, uint32_t *n_exp);
+int orc_graph_search_level_batch(const orc_graph *g, const uint32_t *rows, uint64_t nq, uint32_t target_level, uint32_t ef,
+                                 int algo, uint32_t nthreads, uint64_t *keys64, uint32_t *counts, uint64_t *exp_keys64,
+                                 uint32_t exp_cap, uint32_t *n_exp);
+/* the builder's prune rule (csrc/prune.cuh) over a sorted pool; exact only for rows with exact f32 dot products
+ * (tests/build_ref.py; tests/consolidate_ref.py:prune is its numpy form) */
+uint32_t orc_prune(const float *X, uint32_t d, uint32_t ld, const uint32_t *ids, const float *dists, uint32_t nc, uint32_t limit,
+                   float alpha, int two_stage, uint32_t *out_pos);
+
 /* ---- top-k merge of per-shard results (new) --------------------------------- */
 void orc_merge_topk(const uint64_t *keys, const float *dists, const uint32_t *counts,
                     uint32_t n_shards, uint32_t k_in, uint32_t k_out, uint64_t *out_keys,

@@ -68,6 +68,12 @@ def lib():
                                              C.c_int, C.c_uint32, u64p, f32p, u32p, u64p]
         L.orc_graph_search_filtered_batch.argtypes = [C.c_void_p, f32p, C.c_uint64, C.c_uint32, C.c_uint32,
                                                       C.c_int, C.c_uint32, u8p, C.c_uint64, u64p, f32p, u32p, u64p]
+        L.orc_graph_search_level.argtypes = [C.c_void_p, f32p, C.c_uint32, C.c_uint32, C.c_int, u64p, u32p, u64p,
+                                             C.c_uint32, u32p]
+        L.orc_graph_search_level_batch.argtypes = [C.c_void_p, u32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32,
+                                                   u64p, u32p, u64p, C.c_uint32, u32p]
+        L.orc_prune.restype = C.c_uint32
+        L.orc_prune.argtypes = [f32p, C.c_uint32, C.c_uint32, u32p, f32p, C.c_uint32, C.c_uint32, C.c_float, C.c_int, u32p]
         L.orc_merge_topk.argtypes = [u64p, f32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, u64p,
                                      f32p, u32p]
         L.orc_hybrid_rerank.argtypes = [u64p, f32p, C.c_uint32, f32p, C.c_uint64, C.c_float, u64p,
@@ -208,11 +214,45 @@ class Graph:
                                               _p(keys, u64p), _p(dists, f32p), _p(counts, u32p), _p(stats, u64p))
         return keys, dists, counts, stats
 
+    def search_level(self, q, target_level, ef, algo=0, exp_cap=0):
+        """construction search (SearchArgs::target_level / out_expanded): -> (beam keys orderable(dist) << 32 | id, ascending;
+        the first exp_cap keys expanded on the target level, in expansion order)"""
+        q = np.ascontiguousarray(q, np.float32)
+        keys = np.zeros(max(ef, 1), np.uint64)
+        exp = np.zeros(max(exp_cap, 1), np.uint64)
+        n, ne = C.c_uint32(0), C.c_uint32(0)
+        lib().orc_graph_search_level(self.h, _p(q, f32p), target_level, ef, algo, _p(keys, u64p), C.byref(n), _p(exp, u64p),
+                                     exp_cap, C.byref(ne))
+        return keys[: n.value], exp[: ne.value]
+
+    def search_level_batch(self, rows, target_level, ef, algo=0, exp_cap=0, nthreads=1):
+        """the same for the graph's own rows `rows` as queries: -> keys [nq x ef], counts [nq], exp_keys [nq x exp_cap], n_exp [nq]"""
+        rows = np.ascontiguousarray(rows, np.uint32)
+        nq = rows.shape[0]
+        keys = np.full((nq, max(ef, 1)), 0xFFFFFFFFFFFFFFFF, np.uint64)
+        counts = np.zeros(nq, np.uint32)
+        exp = np.full((nq, max(exp_cap, 1)), 0xFFFFFFFFFFFFFFFF, np.uint64)
+        n_exp = np.zeros(nq, np.uint32)
+        lib().orc_graph_search_level_batch(self.h, _p(rows, u32p), nq, target_level, ef, algo, nthreads, _p(keys, u64p),
+                                           _p(counts, u32p), _p(exp, u64p) if exp_cap else None, exp_cap,
+                                           _p(n_exp, u32p) if exp_cap else None)
+        return keys, counts, exp, n_exp
+
     def __del__(self):
         try:
             lib().orc_graph_free(self.h)
         except Exception:
             pass
+
+
+def prune(X, ids, dists, limit, alpha, two_stage):
+    """oracle.c:orc_prune — positions (into ids) kept by the builder's prune rule, in kept order; X contiguous [n x d] f32"""
+    ids = np.ascontiguousarray(ids, np.uint32)
+    dists = np.ascontiguousarray(dists, np.float32)
+    out = np.zeros(max(len(ids), 1), np.uint32)
+    ns = lib().orc_prune(_p(X, f32p), X.shape[1], X.shape[1], _p(ids, u32p), _p(dists, f32p), len(ids), limit, float(alpha),
+                         1 if two_stage else 0, _p(out, u32p))
+    return out[:ns]
 
 
 def synth_features(seed, h, n_clusters, sigma, stream, i0, n, r_int=0):

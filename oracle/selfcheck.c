@@ -23,6 +23,20 @@ int main(void) {
     if (memcmp(k2, keys[0], sizeof k2)) { puts("FAIL: export/import"); return 1; }
     orc_graph *v = orc_vamana_build(X, 600, d, 12, 24, 1.2f, 5);
     orc_graph_search(v, Q, 10, 30, 1, k2, d2, &c2, s2);
+    {
+        uint64_t lk[50], le[8], bk[3 * 50], be[3 * 8]; uint32_t ln, lne, bc[3], bn[3], rows[3] = {1, 700, 1499}, pos[10], pid[10]; float pd[10];
+        orc_graph_search_level(g, Q, 0, 50, 0, lk, &ln, le, 8, &lne);
+        orc_graph_search(g, Q, 50, 50, 0, keys[1], dist[1], &c2, NULL);
+        if (ln != c2 || lne == 0) { puts("FAIL: level search count"); return 1; }
+        for (uint32_t i = 0; i < ln; i++)
+            if ((uint32_t)lk[i] != (uint32_t)keys[1][i]) { puts("FAIL: level search != search at level 0"); return 1; }
+        orc_graph_search_level(g, Q, 99, 50, 0, lk, &ln, le, 8, &lne);
+        if (ln || lne) { puts("FAIL: level above max_level"); return 1; }
+        orc_graph_search_level_batch(g, rows, 3, 1, 50, 0, 2, bk, bc, be, 8, bn);
+        orc_graph_search_level_batch(v, rows, 2, 0, 50, 1, 1, bk, bc, NULL, 0, NULL);
+        for (uint32_t i = 0; i < 10; i++) { pid[i] = (uint32_t)bk[i]; pd[i] = orc_orderable_f32((uint32_t)(bk[i] >> 32)); }
+        if (orc_prune(X, d, d, pid, pd, 10, 4, 1.2f, 1, pos) < 1 || orc_prune(X, d, d, pid, pd, 10, 4, 0.0f, 0, pos) < 1) { puts("FAIL: prune"); return 1; }
+    }
     uint64_t sk[5]; float ss[5]; uint32_t sn; uint8_t mask[(1500 + 7) / 8]; memset(mask, 0x55, sizeof mask);
     orc_scan_topk(X, n, d, Q, 5, 0, mask, sk, ss, &sn);
     uint64_t mk[10]; float md[10]; uint32_t mn;

@@ -246,6 +246,9 @@ def test_vamana_builder_knobs_produce_searchable_graphs(la, po, gpu, monkeypatch
     s = la.BackendSearcher.build_device(la.BackendType.DiskAnn, dX.ptr, n, d, d, R, 48)
     g = s.graph_export()
     assert (g["max_level"] > 0) == ("LEANN_VAMANA_NAV" in knobs) and g["M0"] == R
+    for A in (g["adj0"], g["adjU"]):  # no id twice in a list (a refine pass proposes sources that the target already holds)
+        srt = np.sort(A, axis=1)
+        assert not ((srt[:, 1:] == srt[:, :-1]) & (srt[:, 1:] != 0xFFFFFFFF)).any()
     G = po.Graph.from_arrays(X, g["M"], g["M0"], g["max_level"], g["entry"], g["levels"], g["upper_off"], g["adj0"], g["adjU"])
     gk = _assert_same(po, G, s, Q, 10, 48, algo=1)
     assert recall_at_k(gk, po.exact_topk(X, Q, 10)) >= 0.9
