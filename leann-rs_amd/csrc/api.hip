@@ -247,97 +247,45 @@ size_t leann_internal_effective_complexity(const leann_backend *h, size_t comple
 }
 
 // ---- kernel dispatch --------------------------------------------------------------------------------
-// LDS visited table: 4 workgroups per CU are register-limited anyway, so 32 KiB (8192 slots) per
-// query is free; larger beams take 64 / 128 KiB.  A query that outgrows it moves to the HBM pool.
-static uint32_t pick_hash_bits(uint32_t ef) {
-    if (const int v = leann_knobs().hash_bits) return (uint32_t)v; // test hook: force tiny tables to exercise the HBM pool
-    // measured on 10M x 768: ~20-25 distance evaluations per unit of ef on average, p99.9 ~ 50 x ef.
-    // 4 workgroups per CU need <= 32 KiB tables; a 64 KiB table halves occupancy and throughput, so
-    // beams up to 256 keep the 8 192-slot table and let the ~1 % heaviest queries migrate to HBM.
-    uint32_t want = ef * 24u, b = 13;
-    while ((1u << b) < want && b < 15) b++;
-    return b;
+// Which kernel a call runs is decided by search_plan (search_plan.h); the table below holds every traversal kernel this file compiles
+// — F32, SCREEN, FEAT and FEAT256; the bf16 rows' kernels have a table of their own (search_bf16.hip) —, one row per kernel, the key
+// and the instantiation written from the same template arguments.
+template <int FAMILY, int T, int R, int NW, bool WIDE, bool FILT, bool BUILD>
+static constexpr SearchKernelRow search_row() {
+    SearchKernel k = nullptr;
+    if constexpr (FAMILY == SEARCH_SCREEN) k = beam_search_screen_kernel<T, R>;
+    else if constexpr (FAMILY == SEARCH_F32 && WIDE) k = FILT ? wide_beam_search_filtered_kernel<T, R, NW> : wide_beam_search_kernel<T, R, NW, BUILD>;
+    else if constexpr (FAMILY == SEARCH_F32) k = FILT ? beam_search_filtered_kernel<T, R, NW> : beam_search_kernel<T, R, NW, BUILD>;
+    else if constexpr (FAMILY == SEARCH_FEAT && WIDE) k = FILT ? wide_beam_search_feat_filtered_kernel<T, R, NW> : wide_beam_search_feat_kernel<T, R, NW>;
+    else if constexpr (FAMILY == SEARCH_FEAT) k = FILT ? beam_search_feat_filtered_kernel<T, R, NW> : beam_search_feat_kernel<T, R, NW>;
+    else if constexpr (FAMILY == SEARCH_FEAT256 && WIDE) k = FILT ? wide_beam_search_feat256_filtered_kernel<R, NW> : wide_beam_search_feat256_kernel<R, NW>;
+    else if constexpr (FAMILY == SEARCH_FEAT256) k = FILT ? beam_search_feat256_filtered_kernel<R, NW> : beam_search_feat256_kernel<R, NW>;
+    return {FAMILY, T, R, NW, WIDE, FILT, BUILD, k};
 }
-
-using SearchKernel = void (*)(GraphView, SearchArgs); // every traversal kernel of search.cuh
-static int launch_one(SearchKernel kernel, int nthreads, size_t lds, const GraphView &g, const SearchArgs &a, hipStream_t st) {
-    if (lds > 64 * 1024)
+// stored f32 rows: plain, construction and filtered form of one <T, R, NW>; 16, 8 and 4 waves, wide lists 16 and 4 only
+#define F32_ROW(T, NW, WIDE, FILT, BUILD) search_row<SEARCH_F32, T, search_f32_R(T), NW, WIDE, FILT, BUILD>()
+#define F32_FORMS(T, NW, WIDE) F32_ROW(T, NW, WIDE, false, false), F32_ROW(T, NW, WIDE, false, true), F32_ROW(T, NW, WIDE, true, false)
+#define F32_WIDTH(T) F32_FORMS(T, 16, false), F32_FORMS(T, 8, false), F32_FORMS(T, 4, false), F32_FORMS(T, 16, true), F32_FORMS(T, 4, true)
+// recompute-on rows: plain and filtered, narrow and wide lists, of one <T, R, NW> (FEAT256: <G = R, NW>, T = 1)
+#define FEAT_FORMS(FAMILY, T, R, NW)                                                                                               \
+    search_row<FAMILY, T, R, NW, false, false, false>(), search_row<FAMILY, T, R, NW, false, true, false>(),                       \
+        search_row<FAMILY, T, R, NW, true, false, false>(), search_row<FAMILY, T, R, NW, true, true, false>()
+#define FEAT_WIDTH(T) FEAT_FORMS(SEARCH_FEAT, T, search_feat_R(T), 16), FEAT_FORMS(SEARCH_FEAT, T, search_feat_R(T), 4)
+static int search_kernel(const SearchPlan &p, SearchKernel *out) {
+    static constexpr SearchKernelRow rows[] = {
+        F32_WIDTH(1), F32_WIDTH(2), F32_WIDTH(3), F32_WIDTH(4), F32_WIDTH(6), F32_WIDTH(8), F32_WIDTH(12), F32_WIDTH(16),
+        search_row<SEARCH_SCREEN, 3, LEANN_SCREEN_R3, 4, false, false, false>(), search_row<SEARCH_SCREEN, 6, LEANN_SCREEN_R6, 4, false, false, false>(),
+        FEAT_WIDTH(1), FEAT_WIDTH(2), FEAT_WIDTH(4),
+        FEAT_FORMS(SEARCH_FEAT256, 1, 1, 16), FEAT_FORMS(SEARCH_FEAT256, 1, LEANN_FEAT_G, 4),
+    };
+    return leann_internal_find_kernel(rows, p, out);
+}
+int launch_plan(SearchKernel kernel, const SearchPlan &p, const GraphView &g, const SearchArgs &a, hipStream_t st) {
+    if (p.lds_bytes > 64 * 1024)
         HIP_CHECK_RET(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(kernel, dim3(a.nq), dim3(nthreads), lds, st, g, a);
+    hipLaunchKernelGGL(kernel, dim3(a.nq), dim3(p.NW * 64), p.lds_bytes, st, g, a);
     HIP_CHECK_RET(hipGetLastError());
     return LEANN_OK;
-}
-static int search_lds_checked(const GraphView &g, const SearchArgs &a, size_t *lds, int nw) {
-    *lds = search_lds_bytes(a.ef, std::max(g.M0, g.M), a.hash_bits, a.allow ? a.k : 0u, nw > 4 ? 2u : 1u);
-    if (*lds > 160 * 1024) {
-        leann_set_error("search: complexity %u needs %zu B of LDS per query (> 160 KiB)", a.ef, *lds);
-        return LEANN_ERR_INVALID;
-    }
-    return LEANN_OK;
-}
-
-// Lists of more than 64 ids (HNSW M > 32, DiskANN R > 64) take the wide kernels: two list ids per lane of wave 0 (search.cuh, LW = 2).
-// They exist in the 4- and 16-wave forms only (the 8-wave form's batches, 385..640 queries, run 16 waves): every wide form adds the
-// compile time of a narrow one, and all three doubled that of this file (34 -> 70 s).
-static bool wide_graph(const GraphView &g) { return std::max(g.M0, g.M) > 64; }
-
-template <int T, int R, int NW>
-static int launch_search_NW(const GraphView &g, const SearchArgs &a, hipStream_t st) {
-    size_t lds;
-    if (int rc = search_lds_checked(g, a, &lds, NW)) return rc;
-    SearchKernel k = a.allow ? beam_search_filtered_kernel<T, R, NW> : a.q_rows ? beam_search_kernel<T, R, NW, true> : beam_search_kernel<T, R, NW, false>;
-    if constexpr (NW != 8)
-        if (wide_graph(g))
-            k = a.allow ? wide_beam_search_filtered_kernel<T, R, NW> : a.q_rows ? wide_beam_search_kernel<T, R, NW, true> : wide_beam_search_kernel<T, R, NW, false>;
-    return launch_one(k, NW * 64, lds, g, a, st);
-}
-
-// Waves per query: 4 for throughput batches (4 workgroups per CU hide each other's dependent hops);
-// 16 for small batches, where the chip is mostly idle and the per-hop row fetch is the critical path —
-// all ~40 new rows of a hop are then in flight at once (results are identical: same order, same sums).
-// Rows in flight per wave of the screen kernels: a hi-plane row is half a row's bytes (768-d: 4, 1 536-d: 2 as for whole rows).
-#ifndef LEANN_SCREEN_R3
-#define LEANN_SCREEN_R3 4
-#endif
-#ifndef LEANN_SCREEN_R6
-#define LEANN_SCREEN_R6 2
-#endif
-// `screen`: the handle's split planes are in place (a.x_hi / a.x_lo): the plain throughput form takes the row-screen kernel.  The
-// latency forms, the filtered and the construction searches read whole rows as before.
-template <int T, int R>
-static int launch_search_T(const GraphView &g, const SearchArgs &a, hipStream_t st, bool screen = false) {
-    int nw = a.nq <= 384 ? 16 : a.nq <= 640 ? 8 : 4; // 10M x 768, ef = 56: 16 waves win up to 256 queries, 8 at 512, 4 from 768 on (scripts/exp/batch_sweep.py)
-    if (const int v = leann_knobs().nw) nw = v;
-    if (nw >= 8 && wide_graph(g)) nw = 16; // (no 8-wave wide kernels)
-    if (nw >= 16) return launch_search_NW<T, R, 16>(g, a, st);
-    if (nw >= 8) return launch_search_NW<T, R, 8>(g, a, st);
-    if constexpr (T == 3 || T == 6) {
-        if (screen && !a.allow && !a.q_rows && !wide_graph(g)) {
-            size_t lds;
-            if (int rc = search_lds_checked(g, a, &lds, 4)) return rc;
-            return launch_one(beam_search_screen_kernel<T, T == 3 ? LEANN_SCREEN_R3 : LEANN_SCREEN_R6>, 256, lds, g, a, st);
-        }
-    }
-    return launch_search_NW<T, R, 4>(g, a, st);
-}
-
-template <int T, int R>
-static int launch_search_feat(const GraphView &g, const SearchArgs &a, hipStream_t st) {
-    size_t lds;
-    if (int rc = search_lds_checked(g, a, &lds, a.nq <= 512 ? 16 : 4)) return rc;
-    const bool wide = wide_graph(g), filt = a.allow != nullptr, small = a.nq <= 512; // small batches: 16 waves per query, else 4
-    SearchKernel k;
-    if (T == 1 && g.feat_h == 256 && !leann_knobs().no_feat256) // four rows per wave instruction
-        k = wide ? (small ? (filt ? wide_beam_search_feat256_filtered_kernel<1, 16> : wide_beam_search_feat256_kernel<1, 16>)
-                          : (filt ? wide_beam_search_feat256_filtered_kernel<LEANN_FEAT_G, 4> : wide_beam_search_feat256_kernel<LEANN_FEAT_G, 4>))
-                 : (small ? (filt ? beam_search_feat256_filtered_kernel<1, 16> : beam_search_feat256_kernel<1, 16>)
-                          : (filt ? beam_search_feat256_filtered_kernel<LEANN_FEAT_G, 4> : beam_search_feat256_kernel<LEANN_FEAT_G, 4>));
-    else
-        k = wide ? (small ? (filt ? wide_beam_search_feat_filtered_kernel<T, R, 16> : wide_beam_search_feat_kernel<T, R, 16>)
-                          : (filt ? wide_beam_search_feat_filtered_kernel<T, R, 4> : wide_beam_search_feat_kernel<T, R, 4>))
-                 : (small ? (filt ? beam_search_feat_filtered_kernel<T, R, 16> : beam_search_feat_kernel<T, R, 16>)
-                          : (filt ? beam_search_feat_filtered_kernel<T, R, 4> : beam_search_feat_kernel<T, R, 4>));
-    return launch_one(k, small ? 16 * 64 : 4 * 64, lds, g, a, st);
 }
 
 // recompute-on mode: queries [nq x dims] -> g = W q [nq x feat_h] into the stream's scratch (f32 MFMA, k-ordered chains)
@@ -363,55 +311,34 @@ static int project_queries(leann_backend *h, const float *d_queries, size_t nq, 
 
 int leann_internal_launch_search(leann_backend *h, SearchArgs a, hipStream_t st) {
     if (a.nq == 0) return LEANN_OK;
-    if (h->g.feat_h) {
-        if (a.q_rows) { leann_set_error("recompute-on index: construction searches are not supported"); return LEANN_ERR_UNSUPPORTED; }
-        if (a.ef < a.k) a.ef = a.k;
-        // 520-B rows make this mode latency- rather than bandwidth-bound: favour occupancy (16 KiB visited table ->
-        // 6-8 workgroups per CU) for narrow beams; heavier queries migrate to the HBM pool
-        a.hash_bits = leann_knobs().hash_bits ? pick_hash_bits(a.ef) : (a.ef <= 64 ? 12u : pick_hash_bits(a.ef));
-        int rc = ensure_gpool(h);
-        if (rc) return rc;
-        set_pool_args(h, a);
-        const float *G = nullptr;
-        rc = project_queries(h, a.queries, a.nq, st, &G);
-        if (rc) return rc;
-        a.queries = G;
-        a.ldq = h->g.feat_h;
-        const int T = (int)((h->g.feat_h + 255) / 256);
-        switch (T) {
-            case 1: return launch_search_feat<1, LEANN_FEAT_R1>(h->g, a, st);
-            case 2: return launch_search_feat<2, 6>(h->g, a, st);
-            case 3: case 4: return launch_search_feat<4, 4>(h->g, a, st);
-            default: leann_set_error("recompute-on index: feature width %u > 1024 not supported", h->g.feat_h); return LEANN_ERR_INVALID;
-        }
-    }
-    if (a.ef < a.k) a.ef = a.k; // diskann.rs:54
-    // Rows of up to 512 floats leave registers for 5-7 workgroups per CU where the 32 KiB visited table allows 4, and rows this short
-    // do not hide a hop's dependent phases behind their own transfer: narrow beams take the 16 KiB table (the heaviest queries
-    // move to the HBM pool).  10M rows, ef = 64: 128-d 2.41 -> 3.10 M queries/s, 256-d 2.16 -> 2.72 M, 384-d 1.66 -> 1.85 M, 512-d
-    // unchanged; 768-d and wider are bound by HBM either way and keep the larger table (scripts/exp/dims_sweep.py).
-    a.hash_bits = (h->g.ld <= 512 && a.ef <= 64 && !a.q_rows && !leann_knobs().hash_bits) ? 12u : pick_hash_bits(a.ef);
-    int rc = ensure_gpool(h);
-    if (rc) return rc;
-    set_pool_args(h, a);
-    if (leann_internal_bf16(h)) return leann_internal_launch_search_bf16(h->g, a, st); // kernels and launcher of their own (search_bf16.hip)
     const GraphView &g = h->g;
-    int T = (int)((g.ld + 255) / 256);
-    const bool screen = h->row_screen.load(std::memory_order_relaxed) != 0 && leann_internal_planes_ready(h) && leann_internal_screen_shape(g);
-    if (screen) { a.x_hi = h->x_hi; a.x_lo = h->x_lo; a.ldp = h->ldp; a.screen_ctr = h->screen_ctr; }
-    switch (T) {
-        case 1: return launch_search_T<1, 4>(g, a, st);
-        case 2: return launch_search_T<2, 4>(g, a, st);
-        case 3: return launch_search_T<3, 4>(g, a, st, screen);
-        case 4: return launch_search_T<4, 3>(g, a, st);
-        case 5: case 6: return launch_search_T<6, 2>(g, a, st, screen);
-        case 7: case 8: return launch_search_T<8, 2>(g, a, st);
-        case 9: case 10: case 11: case 12: return launch_search_T<12, 1>(g, a, st); // 3 072-d: text-embedding-3-large (embedding/models.rs:113)
-        case 13: case 14: case 15: case 16: return launch_search_T<16, 1>(g, a, st);
-        default:
-            leann_set_error("search: dims %u > 4096 not supported", g.d);
-            return LEANN_ERR_INVALID;
+    if (a.ef < a.k) a.ef = a.k; // diskann.rs:54
+    SearchShape shape{};
+    shape.ld = g.ld; shape.d = g.d; shape.feat_h = g.feat_h; shape.bf16 = leann_internal_bf16(h); shape.maxdeg = std::max(g.M0, g.M);
+    shape.screen_ready = !g.feat_h && !shape.bf16 && h->row_screen.load(std::memory_order_relaxed) != 0 && leann_internal_planes_ready(h) &&
+                         leann_internal_screen_shape(g);
+    const SearchCall call{a.nq, a.k, a.ef, a.allow != nullptr, a.q_rows != nullptr};
+    const SearchKnobs knobs{leann_knobs().hash_bits, leann_knobs().nw, leann_knobs().no_feat256};
+    const SearchPlan p = search_plan(shape, call, knobs);
+    if (p.err) { leann_set_error("%s", p.msg); return p.err; }
+    a.hash_bits = p.hash_bits;
+    if (int rc = ensure_gpool(h)) return rc;
+    set_pool_args(h, a);
+    if (g.feat_h) { // the walk runs on the projected queries
+        const float *G = nullptr;
+        if (int rc = project_queries(h, a.queries, a.nq, st, &G)) return rc;
+        a.queries = G;
+        a.ldq = g.feat_h;
     }
+    if (p.family == SEARCH_SCREEN) { a.x_hi = h->x_hi; a.x_lo = h->x_lo; a.ldp = h->ldp; a.screen_ctr = h->screen_ctr; }
+    SearchKernel kernel = nullptr;
+    if (int rc = p.family == SEARCH_BF16 ? leann_internal_bf16_kernel(g, p, &kernel) : search_kernel(p, &kernel)) return rc;
+    if (leann_log_enabled(LEANN_LOG_DEBUG)) {
+        char name[96];
+        search_plan_name(p, name, sizeof name);
+        leann_log(LEANN_LOG_DEBUG, "search: %s, hash_bits %u, lds_bytes %zu", name, p.hash_bits, p.lds_bytes);
+    }
+    return launch_plan(kernel, p, g, a, st);
 }
 
 extern "C" int leann_backend_search_batch_device(const leann_backend *hc, const float *d_queries, size_t nq,

@@ -114,7 +114,29 @@ int leann_internal_check_build_args(int backend, size_t graph_degree, size_t com
 // build.hip: leann_backend_build_device (rows borrowed) without cutting the row screen's planes
 int leann_internal_build_device_no_planes(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld, size_t graph_degree,
                                           size_t complexity, int device, uint64_t key_offset, leann_backend **out);
-int leann_internal_launch_search_bf16(const GraphView &g, const SearchArgs &a, hipStream_t st); // search_bf16.hip
+// Kernel tables (api.hip; search_bf16.hip for the bf16 rows' kernels): one row per compiled traversal kernel, keyed by the fields of a
+// SearchPlan (search_plan.h) that name it.  A plan without a row is an error, never a neighbouring kernel.
+using SearchKernel = void (*)(GraphView, SearchArgs); // every traversal kernel of search.cuh and search_bf16.hip
+struct SearchKernelRow {
+    int family, T, R, NW;
+    bool wide, filtered, build;
+    SearchKernel kernel;
+};
+template <size_t N>
+inline int leann_internal_find_kernel(const SearchKernelRow (&rows)[N], const SearchPlan &p, SearchKernel *out) {
+    for (const SearchKernelRow &r : rows)
+        if (r.family == p.family && r.T == p.T && r.R == p.R && r.NW == p.NW && r.wide == p.wide && r.filtered == p.filtered && r.build == p.build) {
+            *out = r.kernel;
+            return LEANN_OK;
+        }
+    char name[96];
+    search_plan_name(p, name, sizeof name);
+    leann_set_error("search: no kernel %s is compiled", name);
+    return LEANN_ERR_INVALID;
+}
+int leann_internal_bf16_kernel(const GraphView &g, const SearchPlan &p, SearchKernel *out); // search_bf16.hip: checks the row store too
+// the one launch of a traversal kernel (api.hip): > 64 KiB of LDS is asked for first; grid = a.nq workgroups of p.NW waves
+int launch_plan(SearchKernel kernel, const SearchPlan &p, const GraphView &g, const SearchArgs &a, hipStream_t st);
 bool leann_internal_screen_shape(const GraphView &g);      // the row widths and list lengths the screen kernel is compiled for
 void leann_internal_sync_planes(leann_backend *h);          // (re)build the planes of a plain handle; logs and returns on failure
 bool leann_internal_planes_ready(const leann_backend *h);   // planes present and cut from the rows h->g names now

@@ -23,6 +23,7 @@
 #pragma once
 #include "common.cuh"
 #include "row_screen.h"
+#include "search_plan.h"
 
 struct GraphView {
     const float *X;            // [n x ld] rows, 16-byte aligned, zero padded
@@ -365,15 +366,7 @@ struct SearchLds {
                      // [6]=1 if the target level's seed is allowed (filtered) [8],[9]=n_new (by hop parity)
                      // [10]=rows the workgroup's waves ruled out on their hi plane (SCREEN); [7], [11]..[15] free
 };
-// kf = result-list length of a filtered search (0: unfiltered)
-// nbuf = 2 for the latency form of the hop loop (NW > 4: s_key / s_new / s_keyR per hop parity), 1 for the throughput form
-__host__ __device__ inline size_t search_lds_bytes(uint32_t ef, uint32_t maxdeg, uint32_t hash_bits, uint32_t kf = 0, uint32_t nbuf = 2) {
-    size_t efp = (ef + 1) & ~1u;
-    size_t b = 2 * efp * 8 + nbuf * ((size_t)maxdeg + 8) * 8 + nbuf * (size_t)maxdeg * 4 + 16 * 4; // s_key carries 8 sentinel slots
-    b = (b + 15) & ~(size_t)15;
-    if (kf) b += 2 * (size_t)((kf + 1) & ~1u) * 8 + nbuf * ((size_t)maxdeg + 8) * 8;
-    return b + ((size_t)1 << hash_bits) * 4;
-}
+// (its size: search_lds_bytes, search_plan.h)
 
 // G16 (recompute-on rows of 256 features only): phase C evaluates four rows per wave instruction (group_dist_rows_feat256), R = groups
 // in flight per wave.
@@ -1261,17 +1254,11 @@ __global__ void __launch_bounds__(NW * 64) beam_search_feat_filtered_kernel(Grap
 #ifndef LEANN_FEAT_OCC
 #define LEANN_FEAT_OCC 8
 #endif
-#ifndef LEANN_FEAT_R1
-#define LEANN_FEAT_R1 5
-#endif
 // recompute-on rows of exactly 256 features: four rows per wave instruction, G groups in flight per wave (G16 above).  Throughput
 // shape = 7 workgroups per CU x 1 group (72 registers, no spills; 16 rows per workgroup and round): 4.5 M queries/s at ef = 52 =
 // 7.9 G random rows/s, against the 10 G rows/s scripts/micro/gather_bw.hip measures as the memory system's ceiling for this access
 // shape.  6 workgroups x 2 groups (a typical hop's ~26 unseen neighbours in ONE round) is 2 % behind, 8 workgroups (64 registers) spill:
 // 3.7-3.9 M, 6 x 3 groups 3.5 M (scripts/exp/feat256_shape.sh).
-#ifndef LEANN_FEAT_G
-#define LEANN_FEAT_G 1
-#endif
 #ifndef LEANN_FEAT256_OCC
 #define LEANN_FEAT256_OCC 7
 #endif

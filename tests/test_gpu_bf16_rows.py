@@ -5,8 +5,8 @@ f32 index over Xr = w(r(X)) with the same graph.  So every comparison here is bi
 n_dist_evals, n_hops_base, n_hops_upper — against the oracle walking the same graph on Xr, and the handles are made from the UNROUNDED
 X, so that the device rounding kernel is on the path.
 
-Dispatch, read off leann_internal_launch_search_bf16 / launch_bf16_T (search_bf16.hip): T = ceil(ld / 256) picks the kernel width as
-api.hip does for f32 rows; nq <= 512 runs 16 waves per query, larger batches 4, each with its own rows in flight per wave
+Dispatch, as csrc/search_plan.h decides it (family BF16; held to hand-written plans by tests/test_cpu_search_plan.py): T = ceil(ld / 256)
+picks the kernel width as for f32 rows; nq <= 512 runs 16 waves per query, larger batches 4, each with its own rows in flight per wave
 (ROWS_IN_FLIGHT below); an allow mask picks the filtered kernel; lists of more than 64 ids the wide kernels.
 
     ld chunks  T    R (4 waves / 16 waves)   d in this file (n)
@@ -37,7 +37,7 @@ NQ = 704  # > 512: the 4-wave form
 M, EFC = 8, 48
 WIDTHS = {128: 2000, 260: 2000, 768: 1500, 900: 1500, 1100: 1500, 1600: 1200, 2820: 800, 3400: 800}  # d -> n
 ROWS_IN_FLIGHT = {1: (8, 4), 2: (8, 4), 3: (8, 4), 4: (6, 4), 6: (4, 3), 8: (4, 2), 12: (2, 1), 16: (2, None)}  # T -> R of the 4- and the
-# 16-wave form, launch_bf16_T<T, R4, R16> (search_bf16.hip); None: that width has no 16-wave form
+# 16-wave form (search_plan.h: search_bf16_R4 / _R16); None: that width has no 16-wave form
 UNSUPPORTED, INVALID = 5, 1
 
 

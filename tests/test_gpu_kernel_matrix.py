@@ -1,6 +1,6 @@
 """-m gpu: every narrow beam-search kernel api.hip can launch, against the oracle walk, bit for bit.
 
-Dispatch, read off leann_internal_launch_search / launch_search_T / launch_search_NW / launch_search_feat (api.hip).  Stored f32 rows:
+Dispatch, as csrc/search_plan.h decides it (its rules are held to hand-written plans by tests/test_cpu_search_plan.py).  Stored f32 rows:
 T = ceil(ld / 256) picks <T, R> (R rows in flight per wave); the batch picks NW = 16 (nq <= 384), 8 (<= 640) or 4 waves per query
 (LEANN_DEBUG_NW overrides); an allow mask picks the filtered kernel.  "nat" = test_natural_dispatch, "nw" = test_forced_wave_counts,
 "filt" = test_filtered, "vam" = test_diskann_leg, each parametrised by the row width d.
@@ -17,7 +17,7 @@ T = ceil(ld / 256) picks <T, R> (R rows in flight per wave); the batch picks NW 
     9..12      <12, 1>         2820 (4 floats in chunk 11) nat, nw                                  filt[2820]
     13..16     <16, 1>         3400 (T = 14: two padded)  nat, nw                                   filt[3400]
 
-  * hash_bits: 12 (4096 slots) when ld <= 512 and ef <= 64, else pick_hash_bits(ef) = 13 here: test_small_visited_table (d = 384,
+  * hash_bits: 12 (4096 slots) when ld <= 512 and ef <= 64, else pick(ef) = 13 here: test_small_visited_table (d = 384,
     ef 64 / 65; LEANN_DEBUG_HASH_BITS=8 moves every query to the HBM pool inside the <2, 4, 16> and <2, 4, 4> kernels).
   * batch thresholds 384 | 385 and 640 | 641: test_batch_size_thresholds (d = 128).
   * beam_search_kernel<T,R,NW,true> (BUILD: the query is a stored row, SearchArgs::q_rows): launched by the on-device builder only
@@ -29,7 +29,7 @@ T = ceil(ld / 256) picks <T, R> (R rows in flight per wave); the batch picks NW 
   * beam_search_screen_kernel<3, 4> / <6, 2> (split planes, 4-wave unfiltered batches): test_gpu_row_screen.py, whose fixture dims
     520, 700, 768 run <3, 4> and 1100, 1280 (T = 5 in the 6-kernel), 1536 run <6, 2>.
 
-Recompute-on graphs (bf16 feature rows, launch_search_feat<T, R>; 16 waves for nq <= 512, else 4; "rc" = test_recompute_on_wide_features):
+Recompute-on graphs (bf16 feature rows, family FEAT / FEAT256 of search_plan.h; 16 waves for nq <= 512, else 4; "rc" = test_recompute_on_wide_features):
 
     feat_h      kernel                                             case
     <= 256      beam_search_feat[_filtered]_kernel<1, R1, 16|4>    rc[100] (row_bytes 208, inline norm), nq 64 / 704, plain + bitmap
@@ -60,7 +60,7 @@ M, EFC = 8, 48
 WIDTHS = {128: 2000, 384: 2000, 260: 2000, 768: 1500, 1024: 1500, 900: 1500, 1100: 1500, 1536: 1200, 2048: 1200, 1600: 1200,
           2820: 800, 3400: 800}  # d -> n
 PADDED_CHUNKS = {1100: 1, 1600: 1, 3400: 2}  # T = 5 in the 6-kernel, 7 in the 8-kernel, 14 in the 16-kernel
-ROWS_IN_FLIGHT = {1: 4, 2: 4, 3: 4, 4: 3, 6: 2, 8: 2, 12: 1, 16: 1}  # R of launch_search_T<T, R> (api.hip)
+ROWS_IN_FLIGHT = {1: 4, 2: 4, 3: 4, 4: 3, 6: 2, 8: 2, 12: 1, 16: 1}  # R by T of the stored-f32 kernels (search_plan.h: search_f32_R)
 
 
 def _kernel_T(d):
