@@ -501,6 +501,9 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
         // batches <= 512): wave 0 runs phase B of hop h + 1 right behind phase E, UNDER the merge of hop h — two barriers per hop, single
         // query 0.365 -> 0.32 ms.  With the chip saturated the adjacency round trip outlasts the merge either way and the leaner wave 0
         // of the throughput form is faster (recompute-on search: 3.05 against 2.98 M queries/s; hnsw10m equal; scripts/exp/ab.sh).
+        // Every phase is stated once, in a fragment file included by both forms (hop_adj.cuh B, hop_migrate.cuh the table migration,
+        // hop_rows.cuh C, hop_select.cuh E, hop_merge.cuh D, hop_rmerge.cuh the filtered R list): what remains here, and all the two forms
+        // differ in, is where phase B sits, the parity of its buffers, the barriers, and the row screen (throughput form only).
         constexpr bool EARLY_B = NW > 4;
         if constexpr (!EARLY_B) {
             // Adjacency list of the NEXT node to expand, LW neighbour ids per lane of wave 0 (lists hold at most 64 LW ids).  The load is
@@ -521,37 +524,10 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
     #endif
                 // ---- phase B: adjacency list through the visited table (wave 0) ------------------
                 if (wave == 0) {
-                    const uint32_t node = key_id(Wc[sel]);
-                    if (za->out_expanded && lv == (int)a.target_level && lane == 0 && hop < za->exp_cap)
-                        za->out_expanded[(size_t)qi * za->exp_cap + hop] = ((Wc[sel] >> 32) << 32) | node;
-                    uint32_t n_new = 0;
-                    bool ovf = (n_vis + deg > vis_limit);
-                    if (!ovf) {
-                        const uint32_t e = e_pref; // this node's list (a hop redone after a table migration reads the same register again)
-                        bool isnew = false;
-                        if (e != LEANN_EMPTY) isnew = hbm ? vis_insert_hbm(gtab, gbits, gen, e) : vis_insert_lds(table, hbits, e);
-                        unsigned long long m = __ballot(isnew);
-                        uint32_t pos = __popcll(m & ((1ull << lane) - 1ull));
-                        if (isnew) s.s_new[pos] = e;
-                        n_new = __popcll(m);
-                        if constexpr (LW == 2) { // ids 64..127: a second ballot, compacted behind the first half's unseen ids
-                            const uint32_t e1 = e_pref1;
-                            bool isnew1 = false;
-                            if (e1 != LEANN_EMPTY) isnew1 = hbm ? vis_insert_hbm(gtab, gbits, gen, e1) : vis_insert_lds(table, hbits, e1);
-                            const unsigned long long m1 = __ballot(isnew1);
-                            if (isnew1) s.s_new[n_new + __popcll(m1 & ((1ull << lane) - 1ull))] = e1;
-                            n_new += __popcll(m1);
-                        }
-                    }
-                    n_vis += n_new;
-                    n_evals += n_new;
-                    if (!ovf) { if (lv == 0) hops0++; else hopsU++; }
-                    if (lane < 8) s.s_key[n_new + lane] = ~0ull; // sentinels: the merge scans keys 8 at a time
-                    if (filt_level && lane < 8) s_keyR[n_new + lane] = ~0ull;
-                    if (lane == 0) {
-                        s.misc[0] = n_new;
-                        if (ovf) s.misc[3] = 1;
-                    }
+                    constexpr uint32_t p = 0;
+                    const uint64_t ckey = Wc[sel];
+                    const uint32_t hidx = hop;
+                    #include "hop_adj.cuh"
                 }
     #ifdef LEANN_STAMPS
                 const uint64_t stB = __builtin_amdgcn_s_memtime();
@@ -563,74 +539,14 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
                 const uint32_t table_full = uni(s.misc[3]);
                 if (table_full) {
                     // Table full: move the visited set one level up (LDS -> pool 1 -> pool 2) and redo this hop.
-                    const uint32_t next = hbm + 1;
-                    if (next > 2 || (next == 2 && !za->gpool2)) { aborted = true; break; } // defensive: see the pool comment above
-                    __syncthreads(); // every thread has read the flag before it is cleared
-                    if (tid == 0) {
-                        uint32_t *locks = next == 1 ? za->gpool_lock : za->gpool2_lock;
-                        const uint32_t ntab = next == 1 ? za->gpool_tables : za->gpool2_tables;
-                        uint32_t t = atomicAdd(&za->gpool_ctr[next == 1 ? 0 : 2], 1u), slot;
-                        for (uint32_t i = 0;; i++) { // holders never wait for anything, so a table always comes free
-                            slot = (t + i) % ntab;
-                            if (atomicCAS(&locks[slot], 0u, 1u) == 0u) break;
-                            if ((i % ntab) == ntab - 1) __builtin_amdgcn_s_sleep(32);
-                        }
-                        s.misc[4] = slot;
-                        if (!hbm) s.misc[5] = atomicAdd(&za->gpool_ctr[1], 1u) + 1u; // pool 1 -> 2 keeps the generation
-                        s.misc[3] = 0;
-                    }
-                    __syncthreads();
-                    const uint32_t nslot = uni(s.misc[4]);
-                    const uint32_t nbits = next == 1 ? za->gpool_bits : za->gpool2_bits;
-                    unsigned long long *ntab_p = (next == 1 ? za->gpool : za->gpool2) + ((size_t)nslot << nbits);
-                    if (!hbm) {
-                        gen = uni(s.misc[5]);
-                        for (uint32_t i = tid; i < hsize; i += NW * 64) {
-                            uint32_t e = table[i];
-                            if (e != LEANN_EMPTY) vis_insert_hbm(ntab_p, nbits, gen, e);
-                        }
-                    } else {
-                        for (uint32_t i = tid; i < (1u << gbits); i += NW * 64) {
-                            const unsigned long long cur = __hip_atomic_load(&gtab[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            if ((uint32_t)(cur >> 32) == gen) vis_insert_hbm(ntab_p, nbits, gen, (uint32_t)cur);
-                        }
-                        __syncthreads(); // every probe of the old table has returned
-                        if (tid == 0) atomicExch(&za->gpool_lock[gslot], 0u);
-                    }
-                    gtab = ntab_p;
-                    gbits = nbits;
-                    gslot = nslot;
-                    hbm = next;
-                    vis_limit = (1u << gbits) - (1u << (gbits - 2));
-                    __syncthreads();
+                    #include "hop_migrate.cuh"
                     continue;
                 }
                 const uint32_t n_new = uni(s.misc[0]);
+                uint64_t *const skey = s.s_key, *const skeyR = s_keyR; // the names the shared phases (hop_*.cuh) use;
+                const uint32_t *const snew = s.s_new;                  // the latency form has one of each per parity
                 // ---- phase C: stream the new rows, R in flight per wave ------------------------------
-                if constexpr (G16) {
-                    for (uint32_t jb = 0; jb < n_new; jb += NW * 4 * R) {
-                        uint32_t ids[R], jj[R], abyte[R];
-                        bool valid[R];
-                        float dd[R];
-    #pragma unroll
-                        for (int r = 0; r < R; r++) {
-                            jj[r] = jb + (uint32_t)(r * NW + wave) * 4u + (uint32_t)(lane >> 4);
-                            valid[r] = jj[r] < n_new;
-                            ids[r] = valid[r] ? s.s_new[jj[r]] : 0u;
-                            abyte[r] = (filt_level && valid[r] && (lane & 15) == 15) ? allow[ids[r] >> 3] : 0u;
-                        }
-                        group_dist_rows_feat256<R>(qa, qb, reinterpret_cast<const char *>(g.X), g.row_bytes, ids, valid, lane, dd, g.norms);
-                        if ((lane & 15) == 15) {
-    #pragma unroll
-                            for (int r = 0; r < R; r++)
-                                if (valid[r]) {
-                                    const uint64_t key = make_key(dd[r], ids[r]);
-                                    s.s_key[jj[r]] = key;
-                                    if (filt_level) s_keyR[jj[r]] = ((abyte[r] >> (ids[r] & 7u)) & 1u) ? key : ~0ull;
-                                }
-                        }
-                    }
-                } else if constexpr (SCREEN) {
+                if constexpr (SCREEN) {
                     const bool armed = wsize == ef_l; // a full beam: its last entry is the distance to beat
                     const float worst = orderable_f32(uni((uint32_t)(Wc[wsize - 1] >> 32)));
                     for (uint32_t j0 = wave; j0 < n_new; j0 += NW * R) {
@@ -650,35 +566,8 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
                                 if (r < nrows) s.s_key[j0 + r * NW] = make_key(dd[r], ids[r]);
                         }
                     }
-                } else
-                for (uint32_t j0 = wave; j0 < n_new; j0 += NW * R) {
-                    uint32_t ids[R];
-                    float dd[R];
-                    int nrows = 0;
-    #pragma unroll
-                    for (int r = 0; r < R; r++) {
-                        uint32_t j = j0 + r * NW;
-                        if (j < n_new) { ids[r] = s.s_new[j]; nrows = r + 1; }
-                    }
-                    uint32_t abyte = 0, abit = 0;
-                    if (filt_level && lane < R && j0 + lane * NW < n_new) { // lane r fetches row r's allow bit alongside the rows
-                        const uint32_t e = s.s_new[j0 + lane * NW];
-                        abyte = allow[e >> 3];
-                        abit = e & 7u;
-                    }
-                    if (FEAT) wave_dist_rows_feat<T, R>(q, reinterpret_cast<const char *>(g.X), g.row_bytes, g.feat_h, ids, nrows, lane, dd, g.norms);
-                    else if constexpr (BF16) wave_dist_rows_bf16<T, R>(q, reinterpret_cast<const uint16_t *>(g.X), g.row_bytes >> 1, ids, nrows, lane, dd);
-                    else wave_dist_rows<T, R>(q, g.X, g.ld, ids, nrows, lane, dd);
-                    const unsigned long long amask = FILT ? __ballot((abyte >> abit) & 1u) : 0ull;
-                    if (lane == 0) {
-    #pragma unroll
-                        for (int r = 0; r < R; r++)
-                            if (r < nrows) {
-                                const uint64_t key = make_key(dd[r], ids[r]);
-                                s.s_key[j0 + r * NW] = key;
-                                if (filt_level) s_keyR[j0 + r * NW] = ((amask >> r) & 1ull) ? key : ~0ull;
-                            }
-                    }
+                } else {
+                    #include "hop_rows.cuh"
                 }
     #ifdef LEANN_STAMPS
                 const uint64_t stC = __builtin_amdgcn_s_memtime();
@@ -687,114 +576,16 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
     #ifdef LEANN_STAMPS
                 const uint64_t stB2 = __builtin_amdgcn_s_memtime();
     #endif
-                // ---- phase E (wave 0): the next candidate, known before the merge -------------------------------------
-                // The merged beam's first unexpanded entry is the smaller of (a) the first unexpanded entry of the OLD beam other than
-                // the one just expanded and (b) the smallest new key; its index in the merged beam is the number of keys below it.
-                // Same entry, same index as a scan of the merged list would give — but available one merge earlier, so wave 0 issues
-                // the next hop's adjacency load now and the other waves merge meanwhile.
                 uint32_t *next_slot = &s.misc[1 + (hop & 1)];
                 const uint32_t n_pad = (n_new + 7) & ~7u;
                 if (wave == 0) {
-                    uint32_t u = LEANN_EMPTY;
-                    for (uint32_t base = 0; base < wsize && u == LEANN_EMPTY; base += 64) {
-                        const uint32_t i = base + lane;
-                        const unsigned long long m = __ballot(i < wsize && i != sel && !(Wc[i] & 1ull));
-                        if (m) u = base + (uint32_t)__ffsll((long long)m) - 1u;
-                    }
-                    const uint64_t c_old = u != LEANN_EMPTY ? Wc[u] : ~0ull;
-                    const uint64_t kj = (uint32_t)lane < n_new ? s.s_key[lane] : ~0ull; // n_new <= 64 LW: LW keys per lane
-                    const uint64_t kj1 = LW == 2 && (uint32_t)lane + 64u < n_new ? s.s_key[lane + 64] : ~0ull;
-                    const uint64_t km = LW == 2 ? min(kj, kj1) : kj;
-                    const uint32_t hi = wave_min_u32((uint32_t)(km >> 32));
-                    const uint32_t lo = wave_min_u32((uint32_t)(km >> 32) == hi ? (uint32_t)km : 0xFFFFFFFFu);
-                    const uint64_t c_new = n_new ? (((uint64_t)hi << 32) | lo) : ~0ull;
-                    uint32_t next = LEANN_EMPTY, cnode = 0;
-                    if (c_old != ~0ull || c_new != ~0ull) {
-                        uint32_t rank;
-                        if ((c_old >> 1) < (c_new >> 1)) {
-                            rank = u + (uint32_t)__popcll(__ballot((kj >> 1) < (c_old >> 1)));
-                            if constexpr (LW == 2) rank += (uint32_t)__popcll(__ballot((kj1 >> 1) < (c_old >> 1)));
-                            cnode = key_id(c_old);
-    #ifdef LEANN_STAMPS
-                            stamp[7] += 1;
-    #endif
-                        } else {
-                            rank = 0;
-                            for (uint32_t base = 0; base < wsize; base += 64) {
-                                const uint32_t i = base + lane;
-                                rank += (uint32_t)__popcll(__ballot(i < wsize && (Wc[i] >> 1) < (c_new >> 1)));
-                            }
-                            cnode = key_id(c_new);
-                        }
-                        if (rank < ef_l) next = rank;
-                    }
-                    if (lane == 0) *next_slot = next;
-                    if (next != LEANN_EMPTY) { // in flight across the merge and barrier B3
-                        e_pref = (uint32_t)lane < deg ? adj_list(adj_base, upoff_p, deg, lv, cnode)[lane] : LEANN_EMPTY;
-                        if constexpr (LW == 2) e_pref1 = (uint32_t)lane + 64u < deg ? adj_list(adj_base, upoff_p, deg, lv, cnode)[lane + 64] : LEANN_EMPTY;
-                    }
+                    // ---- phase E: the next candidate, known before the merge; its adjacency load is issued now ----------------
+                    #include "hop_select.cuh"
                 } else {
-                    // ---- phase D (waves 1 .. NW-1): merge by rank into the other buffer ---------------------------------
-                    // One work item per old entry (rank = index + #new keys below it) and per new key (rank = #old below it, by
-                    // binary search, + #new below it); the scan over the new keys reads 16 B per LDS instruction, 8 keys per
-                    // unrolled step, so the loads pipeline instead of paying one LDS latency per key.
-                    const ulonglong2 *kp = reinterpret_cast<const ulonglong2 *>(s.s_key);
-                    for (uint32_t it = tid - 64; it < wsize + n_new; it += (NW - 1) * 64) {
-                        const bool isW = it < wsize;
-                        uint64_t k = isW ? Wc[it] : s.s_key[it - wsize];
-                        if (isW && it == sel) k |= 1ull;
-                        const uint64_t kk = k >> 1;
-                        uint32_t cnt = 0;
-    #pragma unroll 4
-                        for (uint32_t j = 0; j < n_pad; j += 2) {
-                            const ulonglong2 v = kp[j >> 1];
-                            cnt += ((v.x >> 1) < kk) + ((v.y >> 1) < kk);
-                        }
-                        uint32_t rank = isW ? it + cnt : cnt;
-                        if (!isW) {
-                            uint32_t lo = 0, hi = wsize;
-                            while (lo < hi) {
-                                uint32_t mid = (lo + hi) >> 1;
-                                if ((Wc[mid] >> 1) < kk) lo = mid + 1; else hi = mid;
-                            }
-                            rank += lo;
-                        }
-                        if (rank < ef_l) Wn[rank] = k;
-                    }
+                    #include "hop_merge.cuh"
                 }
                 if (filt_level) {
-                    // R <- kf best of R ∪ {allowed new keys}: the same merge by rank, on the blanked copy of the new keys.
-                    // Skipped (uniformly) when no allowed new key beats the current kf-th.
-                    uint64_t *Rc = R0 + rcur * kfp, *Rn = R0 + (rcur ^ 1) * kfp;
-                    const uint64_t thr = rsize == kf ? Rc[kf - 1] : ~0ull;
-                    uint32_t n_in = 0;
-                    for (uint32_t j = 0; j < n_new; j += 64) n_in += __popcll(__ballot(j + lane < n_new && s_keyR[j + lane] < thr));
-                    if (n_in) {
-                        const ulonglong2 *kr = reinterpret_cast<const ulonglong2 *>(s_keyR);
-                        for (uint32_t it = tid; it < rsize + n_new; it += NW * 64) {
-                            const bool isR = it < rsize;
-                            const uint64_t k = isR ? Rc[it] : s_keyR[it - rsize];
-                            if (k >= thr && !isR) continue; // disallowed, or cannot enter a full list
-                            uint32_t cnt = 0;
-    #pragma unroll 4
-                            for (uint32_t j = 0; j < n_pad; j += 2) {
-                                const ulonglong2 v = kr[j >> 1];
-                                cnt += (v.x < k) + (v.y < k);
-                            }
-                            uint32_t rank = isR ? it + cnt : cnt;
-                            if (!isR) {
-                                uint32_t lo = 0, hi = rsize;
-                                while (lo < hi) {
-                                    uint32_t mid = (lo + hi) >> 1;
-                                    if (Rc[mid] < k) lo = mid + 1; else hi = mid;
-                                }
-                                rank += lo;
-                            }
-                            if (rank < kf) Rn[rank] = k;
-                        }
-                        rsize = min(rsize + n_in, kf);
-                        rcur ^= 1;
-                    }
+                    #include "hop_rmerge.cuh"
                 }
     #ifdef LEANN_STAMPS
                 const uint64_t stD = __builtin_amdgcn_s_memtime();
@@ -825,39 +616,7 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
             const uint32_t *const adj_base = lv == 0 ? adj0_p : adjU_p; // (as VALUES: an address-select between struct members puts the by-value GraphView in scratch)
             uint32_t e_pref = LEANN_EMPTY, e_pref1 = LEANN_EMPTY; // e_pref1: ids 64..127 (LW = 2)
             auto phase_b = [&](uint32_t p, uint64_t ckey, uint32_t hidx) __attribute__((always_inline)) { // wave 0
-                uint64_t *skey = s.s_key + p * kstride;
-                uint32_t *snew = s.s_new + p * maxdeg;
-                const uint32_t node = key_id(ckey);
-                if (za->out_expanded && lv == (int)a.target_level && lane == 0 && hidx < za->exp_cap)
-                    za->out_expanded[(size_t)qi * za->exp_cap + hidx] = ((ckey >> 32) << 32) | node;
-                uint32_t n_new = 0;
-                const bool ovf = (n_vis + deg > vis_limit);
-                if (!ovf) {
-                    const uint32_t e = e_pref; // (a hop redone after a table migration reads the same register again)
-                    bool isnew = false;
-                    if (e != LEANN_EMPTY) isnew = hbm ? vis_insert_hbm(gtab, gbits, gen, e) : vis_insert_lds(table, hbits, e);
-                    const unsigned long long m = __ballot(isnew);
-                    const uint32_t pos = __popcll(m & ((1ull << lane) - 1ull));
-                    if (isnew) snew[pos] = e;
-                    n_new = __popcll(m);
-                    if constexpr (LW == 2) { // ids 64..127: a second ballot, compacted behind the first half's unseen ids
-                        const uint32_t e1 = e_pref1;
-                        bool isnew1 = false;
-                        if (e1 != LEANN_EMPTY) isnew1 = hbm ? vis_insert_hbm(gtab, gbits, gen, e1) : vis_insert_lds(table, hbits, e1);
-                        const unsigned long long m1 = __ballot(isnew1);
-                        if (isnew1) snew[n_new + __popcll(m1 & ((1ull << lane) - 1ull))] = e1;
-                        n_new += __popcll(m1);
-                    }
-                }
-                n_vis += n_new;
-                n_evals += n_new;
-                if (!ovf) { if (lv == 0) hops0++; else hopsU++; }
-                if (lane < 8) skey[n_new + lane] = ~0ull; // sentinels: the merge scans keys 8 at a time
-                if (filt_level && lane < 8) (s_keyR + p * kstride)[n_new + lane] = ~0ull;
-                if (lane == 0) {
-                    s.misc[8 + p] = n_new;
-                    if (ovf) s.misc[3] = 1;
-                }
+                #include "hop_adj.cuh"
             };
             if (wave == 0) {
                 e_pref = (uint32_t)lane < deg ? adj_list(adj_base, upoff_p, deg, lv, key_id(best))[lane] : LEANN_EMPTY;
@@ -873,46 +632,7 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
 #endif
                 if (uni(s.misc[3])) {
                     // Table full: move the visited set one level up (LDS -> pool 1 -> pool 2), then wave 0 prepares this hop again.
-                    const uint32_t next = hbm + 1;
-                    if (next > 2 || (next == 2 && !za->gpool2)) { aborted = true; break; } // defensive: see the pool comment above
-                    __syncthreads(); // every thread has read the flag before it is cleared
-                    if (tid == 0) {
-                        uint32_t *locks = next == 1 ? za->gpool_lock : za->gpool2_lock;
-                        const uint32_t ntab = next == 1 ? za->gpool_tables : za->gpool2_tables;
-                        uint32_t t = atomicAdd(&za->gpool_ctr[next == 1 ? 0 : 2], 1u), slot;
-                        for (uint32_t i = 0;; i++) { // holders never wait for anything, so a table always comes free
-                            slot = (t + i) % ntab;
-                            if (atomicCAS(&locks[slot], 0u, 1u) == 0u) break;
-                            if ((i % ntab) == ntab - 1) __builtin_amdgcn_s_sleep(32);
-                        }
-                        s.misc[4] = slot;
-                        if (!hbm) s.misc[5] = atomicAdd(&za->gpool_ctr[1], 1u) + 1u; // pool 1 -> 2 keeps the generation
-                        s.misc[3] = 0;
-                    }
-                    __syncthreads();
-                    const uint32_t nslot = uni(s.misc[4]);
-                    const uint32_t nbits = next == 1 ? za->gpool_bits : za->gpool2_bits;
-                    unsigned long long *ntab_p = (next == 1 ? za->gpool : za->gpool2) + ((size_t)nslot << nbits);
-                    if (!hbm) {
-                        gen = uni(s.misc[5]);
-                        for (uint32_t i = tid; i < hsize; i += NW * 64) {
-                            uint32_t e = table[i];
-                            if (e != LEANN_EMPTY) vis_insert_hbm(ntab_p, nbits, gen, e);
-                        }
-                    } else {
-                        for (uint32_t i = tid; i < (1u << gbits); i += NW * 64) {
-                            const unsigned long long cur_e = __hip_atomic_load(&gtab[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            if ((uint32_t)(cur_e >> 32) == gen) vis_insert_hbm(ntab_p, nbits, gen, (uint32_t)cur_e);
-                        }
-                        __syncthreads(); // every probe of the old table has returned
-                        if (tid == 0) atomicExch(&za->gpool_lock[gslot], 0u);
-                    }
-                    gtab = ntab_p;
-                    gbits = nbits;
-                    gslot = nslot;
-                    hbm = next;
-                    vis_limit = (1u << gbits) - (1u << (gbits - 2));
-                    __syncthreads();
+                    #include "hop_migrate.cuh"
                     if (wave == 0) phase_b(par, Wc[sel], hop);
                     __syncthreads();
                     continue;
@@ -922,81 +642,7 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
                 const uint32_t *const snew = s.s_new + par * maxdeg;
                 uint64_t *const skeyR = s_keyR + par * kstride;
                 // ---- phase C: stream the new rows, R in flight per wave ------------------------------
-                if constexpr (G16) {
-                    for (uint32_t jb = 0; jb < n_new; jb += NW * 4 * R) {
-                        uint32_t ids[R], jj[R], abyte[R];
-                        bool valid[R];
-                        float dd[R];
-#pragma unroll
-                        for (int r = 0; r < R; r++) {
-                            jj[r] = jb + (uint32_t)(r * NW + wave) * 4u + (uint32_t)(lane >> 4);
-                            valid[r] = jj[r] < n_new;
-                            ids[r] = valid[r] ? snew[jj[r]] : 0u;
-                            abyte[r] = (filt_level && valid[r] && (lane & 15) == 15) ? allow[ids[r] >> 3] : 0u;
-                        }
-#ifndef LEANN_NO_ADJ_TOUCH
-                        // adjacency lists of the rows being evaluated (see the row-per-wave form below): lanes 12, 13 of a row touch
-                        uint32_t touch = 0;
-                        if (lv == 0 && valid[0] && (lane & 14) == 12 && (uint32_t)(lane & 1) * 32u < deg)
-                            touch = adj0_p[(size_t)ids[0] * deg + (uint32_t)(lane & 1) * 32u];
-#endif
-                        group_dist_rows_feat256<R>(qa, qb, reinterpret_cast<const char *>(g.X), g.row_bytes, ids, valid, lane, dd, g.norms);
-#ifndef LEANN_NO_ADJ_TOUCH
-                        asm volatile("" ::"v"(touch));
-#endif
-                        if ((lane & 15) == 15) {
-#pragma unroll
-                            for (int r = 0; r < R; r++)
-                                if (valid[r]) {
-                                    const uint64_t key = make_key(dd[r], ids[r]);
-                                    skey[jj[r]] = key;
-                                    if (filt_level) skeyR[jj[r]] = ((abyte[r] >> (ids[r] & 7u)) & 1u) ? key : ~0ull;
-                                }
-                        }
-                    }
-                } else
-                for (uint32_t j0 = wave; j0 < n_new; j0 += NW * R) {
-                    uint32_t ids[R];
-                    float dd[R];
-                    int nrows = 0;
-#pragma unroll
-                    for (int r = 0; r < R; r++) {
-                        uint32_t j = j0 + r * NW;
-                        if (j < n_new) { ids[r] = snew[j]; nrows = r + 1; }
-                    }
-                    uint32_t abyte = 0, abit = 0;
-                    if (filt_level && lane < R && j0 + lane * NW < n_new) { // lane r fetches row r's allow bit alongside the rows
-                        const uint32_t e = snew[j0 + lane * NW];
-                        abyte = allow[e >> 3];
-                        abit = e & 7u;
-                    }
-#ifndef LEANN_NO_ADJ_TOUCH
-                    // Latency form only: touch the adjacency lists of the rows being evaluated (two 128-B lines each, one lane per
-                    // line).  The next candidates come from these rows, so when phase E picks one its list is an L2 hit instead of
-                    // an HBM round trip at the head of the dependent chain; the chip is idle in this mode, the +8 % traffic is free.
-                    // (An ordinary load issued BEFORE the row loads and consumed behind them: the rows' wait covers it, and the
-                    // compiler keeps its register reserved until then.)
-                    uint32_t touch = 0;
-                    if (lv == 0 && (uint32_t)(lane >> 1) < (uint32_t)nrows && (uint32_t)(lane & 1) * 32u < deg)
-                        touch = adj0_p[(size_t)snew[j0 + (uint32_t)(lane >> 1) * NW] * deg + (uint32_t)(lane & 1) * 32u];
-#endif
-                    if (FEAT) wave_dist_rows_feat<T, R>(q, reinterpret_cast<const char *>(g.X), g.row_bytes, g.feat_h, ids, nrows, lane, dd, g.norms);
-                    else if constexpr (BF16) wave_dist_rows_bf16<T, R>(q, reinterpret_cast<const uint16_t *>(g.X), g.row_bytes >> 1, ids, nrows, lane, dd);
-                    else wave_dist_rows<T, R>(q, g.X, g.ld, ids, nrows, lane, dd);
-#ifndef LEANN_NO_ADJ_TOUCH
-                    asm volatile("" ::"v"(touch));
-#endif
-                    const unsigned long long amask = FILT ? __ballot((abyte >> abit) & 1u) : 0ull;
-                    if (lane == 0) {
-#pragma unroll
-                        for (int r = 0; r < R; r++)
-                            if (r < nrows) {
-                                const uint64_t key = make_key(dd[r], ids[r]);
-                                skey[j0 + r * NW] = key;
-                                if (filt_level) skeyR[j0 + r * NW] = ((amask >> r) & 1ull) ? key : ~0ull;
-                            }
-                    }
-                }
+                #include "hop_rows.cuh"
 #ifdef LEANN_STAMPS
                 const uint64_t stC = __builtin_amdgcn_s_memtime();
 #endif
@@ -1008,108 +654,13 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
                 const uint32_t n_pad = (n_new + 7) & ~7u;
                 if (wave == 0) {
                     // ---- phase E: next candidate; then phase B of the next hop ---------------------------------------------
-                    uint32_t u = LEANN_EMPTY;
-                    for (uint32_t base = 0; base < wsize && u == LEANN_EMPTY; base += 64) {
-                        const uint32_t i = base + lane;
-                        const unsigned long long m = __ballot(i < wsize && i != sel && !(Wc[i] & 1ull));
-                        if (m) u = base + (uint32_t)__ffsll((long long)m) - 1u;
-                    }
-                    const uint64_t c_old = u != LEANN_EMPTY ? Wc[u] : ~0ull;
-                    const uint64_t kj = (uint32_t)lane < n_new ? skey[lane] : ~0ull; // n_new <= 64 LW: LW keys per lane
-                    const uint64_t kj1 = LW == 2 && (uint32_t)lane + 64u < n_new ? skey[lane + 64] : ~0ull;
-                    const uint64_t km = LW == 2 ? min(kj, kj1) : kj;
-                    const uint32_t hi = wave_min_u32((uint32_t)(km >> 32));
-                    const uint32_t lo = wave_min_u32((uint32_t)(km >> 32) == hi ? (uint32_t)km : 0xFFFFFFFFu);
-                    const uint64_t c_new = n_new ? (((uint64_t)hi << 32) | lo) : ~0ull;
-                    uint32_t next = LEANN_EMPTY;
-                    uint64_t ckey = 0;
-                    if (c_old != ~0ull || c_new != ~0ull) {
-                        uint32_t rank;
-                        if ((c_old >> 1) < (c_new >> 1)) {
-                            rank = u + (uint32_t)__popcll(__ballot((kj >> 1) < (c_old >> 1)));
-                            if constexpr (LW == 2) rank += (uint32_t)__popcll(__ballot((kj1 >> 1) < (c_old >> 1)));
-                            ckey = c_old;
-#ifdef LEANN_STAMPS
-                            stamp[7] += 1;
-#endif
-                        } else {
-                            rank = 0;
-                            for (uint32_t base = 0; base < wsize; base += 64) {
-                                const uint32_t i = base + lane;
-                                rank += (uint32_t)__popcll(__ballot(i < wsize && (Wc[i] >> 1) < (c_new >> 1)));
-                            }
-                            ckey = c_new;
-                        }
-                        if (rank < ef_l) next = rank;
-                    }
-                    if (lane == 0) *next_slot = next;
-                    if (next != LEANN_EMPTY) {
-                        e_pref = (uint32_t)lane < deg ? adj_list(adj_base, upoff_p, deg, lv, key_id(ckey))[lane] : LEANN_EMPTY;
-                        if constexpr (LW == 2) e_pref1 = (uint32_t)lane + 64u < deg ? adj_list(adj_base, upoff_p, deg, lv, key_id(ckey))[lane + 64] : LEANN_EMPTY;
-                        phase_b(par ^ 1u, ckey, hop + 1); // waits for the list while the other waves merge
-                    }
+                    #include "hop_select.cuh"
+                    if (next != LEANN_EMPTY) phase_b(par ^ 1u, ckey, hop + 1); // waits for the list while the other waves merge
                 } else {
-                    // ---- phase D (waves 1 .. NW-1): merge by rank into the other buffer ---------------------------------
-                    // One work item per old entry (rank = index + #new keys below it) and per new key (rank = #old below it, by
-                    // binary search, + #new below it); the scan over the new keys reads 16 B per LDS instruction, 8 keys per
-                    // unrolled step, so the loads pipeline instead of paying one LDS latency per key.
-                    const ulonglong2 *kp = reinterpret_cast<const ulonglong2 *>(skey);
-                    for (uint32_t it = tid - 64; it < wsize + n_new; it += (NW - 1) * 64) {
-                        const bool isW = it < wsize;
-                        uint64_t k = isW ? Wc[it] : skey[it - wsize];
-                        if (isW && it == sel) k |= 1ull;
-                        const uint64_t kk = k >> 1;
-                        uint32_t cnt = 0;
-#pragma unroll 4
-                        for (uint32_t j = 0; j < n_pad; j += 2) {
-                            const ulonglong2 v = kp[j >> 1];
-                            cnt += ((v.x >> 1) < kk) + ((v.y >> 1) < kk);
-                        }
-                        uint32_t rank = isW ? it + cnt : cnt;
-                        if (!isW) {
-                            uint32_t lo = 0, hi = wsize;
-                            while (lo < hi) {
-                                uint32_t mid = (lo + hi) >> 1;
-                                if ((Wc[mid] >> 1) < kk) lo = mid + 1; else hi = mid;
-                            }
-                            rank += lo;
-                        }
-                        if (rank < ef_l) Wn[rank] = k;
-                    }
+                    #include "hop_merge.cuh"
                 }
                 if (filt_level) {
-                    // R <- kf best of R ∪ {allowed new keys}: the same merge by rank, on the blanked copy of the new keys.
-                    // Skipped (uniformly) when no allowed new key beats the current kf-th.
-                    uint64_t *Rc = R0 + rcur * kfp, *Rn = R0 + (rcur ^ 1) * kfp;
-                    const uint64_t thr = rsize == kf ? Rc[kf - 1] : ~0ull;
-                    uint32_t n_in = 0;
-                    for (uint32_t j = 0; j < n_new; j += 64) n_in += __popcll(__ballot(j + lane < n_new && skeyR[j + lane] < thr));
-                    if (n_in) {
-                        const ulonglong2 *kr = reinterpret_cast<const ulonglong2 *>(skeyR);
-                        for (uint32_t it = tid; it < rsize + n_new; it += NW * 64) {
-                            const bool isR = it < rsize;
-                            const uint64_t k = isR ? Rc[it] : skeyR[it - rsize];
-                            if (k >= thr && !isR) continue; // disallowed, or cannot enter a full list
-                            uint32_t cnt = 0;
-#pragma unroll 4
-                            for (uint32_t j = 0; j < n_pad; j += 2) {
-                                const ulonglong2 v = kr[j >> 1];
-                                cnt += (v.x < k) + (v.y < k);
-                            }
-                            uint32_t rank = isR ? it + cnt : cnt;
-                            if (!isR) {
-                                uint32_t lo = 0, hi = rsize;
-                                while (lo < hi) {
-                                    uint32_t mid = (lo + hi) >> 1;
-                                    if (Rc[mid] < k) lo = mid + 1; else hi = mid;
-                                }
-                                rank += lo;
-                            }
-                            if (rank < kf) Rn[rank] = k;
-                        }
-                        rsize = min(rsize + n_in, kf);
-                        rcur ^= 1;
-                    }
+                    #include "hop_rmerge.cuh"
                 }
 #ifdef LEANN_STAMPS
                 const uint64_t stD = __builtin_amdgcn_s_memtime();

@@ -286,6 +286,56 @@ def test_small_visited_table(la, cases, monkeypatch):
     _knob(la, monkeypatch, "LEANN_DEBUG_HASH_BITS", None)
 
 
+class _WanderingCase(_Case):
+    """i.i.d. rows (searches wander) under an oracle-built HNSW graph; the handle `s` is made by the test, after its knobs are set"""
+
+    def __init__(self, po, n, d, m):
+        self.d, self.n, self.algo, self._ref = d, n, 0, {}
+        self.X = synth(po, n, d, r=0)
+        self.Q = synth(po, NQ, d, stream=1, r=0)
+        self.G = po.Graph.build_hnsw(self.X, M=m, efc=64)
+
+
+def test_visited_set_climbs_both_pools_in_both_loop_forms(la, po, gpu, monkeypatch):
+    """The visited-set migration (csrc/hop_migrate.cuh), both branches — LDS -> pool 1, then pool 1 -> pool 2, which copies from an
+    HBM table, releases the old table's lock and keeps the generation — in both forms of the hop loop (64 queries: 16 waves; 704: 4
+    waves), plain and under a shared 10 % bitmap.  A 256-slot LDS table and 1024-slot pool-1 tables over 5000 i.i.d. rows: the
+    index does not fit a pool-1 table, so the handle gets a pool 2, and every query evaluates more nodes than pool 1 has slots."""
+    n, d, m, k, ef = 5000, 128, 16, 10, 400
+    c = _WanderingCase(po, n, d, m)
+    bm = np.packbits(np.random.default_rng(7).random(n) < 0.10, bitorder="little")
+    legs = [(nq, name, mask) for nq in (64, NQ) for name, mask in ((None, None), ("shared", bm))]
+    for nq, name, mask in legs:  # on the oracle's own numbers, before the GPU is touched: no leg can pass without reaching pool 2
+        ok, od, oc, ost = c.oracle(nq, k, ef, name, mask)
+        assert int(ost[:, 0].min()) > 1024, (nq, name, int(ost[:, 0].min()))
+    _knob(la, monkeypatch, "LEANN_DEBUG_HASH_BITS", 8)    # LDS table: 256 slots
+    _knob(la, monkeypatch, "LEANN_DEBUG_GPOOL_BITS", 10)  # pool 1: 1024 slots (the pools are sized at a handle's first use)
+    lv, uo, a0, aU = c.G.export()
+    c.s = la.BackendSearcher.from_arrays(la.BackendType.Hnsw, c.X, m, 2 * m, c.G.max_level, c.G.entry, lv, uo, a0, aU)
+    dQ, dbm = la.DeviceArray.from_host(c.Q), la.DeviceArray.from_host(bm)
+    try:
+        for nq, name, mask in legs:
+            gk, gd, gc, st, ost = _same(c, nq, k, ef, name, mask)
+            dk, dd, dc = la.DeviceArray((nq, k), np.uint64), la.DeviceArray((nq, k), np.float32), la.DeviceArray(nq, np.uint32)
+            dst = la.DeviceArray.from_host(np.full((nq, 4), 0xABCD1234, np.uint32))
+            if mask is None:
+                c.s.search_batch_device(dQ.ptr, nq, k, ef, dk.ptr, dd.ptr, dc.ptr, d_stats=dst.ptr)
+            else:
+                c.s.search_filtered_batch_device(dQ.ptr, nq, k, ef, dbm.ptr, 0, dk.ptr, dd.ptr, dc.ptr, d_stats=dst.ptr)
+            la.sync()
+            per_query = dst.to_host()
+            what = f"nq={nq} {name or 'plain'}"
+            print(f"{what}: visited-set level per query {np.bincount(per_query[:, 3], minlength=3).tolist()}, least evaluations {int(ost[:, 0].min())}")
+            assert (per_query[:, 3] == 2).all(), what  # 0 LDS, 1 pool 1, 2 pool 2
+            assert (per_query[:, :3] == ost[:, :3]).all(), what
+            assert (dk.to_host() == gk).all() and (dd.to_host().view(np.uint32) == gd.view(np.uint32)).all() and (dc.to_host() == gc).all(), what
+            assert st["n_table_overflow"] == nq, what
+    finally:
+        c.s.close()
+        _knob(la, monkeypatch, "LEANN_DEBUG_GPOOL_BITS", None)
+        _knob(la, monkeypatch, "LEANN_DEBUG_HASH_BITS", None)
+
+
 # ---- 3. recompute-on graph kernels wider than 256 features ---------------------------------------------------------------------------
 # The widest feature width leann_recompute_create accepts at dims = 128 (recompute.hip): it refuses encode_lds_bytes(hp, dp, fused) =
 # 128 (hp + 8) 2 + 3 (dp + 192) 16 2 + 6 128 4 > 160 KiB, with hp = h rounded up to 16 and dp = 128 (one column tile):
