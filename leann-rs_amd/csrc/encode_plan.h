@@ -28,7 +28,7 @@ struct EncodePlan {
 static inline size_t encode_lds_bytes(size_t hp, size_t cols, bool fused = false) {
     return 128 * (hp + 8) * 2 + 3 * (cols + (fused ? 192 : 0)) * 16 * 2 + 6 * 128 * 4;
 }
-static inline bool encode_ct_compiled(int ct) { return ct == 1 || ct == 2 || ct == 3 || ct == 4 || ct == 6; }
+static inline constexpr bool encode_ct_compiled(int ct) { return ct == 1 || ct == 2 || ct == 3 || ct == 4 || ct == 6; }
 
 static inline EncodePlan encode_plan(size_t h, size_t dims) {
     EncodePlan p = {};

@@ -31,6 +31,16 @@
 #include <vector>
 #include "bf16.h" // f32_to_bf16_rne
 
+// A launch of a kernel whose dynamic LDS may pass 64 KiB: raise the kernel's limit to the CU's 160 KiB (where the site says so),
+// launch, check.  The arguments are converted to the kernel's parameter types.
+template <typename... P, typename... A>
+static int launch_lds(void (*kernel)(P...), bool raise_limit, unsigned grid, unsigned block, size_t lds, hipStream_t st, A... args) {
+    if (raise_limit) HIP_CHECK_RET(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, st, static_cast<P>(args)...);
+    HIP_CHECK_RET(hipGetLastError());
+    return LEANN_OK;
+}
+
 // ---- synthetic features / weights: the recompute twin of gen.hip -----------------------------------
 // f_i[k] = bf16(centre_c[k] + sigma * noise_i[k]),  W[k][j] = bf16(gauss(k, j))  (same hash streams as
 // gen.hip with r = h), so normalise(W^T f_i) is the clustered synthetic corpus at bf16 input precision.
@@ -83,13 +93,9 @@ extern "C" int leann_synth_features_device(uint64_t seed, uint32_t h, uint32_t r
     }
     if (n == 0) return LEANN_OK;
     const size_t lds = r_int ? ((size_t)h * r_int + r_int) * 4 : 0;
-    if (lds > 64 * 1024)
-        HIP_CHECK_RET(hipFuncSetAttribute((const void *)synth_features_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     const uint64_t blocks = r_int ? std::min<uint64_t>(n, 4096) : std::min<uint64_t>((n * h + 255) / 256, 65536);
-    hipLaunchKernelGGL(synth_features_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, seed, h, r_int, n_clusters,
-                       sigma, stream_id, i0, n, d_out);
-    HIP_CHECK_RET(hipGetLastError());
-    return LEANN_OK;
+    return launch_lds(synth_features_kernel, lds > 64 * 1024, (unsigned)blocks, 256, lds, (hipStream_t)stream, seed, h, r_int, n_clusters,
+                      sigma, stream_id, i0, n, d_out);
 }
 extern "C" int leann_synth_weights_device(uint64_t seed, uint32_t h, uint32_t dims, uint16_t *d_out, void *stream) {
     if (!d_out || h == 0 || dims == 0) { leann_set_error("leann_synth_weights_device: invalid arguments"); return LEANN_ERR_INVALID; }
@@ -171,14 +177,15 @@ __global__ void __launch_bounds__(256) project_queries_kernel(const uint16_t *__
 }
 
 // ------------------------------------------------------------------------------------------------
-// encode_kernel<CT, FUSED>: 512 threads = 8 waves; workgroup tile = 128 passages x (CT*4*32) columns
+// encode_kernel<CT, FUSED, POOL>: 512 threads = 8 waves; workgroup tile = 128 passages x (CT*4*32) columns
 // (CT col tiles of 32 per wave, 4 column groups, 2 row halves of 64 passages).  d <= CT*128.
-// LDS: sF[128][hp + 8] bf16 (whole K, loaded once) + a 3-slot ring of sW[DP (+192)][16] bf16 k-step slabs (LDS-DMA,
-// two slabs in flight behind counted vmcnt waits and one raw s_barrier per k-step).
+// LDS: sF[128][hp + 8] bf16 (whole K, loaded once) + a 3-slot ring of sW[DP (+192)][16] bf16 k-step slabs + sN / sM / sC.
 //   FUSED = false: E = l2norm(F W) stored as f32 (validation / leann_recompute_encode_device)
-//   FUSED = true : nothing but S[q][passage] = <f, W q> / ||W^T f|| leaves the workgroup; each wave adds
-//                  3 MFMAs per k-step (hi/lo/lo2 pieces) for one 32-query x 32-passage score tile,
-//                  reusing the feature fragment it already holds as the B operand.
+//   FUSED = true : nothing but S[q][passage] = <f, W q> / ||W^T f|| leaves the workgroup
+//   POOL         : masked mean pooling over the L token rows of a passage between the GEMM and the norm
+// Its phases are the fragments encode_*.cuh, which encode_blocked_kernel (recompute_blocked.cuh) runs per column block: each is
+// stated once and included at its place, so that both kernels keep the device code they had (profiles/encode_fragments.md).
+// The kernel's own: the LDS layout, the one block's names (dp, col0, SN_ADD, SCORE) and the normalised store of E.
 // ------------------------------------------------------------------------------------------------
 template <int CT, bool FUSED, bool POOL>
 __global__ void __launch_bounds__(512) encode_kernel(const uint16_t *__restrict__ F, uint64_t n, uint32_t h, uint32_t hp,
@@ -186,8 +193,9 @@ __global__ void __launch_bounds__(512) encode_kernel(const uint16_t *__restrict_
                                                      float *__restrict__ E, const uint16_t *__restrict__ Gp, uint32_t nq,
                                                      float *__restrict__ S, uint32_t n_rows_s, uint32_t L,
                                                      const uint8_t *__restrict__ mask, float *__restrict__ norms_out) {
-    constexpr int DP = CT * 128;              // padded columns of W
-    constexpr int DPX = DP + (FUSED ? 192 : 0); // + three 64-query pieces of G
+    constexpr bool SCORE = FUSED;               // the fragments' name: the one block is also the block that scores
+    constexpr int DP = CT * 128;                // padded columns of W
+    constexpr int DPX = DP + (SCORE ? 192 : 0); // + three 64-query pieces of G
     constexpr int RING = 3;                     // k-step slabs in LDS: one being consumed, two in flight
     constexpr int NI = DPX * 2 / 64;            // 1-KiB DMA instructions per k-step slab
     constexpr int PER = (NI + 7) / 8;           // ... per wave (the same count in every wave: counted vmcnt waits)
@@ -203,178 +211,19 @@ __global__ void __launch_bounds__(512) encode_kernel(const uint16_t *__restrict_
     const int rhalf = wave >> 2, cgrp = wave & 3;
     const uint64_t row_base = (uint64_t)blockIdx.x * 128;
 
-    // ---- stage the feature tile (zero-padded rows / k) ------------------------------------------------
-    for (uint32_t idx = tid; idx < 128 * (hp / 8); idx += 512) {
-        const uint32_t r = idx / (hp / 8), k8 = (idx % (hp / 8)) * 8;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        const uint64_t row = row_base + r;
-        if (row < n) {
-            if (k8 + 8 <= h && ((h & 7) == 0)) v = *reinterpret_cast<const uint4 *>(F + row * h + k8);
-            else {
-                uint16_t t[8];
-                for (int e = 0; e < 8; e++) t[e] = (k8 + e < h) ? F[row * h + k8 + e] : (uint16_t)0;
-                memcpy(&v, t, 16);
-            }
-        }
-        *reinterpret_cast<uint4 *>(sF + r * fstride + k8) = v;
-    }
-    // k-step staging by LDS-DMA (global_load_lds_dwordx4: 64 lanes x 16 B = 1 KiB per wave instruction, no VGPRs,
-    // asynchronous until the wave's vmcnt wait).  The LDS image is linear in 16-B slots; slot p holds global piece
-    // p ^ ((p >> 4) & 1) (swizzle on the SOURCE address), which makes the 32-B-stride fragment reads conflict-free.
-    auto stage_w = [&](int slot, uint32_t ks) {
-        const char *wsrc = reinterpret_cast<const char *>(Wp + (size_t)ks * DP * 16);
-        const char *gsrc = FUSED ? reinterpret_cast<const char *>(Gp + (size_t)ks * 192 * 16) : nullptr;
-        char *dst = reinterpret_cast<char *>(sW + slot * DPX * 16);
-#pragma unroll
-        for (int j = 0; j < PER; j++) {
-            uint32_t i = wave + 8 * j;
-            if (i >= (uint32_t)NI) i = NI - 1; // padding instruction: re-fetches the last piece (same bytes, same place)
-            const uint32_t p = i * 64 + lane, g = p ^ ((p >> 4) & 1);
-            const char *src = (!FUSED || g < (uint32_t)(DP * 2)) ? wsrc + (size_t)g * 16 : gsrc + (size_t)(g - DP * 2) * 16;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                             (__attribute__((address_space(3))) void *)(dst + i * 1024), 16, 0, 0);
-        }
-    };
-    auto frag = [&](const uint16_t *region, uint32_t col) -> bf16x8 { // 8 consecutive k of one column (16 B)
-        const uint32_t g = 2 * col + lh, p = g ^ ((g >> 4) & 1);
-        return *reinterpret_cast<const bf16x8 *>(reinterpret_cast<const char *>(region) + p * 16);
-    };
-    f32x16 acc[2][CT];
-    f32x16 accs; // FUSED: scores of query tile (cgrp & 1) x passage tile (2*rhalf + (cgrp >> 1))
-#pragma unroll
-    for (int i = 0; i < 16; i++) accs[i] = 0.f;
-#pragma unroll
-    for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++)
-#pragma unroll
-            for (int i = 0; i < 16; i++) acc[rt][ct][i] = 0.f;
+#include "encode_features.cuh" // the feature tile -> sF
+    constexpr uint32_t dp = DP, col0 = 0; // the one block: every column of a k-step slab, from column 0
+#include "encode_ring.cuh" // stage_w, frag, acc = 0, accs = 0
     const int st = cgrp >> 1, qt = cgrp & 1;
-
-    if (POOL && tid < 128) {
-        const uint64_t row = row_base + tid;
-        sM[tid] = (row < n && (!mask || mask[row] != 0)) ? 1.f : 0.f;
-    }
     const uint32_t nks = hp / 16;
-    __syncthreads(); // feature tile + mask visible (no DMA in flight yet: a plain barrier)
-    if (POOL && tid < 128 && (tid % L) == 0) {
-        float c = 0.f;
-        for (uint32_t j = 0; j < L; j++) c += sM[tid + j];
-        sC[tid] = c < 1e-9f ? 1e-9f : c; // candle.rs:213 count.clamp(1e-9, inf)
-    }
-    stage_w(0, 0);
-    if (nks > 1) stage_w(1, 1);
-    for (uint32_t ks = 0; ks < nks; ks++) {
-        // (a) my pieces of slab ks have landed (slab ks+1 may stay in flight), (b) everybody's have, and everybody
-        // is done reading slab ks-1, so (c) its slot can take slab ks+2.  One raw barrier per k-step; __syncthreads()
-        // would drain the DMA queue (vmcnt(0)) and serialise the stream.
-        if (ks + 1 < nks) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (ks + 2 < nks) stage_w((ks + 2) % RING, ks + 2);
-        const uint16_t *w = sW + (ks % RING) * DPX * 16;
-        bf16x8 a[2], b[CT];
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++)
-            a[rt] = *reinterpret_cast<const bf16x8 *>(sF + (rhalf * 64 + rt * 32 + l31) * fstride + ks * 16 + lh * 8);
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++)
-            b[ct] = frag(w, (cgrp * CT + ct) * 32 + l31);
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++)
-                acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[rt], b[ct], acc[rt][ct], 0, 0, 0);
-        if (FUSED) {
-            const bf16x8 fb = st ? a[1] : a[0]; // B operand: B[k][j = passage]  (same bytes as the A fragment of F)
-#pragma unroll
-            for (int p = 0; p < 3; p++) {
-                const bf16x8 g = frag(w, DP + p * 64 + qt * 32 + l31);
-                accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g, fb, accs, 0, 0, 0); // C[i = query][j = passage]
-            }
-        }
-    }
-    __syncthreads();
-
-    // ---- masked mean pooling over the L token rows of a passage (candle.rs:191-216) ------------------------
-    // C/D layout: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5): the four registers of a
-    // group are four consecutive token rows, so L <= 4 pools in registers and L = 8 adds the lane + 32 partner.
-    // The pooled mean lands in the register of the passage's first token; the other registers become 0.
-    if (POOL) {
-#pragma unroll
-    for (int rt = 0; rt < 2; rt++) {
-#pragma unroll
-        for (int g4 = 0; g4 < 4; g4++) {
-            const int r0 = rhalf * 64 + rt * 32 + 8 * g4 + 4 * lh;
-            const float m0 = sM[r0], m1 = sM[r0 + 1], m2 = sM[r0 + 2], m3 = sM[r0 + 3];
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++) {
-                float v0 = acc[rt][ct][4 * g4] * m0, v1 = acc[rt][ct][4 * g4 + 1] * m1;
-                float v2 = acc[rt][ct][4 * g4 + 2] * m2, v3 = acc[rt][ct][4 * g4 + 3] * m3;
-                if (L == 1) {
-                    v0 /= sC[r0]; v1 /= sC[r0 + 1]; v2 /= sC[r0 + 2]; v3 /= sC[r0 + 3];
-                } else if (L == 2) {
-                    v0 = (v0 + v1) / sC[r0]; v2 = (v2 + v3) / sC[r0 + 2]; v1 = 0.f; v3 = 0.f;
-                } else if (L == 4) {
-                    v0 = (((v0 + v1) + v2) + v3) / sC[r0]; v1 = v2 = v3 = 0.f;
-                } else { // L == 8: tokens 0-3 in the lane with lh = 0, tokens 4-7 in its lh = 1 partner
-                    float a = ((v0 + v1) + v2) + v3;
-                    float t = a + __shfl_xor(a, 32, 64);
-                    v0 = lh == 0 ? t / sC[r0] : 0.f; v1 = v2 = v3 = 0.f;
-                }
-                acc[rt][ct][4 * g4] = v0; acc[rt][ct][4 * g4 + 1] = v1; acc[rt][ct][4 * g4 + 2] = v2; acc[rt][ct][4 * g4 + 3] = v3;
-            }
-        }
-    }
-    } // POOL
-    // ---- row norms of the pooled embeddings (candle.rs:218-225) ---------------------------------------------
-#pragma unroll
-    for (int rt = 0; rt < 2; rt++) {
-#pragma unroll
-        for (int reg = 0; reg < 16; reg++) {
-            float p = 0.f;
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++) p = fmaf(acc[rt][ct][reg], acc[rt][ct][reg], p);
-            // sum over the 32 lanes that share lane >> 5 (the 32 columns of a tile)
-            p += __shfl_xor(p, 1, 64);
-            p += __shfl_xor(p, 2, 64);
-            p += __shfl_xor(p, 4, 64);
-            p += __shfl_xor(p, 8, 64);
-            p += __shfl_xor(p, 16, 64);
-            if (l31 == 0) sN[cgrp * 128 + rhalf * 64 + rt * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh] = p;
-        }
-    }
-    __syncthreads();
+#include "encode_mask.cuh" // sM, sC; its barrier publishes the feature tile
+#include "encode_kloop.cuh" // acc = F W, SCORE: accs = G F^T
+    __syncthreads(); // every wave is done with the ring (all DMA waited for: a plain barrier)
+    constexpr bool SN_ADD = false; // the one block: its sums of squares are the row's
+#include "encode_pool.cuh" // POOL: acc = masked mean over the L token rows; sN = the sums of squares
+    __syncthreads(); // the sums of squares of every column group are in sN
     if (FUSED) {
-        // score tile: rows (regs) = queries, col (lane & 31) = token row.  Mask, pool the L adjacent lanes of a
-        // passage, then <mean, q> / ||mean||; 128-B coalesced stores into S[q][passage] when L = 1.
-        const int r = rhalf * 64 + st * 32 + l31;
-        const uint64_t row = row_base + r;
-        const float ss = ((sN[r] + sN[128 + r]) + (sN[256 + r] + sN[384 + r]));
-        float nrm = sqrtf(ss);
-        nrm = nrm < 1e-12f ? 1e-12f : nrm;
-        if (!POOL) {
-            if (row < n) {
-#pragma unroll
-                for (int reg = 0; reg < 16; reg++) {
-                    const uint32_t q = qt * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-                    if (q < nq) S[(size_t)q * n_rows_s + row] = accs[reg] / nrm;
-                }
-            }
-            return;
-        }
-        const float m = sM[r];
-        const bool first = (r % L) == 0;
-        const float cnt = first ? sC[r] : 1.f;
-#pragma unroll
-        for (int reg = 0; reg < 16; reg++) {
-            float v = accs[reg] * m;
-            if (L >= 2) v += __shfl_xor(v, 1, 64);
-            if (L >= 4) v += __shfl_xor(v, 2, 64);
-            if (L >= 8) v += __shfl_xor(v, 4, 64);
-            const uint32_t q = qt * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-            if (first && row < n && q < nq) S[(size_t)q * n_rows_s + row / L] = (v / cnt) / nrm;
-        }
+#include "encode_score.cuh" // S = accs / nrm
         return;
     }
 #pragma unroll
@@ -383,9 +232,7 @@ __global__ void __launch_bounds__(512) encode_kernel(const uint16_t *__restrict_
         for (int reg = 0; reg < 16; reg++) {
             const int r = rhalf * 64 + rt * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
             const uint64_t row = row_base + r;
-            const float ss = ((sN[r] + sN[128 + r]) + (sN[256 + r] + sN[384 + r])); // fixed order: reproducible
-            float nrm = sqrtf(ss);
-            nrm = nrm < 1e-12f ? 1e-12f : nrm;
+#include "encode_norm.cuh" // nrm
             if (row < n && (r % L) == 0) {
                 if (norms_out && cgrp == 0 && l31 == 0) norms_out[row / L] = nrm; // ||W^T f|| before normalisation
 #pragma unroll
@@ -455,6 +302,39 @@ static bool use_fstat(const leann_recompute *r) {
     return r->L == 1 && !r->mask && r->h == 256 && r->dp % 128 == 0 && !leann_knobs().fused_v1;
 }
 
+// The general encode kernels this file compiles, one row per kernel, the key and the instantiation written from the same template
+// arguments.  ct = 0: encode_blocked_kernel, which takes its block widths at run time.
+template <typename K>
+struct EncodeRow {
+    int ct;
+    bool fused, pool;
+    K kernel;
+};
+using EncodeKernel = decltype(&encode_kernel<1, false, false>);
+using EncodeBlockedKernel = decltype(&encode_blocked_kernel<false, false>);
+template <int CT, bool FUSED, bool POOL>
+static constexpr EncodeRow<EncodeKernel> encode_row() { return {CT, FUSED, POOL, encode_kernel<CT, FUSED, POOL>}; }
+template <bool FUSED, bool POOL>
+static constexpr EncodeRow<EncodeBlockedKernel> encode_blocked_row() { return {0, FUSED, POOL, encode_blocked_kernel<FUSED, POOL>}; }
+#define ENCODE_FORMS(CT) encode_row<CT, false, false>(), encode_row<CT, false, true>(), encode_row<CT, true, false>(), encode_row<CT, true, true>()
+static constexpr EncodeRow<EncodeKernel> encode_rows[] = {ENCODE_FORMS(1), ENCODE_FORMS(2), ENCODE_FORMS(3), ENCODE_FORMS(4), ENCODE_FORMS(6)};
+#undef ENCODE_FORMS
+static constexpr EncodeRow<EncodeBlockedKernel> encode_blocked_rows[] = {encode_blocked_row<false, false>(), encode_blocked_row<false, true>(),
+                                                                         encode_blocked_row<true, false>(), encode_blocked_row<true, true>()};
+template <typename K, size_t N>
+static constexpr K encode_find(const EncodeRow<K> (&rows)[N], int ct, bool fused, bool pool) {
+    for (const EncodeRow<K> &row : rows)
+        if (row.ct == ct && row.fused == fused && row.pool == pool) return row.kernel;
+    return nullptr;
+}
+static constexpr bool encode_rows_match_plan() { // the widths encode_plan may choose, in all four forms, and no others
+    for (int ct = 0; ct < 16; ct++)
+        for (int form = 0; form < 4; form++)
+            if ((encode_find(encode_rows, ct, (form & 2) != 0, (form & 1) != 0) != nullptr) != encode_ct_compiled(ct)) return false;
+    return true;
+}
+static_assert(encode_rows_match_plan(), "encode_rows and encode_ct_compiled (encode_plan.h) list different widths");
+
 static int launch_encode(const leann_recompute *r, uint64_t row0, uint64_t rows, float *E, hipStream_t st,
                          const uint16_t *Gp = nullptr, uint32_t nq = 0, float *S = nullptr, float *norms = nullptr,
                          const CandEmit *emit = nullptr, const uint32_t *idx = nullptr) {
@@ -470,75 +350,33 @@ static int launch_encode(const leann_recompute *r, uint64_t row0, uint64_t rows,
         int cus = 256;
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, r->device);
         const unsigned grid2 = (unsigned)std::min<uint64_t>(units, (uint64_t)cus);
-        if (idx) { // rows [row0, row0 + rows) of the LIST: passage i = row idx[i] of the row-major features
-            HIP_CHECK_RET(hipFuncSetAttribute((const void *)fused_fstat_kernel<16, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            hipLaunchKernelGGL((fused_fstat_kernel<16, false, true>), dim3(grid2), dim3(256), lds2, st, r->F, (uint64_t)rows, r->Wp,
-                               (uint32_t)r->dp, Gp, nq, S, (uint32_t)rows, emit ? *emit : CandEmit{}, idx + row0);
-        } else if (r->Ft) {
-            HIP_CHECK_RET(hipFuncSetAttribute((const void *)fused_fstat_kernel<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            hipLaunchKernelGGL((fused_fstat_kernel<16, true>), dim3(grid2), dim3(256), lds2, st,
-                               reinterpret_cast<const uint16_t *>(r->Ft) + row0 * r->h, (uint64_t)rows, r->Wp, (uint32_t)r->dp, Gp, nq, S,
-                               (uint32_t)rows, emit ? *emit : CandEmit{});
-        } else {
-            HIP_CHECK_RET(hipFuncSetAttribute((const void *)fused_fstat_kernel<16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            hipLaunchKernelGGL((fused_fstat_kernel<16, false>), dim3(grid2), dim3(256), lds2, st, r->F + row0 * r->h, (uint64_t)rows, r->Wp,
-                               (uint32_t)r->dp, Gp, nq, S, (uint32_t)rows, emit ? *emit : CandEmit{});
-        }
-        HIP_CHECK_RET(hipGetLastError());
-        return LEANN_OK;
+        const CandEmit em = emit ? *emit : CandEmit{};
+        if (idx) // rows [row0, row0 + rows) of the LIST: passage i = row idx[i] of the row-major features
+            return launch_lds(fused_fstat_kernel<16, false, true>, true, grid2, 256, lds2, st, r->F, rows, r->Wp, r->dp, Gp, nq, S, rows, em,
+                              idx + row0);
+        if (r->Ft)
+            return launch_lds(fused_fstat_kernel<16, true>, true, grid2, 256, lds2, st, reinterpret_cast<const uint16_t *>(r->Ft) + row0 * r->h,
+                              rows, r->Wp, r->dp, Gp, nq, S, rows, em, nullptr);
+        return launch_lds(fused_fstat_kernel<16, false>, true, grid2, 256, lds2, st, r->F + row0 * r->h, rows, r->Wp, r->dp, Gp, nq, S, rows, em,
+                          nullptr);
     }
     // row0 / rows count PASSAGES; the kernel works on token rows (L per passage, tiles of 128 token rows)
     const uint64_t tok0 = row0 * r->L, toks = rows * r->L;
     const unsigned grid = (unsigned)((toks + 127) / 128);
     const uint16_t *F = r->F + tok0 * r->h;
     const uint8_t *mk = r->mask ? r->mask + tok0 : nullptr;
-    if (r->blocks.n) { // dims > 768: column blocks, the LDS ring sized by the widest one
-        const size_t ldsb = encode_lds_bytes(r->hp, (size_t)r->ctb_max * 128, fused);
-        const bool pool = r->L > 1 || r->mask != nullptr;
-#define LAUNCH_BLOCKED(FU, PO)                                                                                                  \
-    do {                                                                                                                        \
-        HIP_CHECK_RET(hipFuncSetAttribute((const void *)encode_blocked_kernel<FU, PO>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                          160 * 1024));                                                                         \
-        hipLaunchKernelGGL((encode_blocked_kernel<FU, PO>), dim3(grid), dim3(512), ldsb, st, F, (uint64_t)toks, (uint32_t)r->h,     \
-                           (uint32_t)r->hp, r->Wp, (uint32_t)r->d, (uint32_t)r->dp, (uint32_t)r->ld, E, Gp, nq, S, (uint32_t)rows,  \
-                           r->L, mk, norms, r->blocks);                                                                         \
-    } while (0)
-        if (fused && pool) LAUNCH_BLOCKED(true, true);
-        else if (fused) LAUNCH_BLOCKED(true, false);
-        else if (pool) LAUNCH_BLOCKED(false, true);
-        else LAUNCH_BLOCKED(false, false);
-#undef LAUNCH_BLOCKED
-        HIP_CHECK_RET(hipGetLastError());
-        return LEANN_OK;
+    const bool pool = r->L > 1 || r->mask != nullptr;
+    if (r->blocks.n) // dims > 768: column blocks, the LDS ring sized by the widest one
+        return launch_lds(encode_find(encode_blocked_rows, 0, fused, pool), true, grid, 512,
+                          encode_lds_bytes(r->hp, (size_t)r->ctb_max * 128, fused), st, F, toks, r->h, r->hp, r->Wp, r->d, r->dp, r->ld, E, Gp,
+                          nq, S, rows, r->L, mk, norms, r->blocks);
+    const EncodeKernel kernel = encode_find(encode_rows, r->ct, fused, pool);
+    if (!kernel) {
+        leann_set_error("recompute: unsupported dims %zu", r->d);
+        return LEANN_ERR_INVALID;
     }
-    const size_t lds = encode_lds_bytes(r->hp, r->dp, fused);
-#define LAUNCH_ONE(CT, FU, PO)                                                                                            \
-    do {                                                                                                                  \
-        HIP_CHECK_RET(hipFuncSetAttribute((const void *)encode_kernel<CT, FU, PO>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                          160 * 1024));                                                                   \
-        hipLaunchKernelGGL((encode_kernel<CT, FU, PO>), dim3(grid), dim3(512), lds, st, F, (uint64_t)toks, (uint32_t)r->h,        \
-                           (uint32_t)r->hp, r->Wp, (uint32_t)r->d, (uint32_t)r->ld, E, Gp, nq, S, (uint32_t)rows, r->L, mk, norms); \
-    } while (0)
-#define LAUNCH_CT(CT)                                                                                                     \
-    do {                                                                                                                  \
-        const bool pool = r->L > 1 || r->mask != nullptr;                                                                 \
-        if (fused && pool) LAUNCH_ONE(CT, true, true);                                                                    \
-        else if (fused) LAUNCH_ONE(CT, true, false);                                                                      \
-        else if (pool) LAUNCH_ONE(CT, false, true);                                                                       \
-        else LAUNCH_ONE(CT, false, false);                                                                                \
-    } while (0)
-    switch (r->ct) {
-        case 1: LAUNCH_CT(1); break;
-        case 2: LAUNCH_CT(2); break;
-        case 3: LAUNCH_CT(3); break;
-        case 4: LAUNCH_CT(4); break;
-        case 6: LAUNCH_CT(6); break;
-        default: leann_set_error("recompute: unsupported dims %zu", r->d); return LEANN_ERR_INVALID;
-    }
-#undef LAUNCH_CT
-#undef LAUNCH_ONE
-    HIP_CHECK_RET(hipGetLastError());
-    return LEANN_OK;
+    return launch_lds(kernel, true, grid, 512, encode_lds_bytes(r->hp, r->dp, fused), st, F, toks, r->h, r->hp, r->Wp, r->d, r->ld, E, Gp, nq, S,
+                      rows, r->L, mk, norms);
 }
 
 extern "C" int leann_recompute_create(const uint16_t *d_features, size_t n, size_t h, const uint16_t *d_weights, size_t dims,

@@ -1,18 +1,16 @@
 // recompute_blocked.cuh — the general encode kernel for dims > 768 (included by recompute.hip only).
 // encode_kernel<CT, ..> keeps a 128-passage x ALL-columns tile in accumulators (192 registers at CT = 6) and a 3-slot ring of
 // all-column k-step slabs in LDS (159 of 160 KiB at dp = 768, h = 256): neither fits twice.  encode_blocked_kernel<FUSED, POOL>
-// keeps the feature tile sF[128][hp + 8] in LDS for the whole workgroup and walks the columns in blocks of CTB * 128
-// (encode_plan.h: CTB in {1, 2, 3, 4, 6}, block b = columns [col0_b, col0_b + CTB_b * 128) of every k-step slab of the SAME
-// Wp[kstep][dp][16] image), each block running encode_kernel's k-loop: 3-slot LDS-DMA ring, counted vmcnt, one raw barrier per k-step.
-//   * sums of squares: per block the narrow kernel's arithmetic (fmaf over the block's tiles, 5-step butterfly over the 32 lanes of a
-//     tile), added to sN[column group][row] by the one lane that owns the entry, block after block; the four column groups are
-//     combined after the last block as encode_kernel does.  No atomics: the same input gives the same bits.
-//   * FUSED: the three G pieces ride in the slabs of the LAST block only and the score MFMAs run there (the score tile is then live in
-//     registers for one block, not for all of them); score = accs / nrm with nrm taken after the last block.
+// keeps the feature tile sF[128][hp + 8] in LDS for the whole workgroup and walks the columns in blocks of CT * 128
+// (encode_plan.h: CT in {1, 2, 3, 4, 6}, block b = columns [col0_b, col0_b + CT_b * 128) of every k-step slab of the SAME
+// Wp[kstep][dp][16] image).  A block runs the phases of encode_kernel, from the same fragments (encode_ring.cuh, encode_kloop.cuh,
+// encode_pool.cuh, encode_score.cuh; encode_features.cuh and encode_mask.cuh once in front of the blocks); what is this kernel's own:
+//   * sums of squares: added to sN block after block (SN_ADD), combined after the last block (encode_norm.cuh).
+//   * FUSED: the three G pieces ride in the slabs of the LAST block only and the score MFMAs run there (SCORE: the score tile is then
+//     live in registers for one block, not for all of them); score = accs / nrm with nrm taken after the last block.
 //   * not FUSED: the row norm is known only after the last block, so every thread stores its unnormalised values as its blocks finish
 //     and, after the last block, re-reads exactly the addresses it wrote and stores value / nrm (same thread, same addresses:
 //     program order, no cross-thread visibility involved).  The GEMM runs once.
-//   * POOL: masked mean pooling per block in registers before squaring, as in encode_kernel.
 #pragma once
 #include "encode_plan.h"
 
@@ -46,154 +44,31 @@ __global__ void __launch_bounds__(512) encode_blocked_kernel(const uint16_t *__r
     const uint64_t row_base = (uint64_t)blockIdx.x * 128;
     const uint32_t nks = hp / 16;
 
-    // ---- stage the feature tile once (zero-padded rows / k); it stays for every column block ----------------
-    for (uint32_t idx = tid; idx < 128 * (hp / 8); idx += 512) {
-        const uint32_t r = idx / (hp / 8), k8 = (idx % (hp / 8)) * 8;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        const uint64_t row = row_base + r;
-        if (row < n) {
-            if (k8 + 8 <= h && ((h & 7) == 0)) v = *reinterpret_cast<const uint4 *>(F + row * h + k8);
-            else {
-                uint16_t t[8];
-                for (int e = 0; e < 8; e++) t[e] = (k8 + e < h) ? F[row * h + k8 + e] : (uint16_t)0;
-                memcpy(&v, t, 16);
-            }
-        }
-        *reinterpret_cast<uint4 *>(sF + r * fstride + k8) = v;
-    }
+#include "encode_features.cuh" // the feature tile -> sF, once: it stays for every column block
     sN[tid] = 0.f; // 512 threads = 4 x 128 entries
-    if (POOL && tid < 128) {
-        const uint64_t row = row_base + tid;
-        sM[tid] = (row < n && (!mask || mask[row] != 0)) ? 1.f : 0.f;
-    }
-    __syncthreads(); // feature tile + mask visible (no DMA in flight yet: a plain barrier)
-    if (POOL && tid < 128 && (tid % L) == 0) {
-        float c = 0.f;
-        for (uint32_t j = 0; j < L; j++) c += sM[tid + j];
-        sC[tid] = c < 1e-9f ? 1e-9f : c; // candle.rs:213 count.clamp(1e-9, inf)
-    }
-    auto frag = [](const uint16_t *region, uint32_t col, int lh) -> bf16x8 { // 8 consecutive k of one column (16 B)
-        const uint32_t g = 2 * col + lh, p = g ^ ((g >> 4) & 1);
-        return *reinterpret_cast<const bf16x8 *>(reinterpret_cast<const char *>(region) + p * 16);
-    };
-    // One column block: CTB tiles of 32 columns per wave starting at column col0; SCORE = the block that also carries G.
-    auto run_block = [&](auto ctb_c, auto score_c, const uint32_t col0) __attribute__((always_inline)) {
-        constexpr int CTB = decltype(ctb_c)::value;
+#include "encode_mask.cuh" // sM, sC; its barrier publishes the feature tile and the zeroed sN
+    // One column block: CT tiles of 32 columns per wave starting at column col0; SCORE = the block that also carries G.
+    auto run_block = [&](auto ct_c, auto score_c, const uint32_t col0) __attribute__((always_inline)) {
+        constexpr int CT = decltype(ct_c)::value;
         constexpr bool SCORE = decltype(score_c)::value;
-        constexpr int DPB = CTB * 128;               // columns of the block
-        constexpr int DPX = DPB + (SCORE ? 192 : 0); // + three 64-query pieces of G
-        constexpr int NI = DPX * 2 / 64;             // 1-KiB DMA instructions per k-step slab
-        constexpr int PER = (NI + 7) / 8;            // ... per wave (the same count in every wave: counted vmcnt waits)
+        constexpr int DP = CT * 128;                // columns of the block
+        constexpr int DPX = DP + (SCORE ? 192 : 0); // + three 64-query pieces of G
+        constexpr int NI = DPX * 2 / 64;            // 1-KiB DMA instructions per k-step slab
+        constexpr int PER = (NI + 7) / 8;           // ... per wave (the same count in every wave: counted vmcnt waits)
         // The lane's indices are re-derived per block from an opaque copy of the thread id: hipcc otherwise hoists the address
         // arithmetic of all five block widths in front of the block loop and spills ~100 registers of it into the k-loops.
         int tid_b = tid;
         asm volatile("" : "+v"(tid_b));
         const int lane = tid_b & 63, wave = tid_b >> 6, l31 = lane & 31, lh = lane >> 5, rhalf = wave >> 2, cgrp = wave & 3;
         const int st = cgrp >> 1, qt = cgrp & 1;
-        // slot p of the block's slab holds piece p ^ ((p >> 4) & 1) of the block's column range (swizzle on the SOURCE address)
-        auto stage_w = [&](int slot, uint32_t ks) {
-            const char *wsrc = reinterpret_cast<const char *>(Wp + ((size_t)ks * dp + col0) * 16);
-            const char *gsrc = SCORE ? reinterpret_cast<const char *>(Gp + (size_t)ks * 192 * 16) : nullptr;
-            char *dst = reinterpret_cast<char *>(sW + slot * DPX * 16);
-#pragma unroll
-            for (int j = 0; j < PER; j++) {
-                uint32_t i = wave + 8 * j;
-                if (i >= (uint32_t)NI) i = NI - 1; // padding instruction: re-fetches the last piece (same bytes, same place)
-                const uint32_t p = i * 64 + lane, g = p ^ ((p >> 4) & 1);
-                const char *src = (!SCORE || g < (uint32_t)(DPB * 2)) ? wsrc + (size_t)g * 16 : gsrc + (size_t)(g - DPB * 2) * 16;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                                 (__attribute__((address_space(3))) void *)(dst + i * 1024), 16, 0, 0);
-            }
-        };
-        f32x16 acc[2][CTB];
-        f32x16 accs; // SCORE: scores of query tile (cgrp & 1) x passage tile (2*rhalf + (cgrp >> 1)); lives in this block only
-#pragma unroll
-        for (int i = 0; i < 16; i++) accs[i] = 0.f;
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-            for (int ct = 0; ct < CTB; ct++)
-#pragma unroll
-                for (int i = 0; i < 16; i++) acc[rt][ct][i] = 0.f;
+#include "encode_ring.cuh" // stage_w, frag, acc = 0, accs = 0 (the score tile lives in the last block only)
         // Everybody is past the barrier that closed the previous block's k-loop, so the ring is free; the previous block's
-        // stores (not FUSED) are retired first so that the counted waits below count DMA instructions only.
+        // stores (not FUSED) are retired first so that the counted waits of the k-loop count DMA instructions only.
         if (!FUSED) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        stage_w(0, 0);
-        if (nks > 1) stage_w(1, 1);
-        for (uint32_t ks = 0; ks < nks; ks++) {
-            // as encode_kernel: (a) my pieces of slab ks have landed, (b) everybody's have and everybody is done reading slab
-            // ks-1, so (c) its slot can take slab ks+2
-            if (ks + 1 < nks) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            if (ks + 2 < nks) stage_w((ks + 2) % RING, ks + 2);
-            const uint16_t *w = sW + (ks % RING) * DPX * 16;
-            bf16x8 a[2], b[CTB];
-#pragma unroll
-            for (int rt = 0; rt < 2; rt++)
-                a[rt] = *reinterpret_cast<const bf16x8 *>(sF + (rhalf * 64 + rt * 32 + l31) * fstride + ks * 16 + lh * 8);
-#pragma unroll
-            for (int ct = 0; ct < CTB; ct++) b[ct] = frag(w, (cgrp * CTB + ct) * 32 + l31, lh);
-#pragma unroll
-            for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-                for (int ct = 0; ct < CTB; ct++)
-                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[rt], b[ct], acc[rt][ct], 0, 0, 0);
-            if (SCORE) {
-                const bf16x8 fb = st ? a[1] : a[0]; // B operand: B[k][j = passage]  (same bytes as the A fragment of F)
-#pragma unroll
-                for (int p = 0; p < 3; p++) {
-                    const bf16x8 g = frag(w, DPB + p * 64 + qt * 32 + l31, lh);
-                    accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g, fb, accs, 0, 0, 0); // C[i = query][j = passage]
-                }
-            }
-        }
+#include "encode_kloop.cuh" // acc = F W over the block's columns, SCORE: accs = G F^T
         __syncthreads(); // every wave is done with the ring (all DMA waited for: a plain barrier)
-
-        // ---- masked mean pooling over the L token rows of a passage: encode_kernel's arithmetic, per block ----
-        if (POOL) {
-#pragma unroll
-            for (int rt = 0; rt < 2; rt++) {
-#pragma unroll
-                for (int g4 = 0; g4 < 4; g4++) {
-                    const int r0 = rhalf * 64 + rt * 32 + 8 * g4 + 4 * lh;
-                    const float m0 = sM[r0], m1 = sM[r0 + 1], m2 = sM[r0 + 2], m3 = sM[r0 + 3];
-#pragma unroll
-                    for (int ct = 0; ct < CTB; ct++) {
-                        float v0 = acc[rt][ct][4 * g4] * m0, v1 = acc[rt][ct][4 * g4 + 1] * m1;
-                        float v2 = acc[rt][ct][4 * g4 + 2] * m2, v3 = acc[rt][ct][4 * g4 + 3] * m3;
-                        if (L == 1) {
-                            v0 /= sC[r0]; v1 /= sC[r0 + 1]; v2 /= sC[r0 + 2]; v3 /= sC[r0 + 3];
-                        } else if (L == 2) {
-                            v0 = (v0 + v1) / sC[r0]; v2 = (v2 + v3) / sC[r0 + 2]; v1 = 0.f; v3 = 0.f;
-                        } else if (L == 4) {
-                            v0 = (((v0 + v1) + v2) + v3) / sC[r0]; v1 = v2 = v3 = 0.f;
-                        } else { // L == 8: tokens 0-3 in the lane with lh = 0, tokens 4-7 in its lh = 1 partner
-                            float s4 = ((v0 + v1) + v2) + v3;
-                            float t = s4 + __shfl_xor(s4, 32, 64);
-                            v0 = lh == 0 ? t / sC[r0] : 0.f; v1 = v2 = v3 = 0.f;
-                        }
-                        acc[rt][ct][4 * g4] = v0; acc[rt][ct][4 * g4 + 1] = v1; acc[rt][ct][4 * g4 + 2] = v2; acc[rt][ct][4 * g4 + 3] = v3;
-                    }
-                }
-            }
-        }
-        // ---- this block's share of the row sums of squares, added by the lane that owns the entry -------------
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++) {
-#pragma unroll
-            for (int reg = 0; reg < 16; reg++) {
-                float p = 0.f;
-#pragma unroll
-                for (int ct = 0; ct < CTB; ct++) p = fmaf(acc[rt][ct][reg], acc[rt][ct][reg], p);
-                p += __shfl_xor(p, 1, 64);
-                p += __shfl_xor(p, 2, 64);
-                p += __shfl_xor(p, 4, 64);
-                p += __shfl_xor(p, 8, 64);
-                p += __shfl_xor(p, 16, 64);
-                if (l31 == 0) sN[cgrp * 128 + rhalf * 64 + rt * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh] += p;
-            }
-        }
+        constexpr bool SN_ADD = true; // this block's share of the row sums of squares is added to the blocks' before it
+#include "encode_pool.cuh" // POOL: acc = masked mean over the L token rows; sN += the block's sums of squares
         // ---- not FUSED: the unnormalised values of the block (normalised in place after the last block) -------
         if (!FUSED) {
 #pragma unroll
@@ -204,44 +79,17 @@ __global__ void __launch_bounds__(512) encode_blocked_kernel(const uint16_t *__r
                     const uint64_t row = row_base + r;
                     if (row < n && (r % L) == 0) {
 #pragma unroll
-                        for (int ct = 0; ct < CTB; ct++) {
-                            const uint32_t col = col0 + (cgrp * CTB + ct) * 32 + l31;
+                        for (int ct = 0; ct < CT; ct++) {
+                            const uint32_t col = col0 + (cgrp * CT + ct) * 32 + l31;
                             if (col < ld_out) E[(size_t)(row / L) * ld_out + col] = col < d ? acc[rt][ct][reg] : 0.f;
                         }
                     }
                 }
             }
         }
-        // ---- SCORE (the last block): score tile, rows (regs) = queries, col (lane & 31) = token row; as encode_kernel ----
-        if constexpr (SCORE) {
+        if constexpr (SCORE) { // the last block
             __syncthreads(); // the sums of squares of every block and column group are in sN
-            const int r = rhalf * 64 + st * 32 + l31;
-            const uint64_t row = row_base + r;
-            const float ss = ((sN[r] + sN[128 + r]) + (sN[256 + r] + sN[384 + r]));
-            float nrm = sqrtf(ss);
-            nrm = nrm < 1e-12f ? 1e-12f : nrm;
-            if (!POOL) {
-                if (row < n) {
-#pragma unroll
-                    for (int reg = 0; reg < 16; reg++) {
-                        const uint32_t q = qt * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-                        if (q < nq) S[(size_t)q * n_rows_s + row] = accs[reg] / nrm;
-                    }
-                }
-            } else {
-                const float m = sM[r];
-                const bool first = (r % L) == 0;
-                const float cnt = first ? sC[r] : 1.f;
-#pragma unroll
-                for (int reg = 0; reg < 16; reg++) {
-                    float v = accs[reg] * m;
-                    if (L >= 2) v += __shfl_xor(v, 1, 64);
-                    if (L >= 4) v += __shfl_xor(v, 2, 64);
-                    if (L >= 8) v += __shfl_xor(v, 4, 64);
-                    const uint32_t q = qt * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-                    if (first && row < n && q < nq) S[(size_t)q * n_rows_s + row / L] = (v / cnt) / nrm;
-                }
-            }
+#include "encode_score.cuh" // S = accs / nrm
         }
     };
 
@@ -276,9 +124,7 @@ __global__ void __launch_bounds__(512) encode_blocked_kernel(const uint16_t *__r
         for (int reg = 0; reg < 16; reg++) {
             const int r = rhalf * 64 + rt * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
             const uint64_t row = row_base + r;
-            const float ss = ((sN[r] + sN[128 + r]) + (sN[256 + r] + sN[384 + r])); // fixed order: reproducible
-            float nrm = sqrtf(ss);
-            nrm = nrm < 1e-12f ? 1e-12f : nrm;
+#include "encode_norm.cuh" // nrm
             if (!(row < n && (r % L) == 0)) continue;
             if (norms_out && cgrp == 0 && l31 == 0) norms_out[row / L] = nrm; // ||W^T f|| before normalisation
             float *erow = E + (size_t)(row / L) * ld_out;

@@ -184,6 +184,60 @@ def test_wide_masked_mean_pooling_provider(la, po, gpu):
     Lc.leann_recompute_close(r)
 
 
+def test_general_kernel_four_tiles_plain(la, po, gpu):
+    """encode_kernel<4, false, false> (encode) and <4, true, false> (search): d = 512 with h = 64, so that the feature-stationary
+    kernel (h = 256 only) is not taken; encode_plan(64, 512) is one block of four tiles.  300 token rows: two full tiles and a tail."""
+    n, h, d, nq, k = 300, 64, 512, 5, 10
+    F, W, ref = _ref(po, n, h, d)
+    Q = _queries(po, W, h, nq)
+    lists = [po.scan_topk(ref, Q[i], k + 5, mode=0) for i in range(nq)]
+    assert _near_tie_share(lists, k) <= 0.02  # on the oracle's scores alone
+    dF, dW, dQ = la.DeviceArray.from_host(F), la.DeviceArray.from_host(W), la.DeviceArray.from_host(Q)
+    r = _create(la, dF, n, h, dW, d)
+    E = _encode(la, r, n, d)
+    print(f"encode {n}x{h}x{d}: max |E - oracle| = {np.abs(E - ref).max():.3e}")
+    assert np.abs(E - ref).max() <= 1e-6
+    assert np.abs(np.linalg.norm(E, axis=1) - 1).max() <= 1e-5
+    gk, gs, gc = _search(la, r, dQ, nq, k)
+    assert (gc == k).all()
+    _check_against_lists(gk, gs, lists, k)
+    la.lib().leann_recompute_close(r)
+
+
+@pytest.mark.parametrize("n,d,L", [(150, 512, 8),   # encode_kernel<4, *, true>: one block of four tiles, lane-partner pooling
+                                   (200, 896, 2),   # encode_blocked_kernel<*, true>, blocks 6 + 1: pair pooling
+                                   (100, 896, 8)])  # ... and lane-partner pooling (__shfl_xor(.., 32))
+def test_general_kernel_pooling_widths(la, po, gpu, n, d, L):
+    """masked mean pooling where test_wide_masked_mean_pooling_provider (L = 4, blocked) and test_masked_mean_pooling_provider
+    (d = 384) do not reach: h = 64 keeps the feature-stationary kernel out, encode_plan(64, 512) is one block of four tiles and
+    encode_plan(64, 896) the blocks 6 + 1; no count of token rows is a multiple of 128.  Tolerances of those two tests."""
+    h, nq, k = 64, 20, 10
+    Lc, chk = la.lib(), la._native.check
+    F = po.synth_features(SEED, h, 64, 1.0, 0, 0, n * L)  # token rows
+    W = po.synth_weights(SEED, h, d)
+    rng = np.random.default_rng(L)
+    mask = (rng.random((n, L)) < 0.7).astype(np.uint8)
+    mask[:5] = 0   # fully padded passages: count clamps to 1e-9 -> zero vector
+    mask[5:10] = 1
+    E = po.recompute_encode_pooled(F, mask, W, L)
+    assert np.abs(E[:5]).max() == 0.0
+    Q = _queries(po, W, h, nq)
+    dF, dW, dM = la.DeviceArray.from_host(F), la.DeviceArray.from_host(W), la.DeviceArray.from_host(mask)
+    r = C.c_void_p()
+    chk(Lc.leann_recompute_create_pooled(dF.ptr, dM.ptr, n, L, h, dW.ptr, d, 0, 0, C.byref(r)))
+    G = _encode(la, r, n, d)
+    print(f"pooled encode {n}x{L}x{h}x{d}: max |E - oracle| = {np.abs(G - E).max():.3e}")
+    assert np.abs(G - E).max() <= 2e-6
+    assert (G[:5] == 0).all()
+    gk, gs, gc = _search(la, r, la.DeviceArray.from_host(Q), nq, k)
+    lists = [po.scan_topk(E, Q[i], k, mode=0) for i in range(nq)]
+    print(f"pooled search: max |score - oracle| = {max(np.abs(gs[i] - s0).max() for i, (_, s0) in enumerate(lists)):.3e}")
+    for i, (k0, s0) in enumerate(lists):
+        assert np.abs(gs[i] - s0).max() <= 1e-5
+        assert len(set(gk[i].tolist()) & set(k0.tolist())) >= k - 1
+    Lc.leann_recompute_close(r)
+
+
 def test_wide_candidate_emission_across_chunks(la, po, gpu, monkeypatch):
     """40 000 passages at d = 1536: one 16k score-slab chunk, then a chunk that emits its survivors straight from the fused kernel
     (twelve weight sub-slices per unit).  Must equal the slab path bit for bit."""
