@@ -229,6 +229,99 @@ __device__ __forceinline__ uint32_t wave_dist_rows_screen(const float4 (&q)[T], 
     return ruled;
 }
 
+// ---- the wide form of the screen (768-d rows, beam_search_screen_kernel<3, R>): the two steps above as two passes over a hop's rows ----
+// H rows per wave go through their hi planes in ONE round trip; what the bound cannot rule out is read afterwards as whole rows, hi and
+// lo together, R at a time.  A hop of up to NW * H rows is then two dependent round trips where R rows per round made it four.  The hi
+// halves of the survivors are not kept (H rows of them next to the lo halves do not fit into the 128 registers the kernel is held to:
+// DESIGN.md §3); their lines were fetched a moment earlier by the same CU, so the second read of them is served by the caches.
+// H: the largest at which the kernel keeps 128 VGPRs, four workgroups per CU and no more scratch than the R-rows-per-round form had.
+#ifndef LEANN_SCREEN_H3
+#define LEANN_SCREEN_H3 7
+#endif
+// Hi pass over rows j0, j0 + NW, .. (at most H of them below n_new) of the hop's unseen ids `snew`, the beam full and `worst` the
+// distance of its last entry.  lb as in wave_dist_rows_screen, bit for bit.  A row ruled out (lb > worst; false for a NaN on either
+// side) gets its key make_key(lb, id) written at once; the others come back as a wave-uniform mask, bit r = row j0 + r * NW.
+template <int T, int H, int NW>
+__device__ __forceinline__ uint32_t wave_screen_hi_rows(const float4 (&q)[T], const uint16_t *__restrict__ Xhi, uint32_t ldp,
+                                                        const uint32_t *snew, uint64_t *skey, uint32_t j0, uint32_t n_new, int lane,
+                                                        float worst, float E) {
+    uint2 h[H][T];
+#pragma unroll
+    for (int r = 0; r < H; r++) {
+        if (j0 + r * NW < n_new) {
+            const uint32_t id = uni(snew[j0 + r * NW]);
+            plane_row_load<T>(Xhi + (size_t)id * ldp, ldp, lane, h[r]);
+        }
+    }
+    uint32_t surv = 0;
+#pragma unroll
+    for (int r = 0; r < H; r++) {
+        if (j0 + r * NW < n_new) {
+            float4 s = make_float4(0.f, 0.f, 0.f, 0.f), a = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int t = 0; t < T; t++) {
+                float4 x;
+                x.x = __uint_as_float(h[r][t].x << 16);
+                x.y = __uint_as_float(h[r][t].x & 0xFFFF0000u);
+                x.z = __uint_as_float(h[r][t].y << 16);
+                x.w = __uint_as_float(h[r][t].y & 0xFFFF0000u);
+                fma4(s, q[t], x);
+                a.x = fmaf(fabsf(q[t].x), fabsf(x.x), a.x);
+                a.y = fmaf(fabsf(q[t].y), fabsf(x.y), a.y);
+                a.z = fmaf(fabsf(q[t].z), fabsf(x.z), a.z);
+                a.w = fmaf(fabsf(q[t].w), fabsf(x.w), a.w);
+            }
+            const float lb = rs_lower_bound(wave_tree_sum(rs_lane_bound(lane4_sum(s), lane4_sum(a))), E);
+            if (lb > worst) {
+                if (lane == 0) skey[j0 + r * NW] = make_key(lb, snew[j0 + r * NW]);
+            } else {
+                surv |= 1u << r;
+            }
+        }
+    }
+    return uni(surv);
+}
+// Survivor pass: the rows j0 + b * NW, b the set bits of the wave-uniform `surv`, read whole — both planes in one round trip, R rows in
+// flight — and their canonical distances (the chain of wave_dist_rows_screen's second step, bit for bit) written as keys.  Each
+// round takes the lowest R set bits, once for the loads and once more for the sums, and reads the ids from `snew` by index both times:
+// arrays of positions and ids filled under `if (m)` cost the kernel 36 B of stack per lane that nothing ever touches.
+template <int T, int R, int NW>
+__device__ __forceinline__ void wave_dist_rows_planes(const float4 (&q)[T], const uint16_t *__restrict__ Xhi, const uint16_t *__restrict__ Xlo,
+                                                      uint32_t ldp, const uint32_t *snew, uint64_t *skey, uint32_t j0, uint32_t surv, int lane) {
+    while (surv) {
+        uint2 h[R][T], l[R][T];
+        uint32_t m = surv;
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            if (m) {
+                const uint32_t id = uni(snew[j0 + (uint32_t)__builtin_ctz(m) * NW]);
+                m &= m - 1u;
+                plane_row_load<T>(Xhi + (size_t)id * ldp, ldp, lane, h[r]);
+                plane_row_load<T>(Xlo + (size_t)id * ldp, ldp, lane, l[r]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            if (surv) {
+                const uint32_t j = j0 + (uint32_t)__builtin_ctz(surv) * NW;
+                surv &= surv - 1u;
+                float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                for (int t = 0; t < T; t++) {
+                    float4 x;
+                    x.x = __uint_as_float((h[r][t].x << 16) | (l[r][t].x & 0xFFFFu));
+                    x.y = __uint_as_float((h[r][t].x & 0xFFFF0000u) | (l[r][t].x >> 16));
+                    x.z = __uint_as_float((h[r][t].y << 16) | (l[r][t].y & 0xFFFFu));
+                    x.w = __uint_as_float((h[r][t].y & 0xFFFF0000u) | (l[r][t].y >> 16));
+                    fma4(acc, q[t], x);
+                }
+                const float dist = 1.0f - wave_tree_sum(lane4_sum(acc));
+                if (lane == 0) skey[j] = make_key(dist, snew[j]);
+            }
+        }
+    }
+}
+
 // Same for bf16 feature rows with the inline norm (recompute-on mode).  Lane l owns elements 256t+4l..+3 again
 // (one 8-byte load per chunk), so the canonical accumulation order is unchanged; only the operands differ.
 template <int T, int R>
@@ -373,7 +466,7 @@ struct SearchLds {
 // LW: adjacency-list ids per lane of wave 0 — 1 for lists of <= 64 ids, 2 for wide graphs (<= 128 ids: lane l holds ids l and 64 + l).
 // Phase B compacts the second half behind the first with a second ballot (the unseen ids keep list order), phase E reduces over both
 // keys of a lane and adds a second rank count; phases C and D already loop over n_new.  LW = 1 compiles to the narrow code unchanged.
-// SCREEN (throughput form of the plain f32 search only): phase C goes through the split planes (wave_dist_rows_screen).
+// SCREEN (throughput form of the plain f32 search only): phase C goes through the split planes (wave_dist_rows_screen; T = 3: its wide form).
 // BF16 (search_bf16.hip): the rows are bf16 (g.X names them, g.row_bytes apart); phase C and the entry go through wave_dist_rows_bf16.
 template <int T, int R, int NW, bool FEAT, bool FILT = false, bool G16 = false, int LW = 1, bool SCREEN = false, bool BF16 = false>
 __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_t qi, unsigned char *smem) {
@@ -549,6 +642,22 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
                 if constexpr (SCREEN) {
                     const bool armed = wsize == ef_l; // a full beam: its last entry is the distance to beat
                     const float worst = orderable_f32(uni((uint32_t)(Wc[wsize - 1] >> 32)));
+                    if constexpr (T == 3) {
+                        // Wide form: one hi-plane round over H rows per wave, then the survivors as whole rows, R at a time.  A beam
+                        // that is not full rules nothing out, so its rows skip the hi round: one round trip per R rows.
+                        constexpr int H = LEANN_SCREEN_H3;
+                        static_assert(H >= 1 && H <= 16, "rows per wave in the hi round");
+                        const uint32_t w = uni((uint32_t)wave);
+                        for (uint32_t j0 = w; j0 < n_new; j0 += NW * H) {
+                            const uint32_t have = min((n_new - j0 + NW - 1) / NW, (uint32_t)H); // rows of this wave in this round
+                            uint32_t surv = (1u << have) - 1u;
+                            if (armed) {
+                                surv = wave_screen_hi_rows<T, H, NW>(q, za->x_hi, za->ldp, s.s_new, s.s_key, j0, n_new, lane, worst, rs_E);
+                                rs_ruled += have - (uint32_t)__popc(surv);
+                            }
+                            wave_dist_rows_planes<T, R, NW>(q, za->x_hi, za->x_lo, za->ldp, s.s_new, s.s_key, j0, surv, lane);
+                        }
+                    } else
                     for (uint32_t j0 = wave; j0 < n_new; j0 += NW * R) {
                         uint32_t ids[R];
                         float dd[R];
@@ -767,8 +876,8 @@ __global__ void __launch_bounds__(NW * 64, (NW == 4 && T == 2) ? LEANN_T2_OCC : 
 }
 // Throughput form (4 waves per query) of the plain search with the split-plane row screen; api.hip launches it only for a handle
 // whose planes are in place (T = 3 and 6: 768-d and 1 536-d rows).
-// Workgroups per CU the compiler is asked to leave registers for: the hi and lo halves of R rows, the query and two sets of
-// accumulators are live together.
+// Workgroups per CU the compiler is asked to leave registers for: the hi and lo halves of R rows (T = 3: the hi halves of
+// LEANN_SCREEN_H3 rows, then both halves of R), the query and two sets of accumulators are live together.
 #ifndef LEANN_SCREEN_OCC3
 #define LEANN_SCREEN_OCC3 4
 #endif
