@@ -2,6 +2,10 @@
 // the screen computes from the upper 16 bits of a row must never exceed the canonical distance computed from the whole row.  Both
 // chains are restated here in the device code's order (lane l owns elements 256 t + 4 l .. + 3; 4 fmaf chains, two in-lane additions,
 // the adjacent-pair tree over 64 lanes), in f32 with fmaf, compiled without contraction.  No GPU.  Prints one JSON object.
+// With a file argument: the file holds cases, each a u32 d (1 .. 4096) followed by d f32 of a query and d f32 of a row; per case one
+// line "<bits of screen_lb> <bits of canon_dist>" in hex, T = ceil(d / 256), from the same two functions — what the device compiles
+// of row_screen.h — so that a second statement of the bound (oracle/oracle.c: orc_screen_lb) can be held to this one bit for bit
+// (tests/test_cpu_row_screen.py).
 #include "../csrc/row_screen.h"
 #include <cstdio>
 #include <cstdlib>
@@ -58,7 +62,23 @@ static void normalize(std::vector<float> &v, int d, float scale) {
     for (int i = 0; i < d; i++) v[i] = (float)(v[i] * n);
 }
 
-int main() {
+static int print_cases(const char *path) {
+    FILE *f = fopen(path, "rb");
+    if (!f) { fprintf(stderr, "row_screen_selftest: cannot open %s\n", path); return 2; }
+    uint32_t d;
+    while (fread(&d, 4, 1, f) == 1) {
+        if (d < 1 || d > 4096) { fprintf(stderr, "row_screen_selftest: d = %u\n", d); fclose(f); return 2; }
+        const int T = ((int)d + 255) / 256;
+        std::vector<float> q(256 * T, 0.f), x(256 * T, 0.f);
+        if (fread(q.data(), 4, d, f) != d || fread(x.data(), 4, d, f) != d) { fprintf(stderr, "row_screen_selftest: short case\n"); fclose(f); return 2; }
+        printf("%08x %08x\n", rs_f32_to_bits(screen_lb(q.data(), x.data(), T)), rs_f32_to_bits(canon_dist(q.data(), x.data(), T)));
+    }
+    fclose(f);
+    return 0;
+}
+
+int main(int argc, char **argv) {
+    if (argc > 1) return print_cases(argv[1]);
     unsigned long long cases = 0, violations = 0, roundtrip_bad = 0, layout_bad = 0;
     double max_gap = 0, min_gap = 1e30; // canonical distance - lower bound (must be >= 0; how sharp the bound is)
     const int dims[] = {768, 1536, 700, 1, 37, 256, 4096};

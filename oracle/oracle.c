@@ -168,6 +168,56 @@ static inline uint32_t key_id(uint64_t k) { return (uint32_t)k; }
 static inline float key_dist(uint64_t k) { return orc_orderable_f32((uint32_t)(k >> 32)); }
 
 /* ============================================================================================
+ * The row screen's lower bound, restated (leann-rs_amd/csrc/row_screen.h (3)-(5); search.cuh: wave_dist_rows_screen).
+ * A second, independent statement: the constants are written out here and row_screen.h is NOT included.
+ *
+ * The device keeps the upper 16 bits of every stored element (the element truncated toward zero) in a plane of its own and computes,
+ * from those halves alone, a number lb <= the canonical distance 1 - orc_dot_canon(q, x).  In the device's order:
+ *   lane l of 64 owns elements 256 t + 4 l .. + 3 of each of the T = ceil(d / 256) chunks, operands zero padded;
+ *   four fmaf chains over t for s (q_i * hi_i), four for a (|q_i| * |hi_i|), four plain sums for |q_i|;
+ *   per lane (c0 + c1) + (c2 + c3) of each, then v_l = fmaf(C, a_l, s_l) with C = 2^-7 + 2^-17;
+ *   the adjacent-pair tree over the 64 lanes: U of the v_l, Q' of the lanes' |q| sums;
+ *   E = fmaf(Q', 2^-119, 2^-100);  lb = 1 - (U + E).
+ * T is the kernel's width: rows of 1 025..1 280 floats (5 chunks) run the 6-chunk kernel, whose sixth chunk lies past the row and
+ * adds fmaf(0, 0, c) = c to every chain and 0 to every |q| sum: exact, so T = ceil(d / 256) here gives the same bits.
+ * ========================================================================================== */
+static float tree64(float *v) {
+    for (int w = 32; w >= 1; w >>= 1)
+        for (int i = 0; i < w; i++) v[i] = v[2 * i] + v[2 * i + 1];
+    return v[0];
+}
+static inline float upper_half(float x) { /* the hi plane's element: the low 16 bits cleared */
+    uint32_t u;
+    memcpy(&u, &x, 4);
+    u &= 0xFFFF0000u;
+    memcpy(&x, &u, 4);
+    return x;
+}
+float orc_screen_lb(const float *q, const float *x, uint32_t d) {
+    const float C = 0x1p-7f + 0x1p-17f; /* exact in f32 */
+    const uint32_t T = (d + 255) / 256;
+    float v[64], qs[64];
+    for (uint32_t l = 0; l < 64; l++) {
+        float s[4] = {0.f, 0.f, 0.f, 0.f}, a[4] = {0.f, 0.f, 0.f, 0.f}, qa[4] = {0.f, 0.f, 0.f, 0.f};
+        for (uint32_t t = 0; t < T; t++)
+            for (uint32_t e = 0; e < 4; e++) {
+                const uint32_t j = 256 * t + 4 * l + e;
+                const float qe = j < d ? q[j] : 0.0f, hi = j < d ? upper_half(x[j]) : 0.0f;
+                s[e] = fmaf(qe, hi, s[e]);
+                a[e] = fmaf(fabsf(qe), fabsf(hi), a[e]);
+                qa[e] = qa[e] + fabsf(qe);
+            }
+        const float sl = (s[0] + s[1]) + (s[2] + s[3]), al = (a[0] + a[1]) + (a[2] + a[3]);
+        v[l] = fmaf(C, al, sl);
+        qs[l] = (qa[0] + qa[1]) + (qa[2] + qa[3]);
+    }
+    const float U = tree64(v);
+    const float E = fmaf(tree64(qs), 0x1p-119f, 0x1p-100f);
+    return 1.0f - (U + E);
+}
+float orc_dist_canon(const float *q, const float *x, uint32_t d) { return 1.0f - orc_dot_canon(q, x, d); }
+
+/* ============================================================================================
  * Recompute / brute-force scan — src/index/recompute.rs:96-109
  * ========================================================================================== */
 typedef struct {
@@ -389,6 +439,9 @@ typedef struct {
     int collect;
     uint64_t *F;
     uint32_t nF, capF;
+    /* counting search: evaluated rows the row screen would rule out (orc_graph_search_counted*) */
+    int screen;
+    uint64_t ruled;
 } ctx_t;
 
 static ctx_t *ctx_new(uint64_t n, uint32_t ef) {
@@ -488,6 +541,12 @@ static void exp_push(ctx_t *c, uint64_t k) {
     c->exp[c->nexp++] = k;
 }
 
+/* The row screen's decision for one evaluated row: its lower bound strictly above the distance of the full beam's last entry as the
+ * expansion began (false for a NaN on either side, so a row with an infinity in it is never ruled out). */
+static inline int screen_rules_out(const orc_graph *g, const float *q, uint32_t id, float worst) {
+    return orc_screen_lb(q, g->X + (size_t)id * g->ld, g->d) > worst;
+}
+
 /* SEARCH-LAYER (Malkov & Yashunin Alg. 2), entry keys in `ep` (dist already known).
  * On return c->W[0..nW) is sorted ascending by (dist, id). */
 static void search_layer_heap(const orc_graph *g, const float *q, const uint64_t *ep, uint32_t nep,
@@ -510,6 +569,10 @@ static void search_layer_heap(const orc_graph *g, const float *q, const uint64_t
         if (c->nW == ef && cur > c->W[0]) break; /* closest candidate is farther than worst result */
         if (level == 0) c->stats[1]++; else c->stats[2]++;
         exp_push(c, cur);
+        /* the row screen's view of this expansion (search.cuh: armed, worst): the beam as the previous expansion left it.  W moves
+         * inside the loop below; these two do not. */
+        const int armed = c->nW == ef;
+        const float worst = key_dist(c->W[0]);
         uint32_t cap;
         const uint32_t *nb = nbrs(g, key_id(cur), level, &cap);
         for (uint32_t t = 0; t < cap; t++) {
@@ -520,6 +583,7 @@ static void search_layer_heap(const orc_graph *g, const float *q, const uint64_t
             c->stamp[e] = c->epoch;
             uint64_t k = mk_key(gdist(g, q, e), e);
             c->stats[0]++;
+            if (c->screen && armed && screen_rules_out(g, q, e, worst)) c->ruled++;
             if (c->collect) filt_push(c, k);
             if (c->nW < ef || k < c->W[0]) {
                 minheap_push(c, k);
@@ -559,6 +623,8 @@ static void search_layer_list(const orc_graph *g, const float *q, const uint64_t
         uint64_t cur = c->W[p];
         if (level == 0) c->stats[1]++; else c->stats[2]++;
         exp_push(c, cur);
+        const int armed = c->nW == L; /* as in search_layer_heap: the list before this expansion touches it */
+        const float worst = key_dist(c->W[c->nW - 1]);
         uint32_t cap;
         const uint32_t *nb = nbrs(g, key_id(cur), level, &cap);
         for (uint32_t t = 0; t < cap; t++) {
@@ -569,6 +635,7 @@ static void search_layer_list(const orc_graph *g, const float *q, const uint64_t
             c->stamp[e] = c->epoch;
             uint64_t k = mk_key(gdist(g, q, e), e);
             c->stats[0]++;
+            if (c->screen && armed && screen_rules_out(g, q, e, worst)) c->ruled++;
             if (c->collect) filt_push(c, k);
             if (c->nW == L && k > c->W[L - 1]) continue;
             uint32_t pos = c->nW < L ? c->nW : L - 1; /* slot that falls off / new tail */
@@ -657,37 +724,68 @@ typedef struct {
     uint64_t *stats;
     const uint8_t *allow; /* optional: bitmap(s) of allowed positions, allow_stride bytes apart per query (0 = shared) */
     uint64_t allow_stride;
+    uint64_t *ruled; /* optional (counting search): per query, the evaluated rows the row screen would rule out */
 } batch_job;
 static void *batch_worker(void *p) {
     batch_job *j = (batch_job *)p;
     ctx_t *c = ctx_new(j->g->n, j->ef > j->k ? j->ef : j->k);
     for (uint64_t i = j->lo; i < j->hi; i++) {
         c->stats[0] = c->stats[1] = c->stats[2] = 0;
+        c->screen = j->ruled != NULL;
+        c->ruled = 0;
         c->allow = j->allow ? j->allow + i * j->allow_stride : NULL;
         graph_search_ctx(j->g, j->Q + i * j->g->d, j->k, j->ef, j->algo, c, j->keys + i * j->k,
                          j->dists + i * j->k, j->counts + i);
         if (j->stats) memcpy(j->stats + i * 3, c->stats, sizeof(c->stats));
+        if (j->ruled) j->ruled[i] = c->ruled;
     }
     ctx_free(c);
     return NULL;
 }
-int orc_graph_search_filtered_batch(const orc_graph *g, const float *Q, uint64_t nq, uint32_t k, uint32_t ef,
-                                    int algo, uint32_t nthreads, const uint8_t *allow, uint64_t allow_stride,
-                                    uint64_t *keys, float *dists, uint32_t *counts, uint64_t *stats);
+static int search_batch_run(const orc_graph *g, const float *Q, uint64_t nq, uint32_t k, uint32_t ef, int algo, uint32_t nthreads,
+                            const uint8_t *allow, uint64_t allow_stride, uint64_t *keys, float *dists, uint32_t *counts,
+                            uint64_t *stats, uint64_t *ruled);
 int orc_graph_search_batch(const orc_graph *g, const float *Q, uint64_t nq, uint32_t k, uint32_t ef,
                            int algo, uint32_t nthreads, uint64_t *keys, float *dists,
                            uint32_t *counts, uint64_t *stats) {
-    return orc_graph_search_filtered_batch(g, Q, nq, k, ef, algo, nthreads, NULL, 0, keys, dists, counts, stats);
+    return search_batch_run(g, Q, nq, k, ef, algo, nthreads, NULL, 0, keys, dists, counts, stats, NULL);
 }
 int orc_graph_search_filtered_batch(const orc_graph *g, const float *Q, uint64_t nq, uint32_t k, uint32_t ef,
                                     int algo, uint32_t nthreads, const uint8_t *allow, uint64_t allow_stride,
                                     uint64_t *keys, float *dists, uint32_t *counts, uint64_t *stats) {
+    return search_batch_run(g, Q, nq, k, ef, algo, nthreads, allow, allow_stride, keys, dists, counts, stats, NULL);
+}
+/* Counting search: orc_graph_search[_batch] and, per query, the number of evaluated rows the split-plane row screen of the device
+ * (search.cuh, beam_search_screen_kernel) would rule out.  Definition, from the kernel's phase C: at the start of each expansion, on
+ * every level (the upper levels run with a beam of one, which is always full), armed = the beam is full and worst = the distance of
+ * its last entry, both as the previous expansion's merge left them; every neighbour newly evaluated by that expansion counts if
+ * armed && orc_screen_lb(q, row) > worst.  The entry point's evaluation is never screened.  Stored-f32 graphs only (-1 otherwise). */
+int orc_graph_search_counted(const orc_graph *g, const float *q, uint32_t k, uint32_t ef, int algo, uint64_t *keys, float *dists,
+                             uint32_t *n_out, uint64_t *stats, uint64_t *ruled) {
+    if (g->feat_h || !ruled) return -1;
+    ctx_t *c = ctx_new(g->n, ef > k ? ef : k);
+    c->screen = 1;
+    graph_search_ctx(g, q, k, ef, algo, c, keys, dists, n_out);
+    if (stats) memcpy(stats, c->stats, sizeof(c->stats));
+    *ruled = c->ruled;
+    ctx_free(c);
+    return 0;
+}
+int orc_graph_search_counted_batch(const orc_graph *g, const float *Q, uint64_t nq, uint32_t k, uint32_t ef, int algo,
+                                   uint32_t nthreads, uint64_t *keys, float *dists, uint32_t *counts, uint64_t *stats,
+                                   uint64_t *ruled /* [nq] */) {
+    if (g->feat_h || !ruled) return -1;
+    return search_batch_run(g, Q, nq, k, ef, algo, nthreads, NULL, 0, keys, dists, counts, stats, ruled);
+}
+static int search_batch_run(const orc_graph *g, const float *Q, uint64_t nq, uint32_t k, uint32_t ef, int algo, uint32_t nthreads,
+                            const uint8_t *allow, uint64_t allow_stride, uint64_t *keys, float *dists, uint32_t *counts,
+                            uint64_t *stats, uint64_t *ruled) {
     if (nthreads < 1) nthreads = 1;
     if (nthreads > nq) nthreads = nq ? (uint32_t)nq : 1;
     pthread_t *th = (pthread_t *)malloc(nthreads * sizeof(pthread_t));
     batch_job *jobs = (batch_job *)malloc(nthreads * sizeof(batch_job));
     for (uint32_t t = 0; t < nthreads; t++) {
-        batch_job j = {g, Q, nq, nq * t / nthreads, nq * (t + 1) / nthreads, k, ef, algo, keys, dists, counts, stats, allow, allow_stride};
+        batch_job j = {g, Q, nq, nq * t / nthreads, nq * (t + 1) / nthreads, k, ef, algo, keys, dists, counts, stats, allow, allow_stride, ruled};
         jobs[t] = j;
         if (nthreads == 1) batch_worker(&jobs[t]);
         else pthread_create(&th[t], NULL, batch_worker, &jobs[t]);

@@ -56,6 +56,12 @@ float orc_dot_fast(const float *a, const float *b, uint32_t d);      /* plain AV
 void orc_set_vamana_two_stage(int on);                             /* RobustPrune form of the builders: 1 (default) = DiskANN's occlude_list, 0 = the paper's Alg. 2 */
 void orc_set_fast_dot(int on);                                      /* graph search uses orc_dot_fast (timing only) */
 
+/* The lower bound the device's split-plane row screen computes for one row from the upper 16 bits of its elements, restated from the
+ * definition in leann-rs_amd/csrc/row_screen.h (3)-(5) in the device's order (oracle.c); orc_dist_canon: 1 - orc_dot_canon, the
+ * distance it bounds.  lb <= dist always; a NaN or an infinity in the row makes lb NaN or -inf. */
+float orc_screen_lb(const float *q, const float *x, uint32_t d);
+float orc_dist_canon(const float *q, const float *x, uint32_t d);
+
 uint32_t orc_f32_orderable(float f);
 float orc_orderable_f32(uint32_t u);
 
@@ -95,6 +101,14 @@ int orc_graph_search(const orc_graph *g, const float *q, uint32_t k, uint32_t ef
 int orc_graph_search_batch(const orc_graph *g, const float *Q, uint64_t nq, uint32_t k, uint32_t ef,
                            int algo, uint32_t nthreads, uint64_t *keys, float *dists,
                            uint32_t *counts, uint64_t *stats /* [nq*3] or NULL */);
+/* Counting search: the same walk and outputs, and in ruled[i] the evaluated rows of query i that the device's row screen would rule
+ * out: those with armed && orc_screen_lb > worst, armed / worst = the beam full / its last entry's distance as each expansion begins
+ * (oracle.c).  Stored-f32 graphs only: -1 for a recompute-on graph. */
+int orc_graph_search_counted(const orc_graph *g, const float *q, uint32_t k, uint32_t ef, int algo,
+                             uint64_t *keys, float *dists, uint32_t *n_out, uint64_t *stats, uint64_t *ruled);
+int orc_graph_search_counted_batch(const orc_graph *g, const float *Q, uint64_t nq, uint32_t k, uint32_t ef,
+                                   int algo, uint32_t nthreads, uint64_t *keys, float *dists,
+                                   uint32_t *counts, uint64_t *stats /* [nq*3] or NULL */, uint64_t *ruled /* [nq] */);
 /* Filtered variants: `allow` = bitmap over positions (bit i of byte i>>3); same traversal as the
  * unfiltered search, answer = k best allowed keys among all keys evaluated on the final layer. */
 int orc_graph_search_filtered(const orc_graph *g, const float *q, uint32_t k, uint32_t ef, int algo,

@@ -44,6 +44,10 @@ def lib():
             f = getattr(L, n)
             f.restype = C.c_float
             f.argtypes = [f32p, f32p, C.c_uint32]
+        for n in ("orc_screen_lb", "orc_dist_canon"):
+            f = getattr(L, n)
+            f.restype = C.c_float
+            f.argtypes = [f32p, f32p, C.c_uint32]
         L.orc_scan_topk.argtypes = [f32p, C.c_uint64, C.c_uint32, f32p, C.c_uint32, C.c_int, u8p,
                                     u64p, f32p, u32p]
         L.orc_level.restype = C.c_uint32
@@ -66,6 +70,9 @@ def lib():
                                        f32p, u32p, u64p]
         L.orc_graph_search_batch.argtypes = [C.c_void_p, f32p, C.c_uint64, C.c_uint32, C.c_uint32,
                                              C.c_int, C.c_uint32, u64p, f32p, u32p, u64p]
+        L.orc_graph_search_counted.argtypes = [C.c_void_p, f32p, C.c_uint32, C.c_uint32, C.c_int, u64p, f32p, u32p, u64p, u64p]
+        L.orc_graph_search_counted_batch.argtypes = [C.c_void_p, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32,
+                                                     u64p, f32p, u32p, u64p, u64p]
         L.orc_graph_search_filtered_batch.argtypes = [C.c_void_p, f32p, C.c_uint64, C.c_uint32, C.c_uint32,
                                                       C.c_int, C.c_uint32, u8p, C.c_uint64, u64p, f32p, u32p, u64p]
         L.orc_graph_search_level.argtypes = [C.c_void_p, f32p, C.c_uint32, C.c_uint32, C.c_int, u64p, u32p, u64p,
@@ -104,6 +111,22 @@ def dot(a, b, kind="canon"):
     a = np.ascontiguousarray(a, np.float32)
     b = np.ascontiguousarray(b, np.float32)
     return float(getattr(lib(), "orc_dot_" + kind)(_p(a, f32p), _p(b, f32p), a.shape[0]))
+
+
+def screen_lb(q, x):
+    """oracle.c:orc_screen_lb — the row screen's lower bound on dist_canon(q, x), from the upper 16 bits of x alone (np.float32)"""
+    q = np.ascontiguousarray(q, np.float32)
+    x = np.ascontiguousarray(x, np.float32)
+    assert q.shape == x.shape and q.ndim == 1
+    return np.float32(lib().orc_screen_lb(_p(q, f32p), _p(x, f32p), q.shape[0]))
+
+
+def dist_canon(q, x):
+    """1 - the canonical dot product, in f32: the distance the traversal kernels compute (np.float32)"""
+    q = np.ascontiguousarray(q, np.float32)
+    x = np.ascontiguousarray(x, np.float32)
+    assert q.shape == x.shape and q.ndim == 1
+    return np.float32(lib().orc_dist_canon(_p(q, f32p), _p(x, f32p), q.shape[0]))
 
 
 def scan_topk(X, q, k, mode=0, allow_mask=None):
@@ -199,6 +222,21 @@ class Graph:
         lib().orc_graph_search_batch(self.h, _p(Q, f32p), nq, k, ef, algo, nthreads, _p(keys, u64p),
                                      _p(dists, f32p), _p(counts, u32p), _p(stats, u64p))
         return keys, dists, counts, stats
+
+    def search_counted_batch(self, Q, k, ef, algo=0, nthreads=1):
+        """search_batch + ruled [nq]: per query, the evaluated rows the device's row screen would rule out (oracle.h)"""
+        Q = np.ascontiguousarray(Q, np.float32)
+        nq = Q.shape[0]
+        keys = np.full((nq, k), 0xFFFFFFFFFFFFFFFF, np.uint64)
+        dists = np.full((nq, k), np.inf, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        stats = np.zeros((nq, 3), np.uint64)
+        ruled = np.zeros(nq, np.uint64)
+        rc = lib().orc_graph_search_counted_batch(self.h, _p(Q, f32p), nq, k, ef, algo, nthreads, _p(keys, u64p), _p(dists, f32p),
+                                                  _p(counts, u32p), _p(stats, u64p), _p(ruled, u64p))
+        if rc != 0:
+            raise ValueError("the counting search walks stored-f32 graphs only")
+        return keys, dists, counts, stats, ruled
 
     def search_filtered_batch(self, Q, k, ef, allow, algo=0, nthreads=1):
         """allow: uint8 bitmap [ceil(n/8)] shared by all queries, or [nq, stride] one per query."""

@@ -37,6 +37,22 @@ int main(void) {
         for (uint32_t i = 0; i < 10; i++) { pid[i] = (uint32_t)bk[i]; pd[i] = orc_orderable_f32((uint32_t)(bk[i] >> 32)); }
         if (orc_prune(X, d, d, pid, pd, 10, 4, 1.2f, 1, pos) < 1 || orc_prune(X, d, d, pid, pd, 10, 4, 0.0f, 0, pos) < 1) { puts("FAIL: prune"); return 1; }
     }
+    {   /* the counting search: same answers as the plain one, something ruled out, the bound below the distance */
+        uint64_t ck[40 * 10], cst[40 * 3], ruled[40], r1, total = 0; float cd[40 * 10]; uint32_t cc[40];
+        for (int algo = 0; algo < 2; algo++) {
+            if (orc_graph_search_counted_batch(g, Q, nq, 10, 50, algo, 3, ck, cd, cc, cst, ruled)) { puts("FAIL: counted batch"); return 1; }
+            if (memcmp(ck, keys[0], sizeof ck) || memcmp(cd, dist[0], sizeof cd) || memcmp(cc, cnt[0], sizeof cc)) { puts("FAIL: counted != plain"); return 1; }
+            if (algo == 0 && memcmp(cst, st, sizeof cst)) { puts("FAIL: counted stats"); return 1; }
+            for (uint32_t i = 0; i < nq; i++) { total += ruled[i]; if (ruled[i] >= cst[3 * i]) { puts("FAIL: more ruled out than evaluated"); return 1; } }
+            if (orc_graph_search_counted(g, Q, 10, 50, algo, k2, d2, &c2, s2, &r1) || r1 != ruled[0]) { puts("FAIL: counted single"); return 1; }
+        }
+        if (!total) { puts("FAIL: nothing ruled out"); return 1; }
+        orc_graph_search_counted(v, Q, 1, 1, 1, k2, d2, &c2, s2, &r1);
+        for (uint32_t i = 0; i < 200; i++)
+            if (!(orc_screen_lb(Q, X + (size_t)i * d, d) <= orc_dist_canon(Q, X + (size_t)i * d, d))) { puts("FAIL: lb > dist"); return 1; }
+        float one = 1.0f;
+        if (!(orc_screen_lb(&one, &one, 1) <= 0.0f)) { puts("FAIL: lb, d = 1"); return 1; }
+    }
     uint64_t sk[5]; float ss[5]; uint32_t sn; uint8_t mask[(1500 + 7) / 8]; memset(mask, 0x55, sizeof mask);
     orc_scan_topk(X, n, d, Q, 5, 0, mask, sk, ss, &sn);
     uint64_t mk[10]; float md[10]; uint32_t mn;

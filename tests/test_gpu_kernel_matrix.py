@@ -28,6 +28,11 @@ T = ceil(ld / 256) picks <T, R> (R rows in flight per wave); the batch picks NW 
   * wide_beam_search_kernel / wide_beam_search_filtered_kernel <T,R,16|4> (lists of more than 64 ids): test_gpu_wide_degree.py.
   * beam_search_screen_kernel<3, 4> / <6, 2> (split planes, 4-wave unfiltered batches): test_gpu_row_screen.py, whose fixture dims
     520, 700, 768 run <3, 4> and 1100, 1280 (T = 5 in the 6-kernel), 1536 run <6, 2>.
+    test_gpu_row_screen_wide.py: <3, 4> over lists of 64 (M = 32).  test_gpu_row_screen_edges.py: 516 (<3, 4>) and 1028 (<6, 2>, the
+    sixth chunk wholly past the plane row) — plane rows ending in a 64-element tail —, <6, 2> over lists of 64 (1100, M = 32), Vamana
+    handles (R = 32 / 64 at 768, R = 32 at 1100), LEANN_DEBUG_HASH_BITS=8 (every query moves to the HBM pool inside <3, 4> and <6, 2>),
+    nq = 641 | 640 | 384 on one handle, k = ef = 1, rows x 37.5 / queries x 1e-3 and rows x 1e-30 / queries x 1e-10, rows holding an
+    infinity, a two-shard composite handle.  All three files hold the device's ruled-out count to the oracle's counting search.
 
 Recompute-on graphs (bf16 feature rows, family FEAT / FEAT256 of search_plan.h; 16 waves for nq <= 512, else 4; "rc" = test_recompute_on_wide_features):
 

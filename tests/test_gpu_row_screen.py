@@ -1,7 +1,9 @@
 """-m gpu: the split-plane row screen of the throughput beam search (csrc/row_screen.h, planes.hip, search.cuh).  Batches of more than
 640 unfiltered queries read a neighbour's upper 16-bit halves first and its lower halves only if a proved lower bound does not put it
 behind the full beam.  Bar: ids, distance bits, counts and stats equal with the screen on, with it off, and in the oracle walking the
-exported graph; the counters show that rows were in fact ruled out."""
+exported graph; and the number of rows the device ruled out equals, exactly, the number the oracle's restatement of the decision
+(oracle.c: orc_screen_lb, the counting search) rules out on the same walk.  A bound that is too weak changes no answer, only that count;
+one that is too strong changes it too, whether or not the wrongly dropped row would have entered a beam."""
 import numpy as np
 import pytest
 
@@ -46,14 +48,17 @@ def _same(a, b):
         assert a["stats"][f] == b["stats"][f], f
 
 
-def _same_as_oracle(a, G, Q, k, ef):
-    ok, od, oc, ost = G.search_batch(Q, k, ef, 0, nthreads=8)
+def _same_as_oracle(a, G, Q, k, ef, algo=0):
+    """answers and visit counters as the oracle's, and the device's ruled-out total as the oracle's count; returns that count"""
+    ok, od, oc, ost, oruled = G.search_counted_batch(Q, k, ef, algo, nthreads=8)
     assert (a["counts"] == oc).all()
     assert (a["keys"] == ok).all(), f"ids differ from the oracle's in {(a['keys'] != ok).any(axis=1).sum()} queries"
     assert (a["dists"].view(np.uint32) == od.view(np.uint32)).all()
     assert a["stats"]["n_dist_evals"] == int(ost[:, 0].sum())
     assert a["stats"]["n_hops_base"] == int(ost[:, 1].sum())
     assert a["stats"]["n_hops_upper"] == int(ost[:, 2].sum())
+    assert a["ruled"] == int(oruled.sum()), f"ruled out: device {a['ruled']}, oracle {int(oruled.sum())}"
+    return int(oruled.sum())
 
 
 # 1100: T = 5 in the 6-kernel, plane rows of 1152 (two interleaved blocks + a 128-element tail, the sixth chunk reads as zeros);
@@ -151,7 +156,8 @@ def test_planes_are_cut_when_a_handle_is_made(la, po, gpu, monkeypatch):
 def test_planes_follow_appended_and_removed_rows(la, po, gpu, tmp_path, monkeypatch):
     """add_to_index, then a removal with consolidation.  The handle is opened with LEANN_ROW_SCREEN=1, so its planes are cut by the open
     itself, from the file add_to_index wrote: the first search screens (ruled out > 0 before any set_row_screen call), returns appended
-    rows, and agrees with the whole-row path; so do the searches after the removal and the repair."""
+    rows, and agrees with the whole-row path; so do the searches after the removal and the repair.  Both times the oracle walks the graph
+exported at that moment and its count of ruled-out rows is the device's."""
     d, n_old, n_add = 768, 3000, 1000
     X = synth(po, n_old + n_add, d, n_clusters=2)
     Q = synth(po, NQ, d, stream=1, n_clusters=2)
@@ -166,6 +172,8 @@ def test_planes_follow_appended_and_removed_rows(la, po, gpu, tmp_path, monkeypa
     on = _search_counted(s, Q, 10, 56)
     assert on["ruled"] > 0 and on["ruled"] + on["full"] == on["stats"]["n_dist_evals"] - NQ
     assert (on["keys"] >= n_old).any()  # appended rows are among the answers
+    g = s.graph_export()
+    _same_as_oracle(on, po.Graph.from_arrays(X, M, 2 * M, g["max_level"], g["entry"], g["levels"], g["upper_off"], g["adj0"], g["adjU"]), Q, 10, 56)
     s.set_row_screen(False)
     off = _search_counted(s, Q, 10, 56)
     assert off["ruled"] == 0 and off["full"] == 0
@@ -179,4 +187,6 @@ def test_planes_follow_appended_and_removed_rows(la, po, gpu, tmp_path, monkeypa
     _same(on, off)
     assert off["ruled"] == 0 and on["ruled"] > 0 and on["ruled"] + on["full"] == on["stats"]["n_dist_evals"] - NQ
     assert not np.isin(on["keys"], gone).any()
+    g = s.graph_export()  # after the repair no live list names a removed row: the plain walk of the export is the search
+    _same_as_oracle(on, po.Graph.from_arrays(X, M, 2 * M, g["max_level"], g["entry"], g["levels"], g["upper_off"], g["adj0"], g["adjU"]), Q, 10, 56)
     s.close()

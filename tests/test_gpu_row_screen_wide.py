@@ -2,7 +2,8 @@
 wave, then the survivors read as whole rows, 4 at a time; hops of an unfilled beam skip the hi round.  test_gpu_row_screen.py builds
 M = 16 graphs, whose lists hold at most 32 ids: one wide round, never full.  Here M = 32 — level-0 lists of 64 ids, so hops of more than
 one wide round and hops at and just past 4 * H rows — and the same bar: ids, distance bits, counts and stats equal with the screen on,
-with it off, and in the oracle walking the exported graph; ruled out + read in full = every evaluation but the entry points'."""
+with it off, and in the oracle walking the exported graph; the device's ruled-out total equal to the oracle's count on the same walk
+(_same_as_oracle); ruled out + read in full = every evaluation but the entry points'."""
 import numpy as np
 import pytest
 
