@@ -9,6 +9,80 @@ def synth(po, n, d, stream=0, i0=0, r=64, n_clusters=256, sigma=1.0, seed=SEED):
     return po.gen_rows(seed, d, r, n_clusters, sigma, stream, i0, n)
 
 
+class HipStreams:
+    """n non-blocking HIP streams (hipStreamCreateWithFlags(.., hipStreamNonBlocking)) for the stream= parameters of backend.py, made
+    with ctypes on the HIP runtime libleann_hip.so links — symbols are looked up through the library's own handle, so no second
+    runtime is loaded and no torch is needed.  streams[i] is the integer those parameters accept; `with HipStreams(la, 8) as st:`
+    destroys them.  call(name, ...) is any runtime function of SIGNATURES, checked: a non-zero hipError_t raises."""
+    import ctypes as _C
+    NON_BLOCKING = 1  # hipStreamNonBlocking
+    D2H, D2D = 2, 3   # hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice
+    _vp, _vpp = _C.c_void_p, _C.POINTER(_C.c_void_p)
+    SIGNATURES = {
+        "hipStreamCreateWithFlags": [_vpp, _C.c_uint],
+        "hipStreamDestroy": [_vp],
+        "hipStreamSynchronize": [_vp],
+        "hipMemcpyAsync": [_vp, _vp, _C.c_size_t, _C.c_int, _vp],
+        "hipEventCreateWithFlags": [_vpp, _C.c_uint],
+        "hipEventDestroy": [_vp],
+        "hipEventRecord": [_vp, _vp],
+        "hipStreamWaitEvent": [_vp, _vp, _C.c_uint],
+        "hipStreamBeginCapture": [_vp, _C.c_int],
+        "hipStreamEndCapture": [_vp, _vpp],
+        "hipGraphInstantiate": [_vpp, _vp, _vpp, _C.c_char_p, _C.c_size_t],
+        "hipGraphLaunch": [_vp, _vp],
+        "hipGraphExecDestroy": [_vp],
+        "hipGraphDestroy": [_vp],
+    }
+
+    def __init__(self, la, n):
+        self._rt = la.lib()
+        self._rt.hipGetErrorString.restype = self._C.c_char_p
+        self._rt.hipGetErrorString.argtypes = [self._C.c_int]
+        self.streams = []
+        for _ in range(n):
+            self.streams.append(self.create("hipStreamCreateWithFlags", self.NON_BLOCKING))
+
+    def call(self, name, *args):
+        f = getattr(self._rt, name)
+        f.restype, f.argtypes = self._C.c_int, self.SIGNATURES[name]
+        rc = f(*args)
+        if rc != 0:
+            raise RuntimeError(f"{name}: hipError {rc}: {self._rt.hipGetErrorString(rc).decode('utf-8', 'replace')}")
+
+    def create(self, name, *args):
+        """a runtime function whose first parameter is the address the new handle is written to; returns the handle as an integer"""
+        out = self._C.c_void_p()
+        self.call(name, self._C.byref(out), *args)
+        return out.value
+
+    def synchronize(self, stream):
+        self.call("hipStreamSynchronize", stream)
+
+    def copy_async(self, dst, src, nbytes, kind, stream):
+        self.call("hipMemcpyAsync", dst, src, nbytes, kind, stream)
+
+    def __len__(self):
+        return len(self.streams)
+
+    def __iter__(self):
+        return iter(self.streams)
+
+    def __getitem__(self, i):
+        return self.streams[i]
+
+    def close(self):
+        for s in self.streams:
+            self.call("hipStreamDestroy", s)
+        self.streams = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def recall_at_k(found, truth):
     k = truth.shape[1]
     hits = 0
