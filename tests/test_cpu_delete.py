@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import consolidate_ref as cr
+import delete_cases as dc
 
 
 def _err(la):
@@ -132,3 +133,89 @@ def test_reference_prune_rules():
     # two stages: the first walk (alpha = 1) drops c2 (1 <= 1); the relaxed second walk takes it back
     assert cr.prune(X, cid, cd, 3, 1.2, True) == [0, 2]
     assert cr.prune(X, cid, cd, 3, 1.0, True) == [0]         # alpha = 1: one stage by definition
+
+
+# ---- the cases of tests/test_gpu_delete_edges.py, on the reference alone ------------------------------------------------------
+
+def test_sparse_rows_keep_the_exactness_argument():
+    rng = np.random.default_rng(1)
+    for rows, nnz in (("sparse", 3), ("mixed", 8), ("dense", 0)):
+        X = cr.random_graph(rng, "diskann", 64, 4096, 4, 4, 0, rows=rows, nnz=nnz)["X"]
+        assert X.dtype == np.float32 and (X * 8 == np.round(X * 8)).all() and np.abs(X).max() <= 0.25
+        if rows == "sparse":
+            assert ((X != 0).sum(axis=1) == nnz).all()
+        if rows == "mixed":
+            assert ((X[1::2] != 0).sum(axis=1) == nnz).all() and ((X[0::2] != 0).sum(axis=1) > 2000).all()
+        # |dot| <= 4096 / 16 = 256 in multiples of 1/64: 2^14 steps, exact in f32 whatever the order of the sum
+        assert (np.abs(X.astype(np.float64) @ X.astype(np.float64).T) <= 256).all()
+    # the dense recipe draws what it always drew: graphs of the older tests keep their bytes
+    a = cr.random_graph(np.random.default_rng(7), "hnsw", 64, 16, 4, 8, 2)
+    b = cr.random_graph(np.random.default_rng(7), "hnsw", 64, 16, 4, 8, 2, rows="dense", nnz=5)
+    assert (a["X"] == b["X"]).all() and (a["adj0"] == b["adj0"]).all() and (a["adjU"] == b["adjU"]).all()
+    assert (a["X"] == (np.random.default_rng(7).integers(-2, 3, (64, 16)) / 8.0).astype(np.float32)).all()
+
+
+@pytest.mark.parametrize("name", list(dc.CASES))
+def test_case_reaches_the_branch_it_is_there_for(name):
+    c = dc.CASES[name]
+    g, removed, special = dc.graph(name)
+    want = dc.reference(name)
+    dc.check_needs(name, want)
+    cn = want["counters"]
+    assert c["n"] % 8 and c["n"] % 256 and removed[g["entry"]] and not removed[want["entry"]]
+    assert cr.pool_size(g) == (256 if max(c["M"], c["M0"]) > 64 else 128)
+    assert cr.pending(g, removed) > 0 and cr.pending(want, removed) == 0
+    assert cn["repairs"] == sum(cn[k] for k in ("pools_0", "pools_1", "pools_2_32", "pools_33_64", "pools_65_128", "pools_129_255")) + \
+        (cn["pools_eq_nc"] if cr.pool_size(g) == 256 else 0)
+    l0 = g["adj0"]
+    clean = ~removed & ~(removed[np.where(l0 == cr.EMPTY, 0, l0)] & (l0 != cr.EMPTY)).any(axis=1)
+    assert clean.sum() >= 8 and (want["adj0"][clean] == l0[clean]).all()
+    lens = (want["adj0"][~removed & ~clean] != cr.EMPTY).sum(axis=1)     # every other live level-0 list was repaired
+    assert cn["lists_gt64"] >= int((lens > 64).sum()) and want["counters_by_level"][0]["lists_full"] == int((lens == c["M0"]).sum())
+    if "full_dead" in special:                                   # width + 1 sources: width * (width + 1) slots
+        l = l0[special["full_dead"]]
+        assert (l != cr.EMPTY).all() and removed[l].all() and len(set(l.tolist())) == c["M0"] == 128
+        assert (c["M0"] + 1) * c["M0"] == 16512 and -(-16512 // 256) == 65
+    if "empty_pool" in special:
+        assert (want["adj0"][special["empty_pool"]] == cr.EMPTY).all()
+
+
+def test_reference_states():
+    """the states of test_gpu_delete_edges.py as the reference sees them"""
+    rng = np.random.default_rng(23)
+    g = cr.random_graph(rng, "hnsw", 515, 40, 8, 16, 2)
+    everything = cr.consolidate(g, np.ones(515, bool))
+    assert (everything["adj0"] == cr.EMPTY).all() and (everything["adjU"] == cr.EMPTY).all()
+    assert everything["entry"] == g["entry"] and everything["max_level"] == g["max_level"] and everything["counters"]["repairs"] == 0
+    removed = g["levels"] >= 1
+    flat = cr.consolidate(g, removed)
+    assert flat["max_level"] == 0 and flat["entry"] == np.flatnonzero(~removed)[0] and (flat["adjU"] == cr.EMPTY).all()
+    assert flat["counters_by_level"][1]["repairs"] == 0 and flat["counters_by_level"][0]["repairs"] > 0
+    # a second round on a repaired graph: the repaired lists are the old lists of the next pass
+    first = rng.random(515) < 0.25
+    one = cr.consolidate(g, first)
+    second = first | (rng.random(515) < 0.15)
+    two = cr.consolidate(one, second)
+    assert cr.pending(one, second) > 0 and cr.pending(two, second) == 0
+    assert (two["adj0"] != cr.consolidate(g, second)["adj0"]).any()    # not the same as removing everything at once
+
+
+@pytest.mark.parametrize("alpha,two_stage", [(0.0, True), (1.2, False), (1.2, True)])
+def test_reference_prune_matches_the_oracle_past_64_kept(po, alpha, two_stage):
+    """cr.prune against the C oracle's prune on one wide pool: 256 candidates, limit 128, rows sparse enough that more than 64 are
+    kept and one dense row so that every rule drops some — the numpy rule is then not the only statement of that path"""
+    rng = np.random.default_rng(256)
+    X = cr.sparse_rows(rng, 300, 256, 3)
+    X[7] = (rng.integers(-2, 3, 256) / 8.0).astype(np.float32)
+    ids = np.concatenate([[7], rng.choice(np.arange(8, 300), 255, replace=False)])
+    d = (np.float32(1.0) - (X[ids].astype(np.float64) @ X[0].astype(np.float64)).astype(np.float32)).astype(np.float32)
+    o = np.lexsort((ids, d))
+    ids, d = ids[o], d[o]
+    want = po.prune(X, ids, d, 128, alpha, two_stage).tolist()
+    info = {}
+    got = list(cr.prune(X, ids.astype(np.int64), d, 128, alpha, two_stage, info))
+    assert got == want and 64 < len(got) <= 128
+    # the rule dropped something on the way (one-stage alpha = 1.2 needs a dot of 1/6 to drop: rows of three 1/8ths hardly have one)
+    assert got != list(range(len(got))) or (alpha > 1 and not two_stage)
+    assert (info["second_stage"] > 0) == (two_stage and alpha > 1)
+    assert len(cr.prune(X, ids.astype(np.int64), d, 64, alpha, two_stage)) == 64
