@@ -12,7 +12,7 @@ HOST     := leann-rs_amd/host
 CXXFLAGS := -O2 -std=c++17 -ffp-contract=off -Wall -Wextra -Wno-unused-parameter
 
 all: $(CSRC)/libleann_hip.so oracle $(HOST)/leann $(HOST)/host_selftest $(HOST)/host_selftest_asan $(HOST)/serve_bench $(HOST)/row_screen_selftest \
-     $(HOST)/encode_plan_selftest $(HOST)/search_plan_selftest
+     $(HOST)/encode_plan_selftest $(HOST)/search_plan_selftest $(HOST)/device_mem_selftest
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -53,12 +53,18 @@ $(HOST)/search_plan_selftest: $(HOST)/search_plan_selftest.cpp $(CSRC)/search_pl
 	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -o $@ \
 	    $(HOST)/search_plan_selftest.cpp
 
+# the owning device-buffer type (csrc/device_mem.h) over a counting malloc / free, on the CPU under AddressSanitizer + UBSan: no GPU,
+# no library
+$(HOST)/device_mem_selftest: $(HOST)/device_mem_selftest.cpp $(CSRC)/device_mem.h include/leann_backend.h
+	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -o $@ \
+	    $(HOST)/device_mem_selftest.cpp
+
 oracle:
 	$(MAKE) -s -C oracle
 
 clean:
 	rm -f $(CSRC)/*.o $(CSRC)/*.so $(HOST)/leann $(HOST)/host_selftest $(HOST)/host_selftest_asan $(HOST)/serve_bench $(HOST)/row_screen_selftest \
-	      $(HOST)/encode_plan_selftest $(HOST)/search_plan_selftest
+	      $(HOST)/encode_plan_selftest $(HOST)/search_plan_selftest $(HOST)/device_mem_selftest
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

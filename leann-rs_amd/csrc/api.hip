@@ -104,6 +104,20 @@ extern "C" int leann_device_free(void *p) {
     if (p) HIP_CHECK_RET(hipFree(p));
     return LEANN_OK;
 }
+// the two functions every DeviceBuf (device_mem.h) allocates and frees through
+void *leann_internal_device_alloc(size_t bytes) {
+    void *p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    return p;
+}
+void leann_internal_device_release(void *p) { (void)hipFree(p); }
+int leann_internal_check_device(int device) {
+    int ndev = 0;
+    leann_device_count(&ndev);
+    if (device >= 0 && device < ndev) return LEANN_OK;
+    leann_set_error("HIP device %d not available (%d visible). This library has no CPU fallback.", device, ndev);
+    return LEANN_ERR_DEVICE;
+}
 extern "C" int leann_device_upload(void *d, const void *h, size_t bytes) {
     HIP_CHECK_RET(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));
     return LEANN_OK;
@@ -120,17 +134,9 @@ extern "C" int leann_device_sync(int device) {
 
 extern "C" int leann_backend_set_coalescing(leann_backend *h, uint32_t wait_us, uint32_t max_batch);
 // ---- handle (structs in internal.h) ---------------------------------------------------------------
-static void ws_free(Workspace *w) {
-    if (!w) return;
-    (void)hipFree(w->d_q);
-    (void)hipFree(w->d_keys);
-    (void)hipFree(w->d_dists);
-    (void)hipFree(w->d_counts);
-    (void)hipFree(w->d_stats);
-    (void)hipFree(w->d_allow);
-    if (w->pin) (void)hipHostFree(w->pin);
-    if (w->stream) (void)hipStreamDestroy(w->stream);
-    delete w;
+Workspace::~Workspace() { // (the six buffers free themselves)
+    if (pin) (void)hipHostFree(pin);
+    if (stream) (void)hipStreamDestroy(stream);
 }
 static uint32_t debug_bits(int knob, uint32_t lo, uint32_t hi, uint32_t dflt) { // test hooks: force tiny visited tables
     return knob >= (int)lo && knob <= (int)hi ? (uint32_t)knob : dflt;
@@ -141,8 +147,8 @@ static uint32_t debug_bits(int knob, uint32_t lo, uint32_t hi, uint32_t dflt) { 
 static int ensure_gpool(leann_backend *h) {
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->gpool) return LEANN_OK;
-    unsigned long long *p = nullptr, *p2 = nullptr;
-    uint32_t *lock = nullptr, *lock2 = nullptr;
+    DeviceBuf<unsigned long long> p, p2; // this call's own until the last lines: a failing return frees them
+    DeviceBuf<uint32_t> lock, lock2;
     const uint32_t bits = debug_bits(leann_knobs().gpool_bits, 6, GPOOL_BITS, GPOOL_BITS), tables = GPOOL_TABLES;
     const size_t slots = (size_t)tables << bits;
     uint32_t bits2 = 0, tables2 = 0;
@@ -155,17 +161,14 @@ static int ensure_gpool(leann_backend *h) {
         tables2 = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(2, (1ull << 30) / per));
     }
     auto fail = [&](const char *what) {
-        (void)hipFree(p); (void)hipFree(p2); (void)hipFree(lock); (void)hipFree(lock2);
         leann_set_error("visited-table pool: %s failed: %s", what, hipGetErrorString(hipGetLastError()));
         return LEANN_ERR_DEVICE;
     };
-    if (hipMalloc((void **)&p, slots * 8) != hipSuccess) return fail("hipMalloc");
-    if (hipMalloc((void **)&lock, (tables + 4) * 4) != hipSuccess) return fail("hipMalloc");
+    if (p.alloc(slots) || lock.alloc(tables + 4)) return LEANN_ERR_DEVICE;
     if (hipMemset(p, 0, slots * 8) != hipSuccess) return fail("hipMemset"); // generation 0 is never issued
     if (hipMemset(lock, 0, (tables + 4) * 4) != hipSuccess) return fail("hipMemset");
     if (tables2) {
-        if (hipMalloc((void **)&p2, ((size_t)tables2 << bits2) * 8) != hipSuccess) return fail("hipMalloc");
-        if (hipMalloc((void **)&lock2, tables2 * 4) != hipSuccess) return fail("hipMalloc");
+        if (p2.alloc((size_t)tables2 << bits2) || lock2.alloc(tables2)) return LEANN_ERR_DEVICE;
         if (hipMemset(p2, 0, ((size_t)tables2 << bits2) * 8) != hipSuccess) return fail("hipMemset");
         if (hipMemset(lock2, 0, tables2 * 4) != hipSuccess) return fail("hipMemset");
     }
@@ -174,15 +177,15 @@ static int ensure_gpool(leann_backend *h) {
     // still being zeroed under them (entries lost -> nodes visited twice -> results off the oracle's; seen once the migration came a
     // few microseconds earlier, tests/test_gpu_parity.py::test_visited_table_overflow_moves_to_hbm_pool).  Once per handle.
     if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize");
-    h->gpool_lock = lock;
-    h->gpool_ctr = lock + tables;
+    h->gpool_lock = lock.release(); // now belong to the handle (leann_internal_free_graph)
+    h->gpool_ctr = h->gpool_lock + tables;
     h->gpool_bits = bits;
     h->gpool_tables = tables;
-    h->gpool2 = p2;
-    h->gpool2_lock = lock2;
+    h->gpool2 = p2.release();
+    h->gpool2_lock = lock2.release();
     h->gpool2_bits = bits2;
     h->gpool2_tables = tables2;
-    h->gpool = p;
+    h->gpool = p.release();
     return LEANN_OK;
 }
 static void set_pool_args(const leann_backend *h, SearchArgs &a) {
@@ -203,7 +206,7 @@ void leann_internal_free_graph(leann_backend *h) {
     (void)hipFree(h->gpool2);
     (void)hipFree(h->gpool2_lock);
     (void)hipFree(h->Wf32);
-    for (auto &kv : h->proj_scratch) (void)hipFree(kv.second.first);
+    h->proj_scratch.clear();
     leann_internal_free_removed(h);
     leann_internal_free_planes(h);
 }
@@ -212,8 +215,8 @@ extern "C" void leann_backend_close(leann_backend *h) {
     if (!h) return;
     leann_backend_set_coalescing(h, 0, 0); // stops the dispatcher thread, if any
     (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();
-    for (auto *w : h->free_ws) ws_free(w);
+    (void)hipDeviceSynchronize(); // before anything the handle owns is freed, here or in `delete h`: no stream still runs on it
+    h->free_ws.clear();
     if (h->sharded) leann_sharded_close(h->sharded); // composite handle: the sub-indexes own the device memory
     else leann_internal_free_graph(h);
     delete h;
@@ -294,15 +297,8 @@ static int project_queries(leann_backend *h, const float *d_queries, size_t nq, 
     {
         std::lock_guard<std::mutex> lk(h->mu);
         auto &sc = h->proj_scratch[st];
-        const size_t need = nq * h->g.feat_h;
-        if (sc.second < need) {
-            (void)hipFree(sc.first);
-            sc.first = nullptr;
-            sc.second = 0;
-            if (hipMalloc((void **)&sc.first, need * 4) != hipSuccess) { leann_set_error("hipMalloc(%zu) failed", need * 4); return LEANN_ERR_DEVICE; }
-            sc.second = need;
-        }
-        G = sc.first;
+        if (int rc = sc.grow(nq * h->g.feat_h)) return rc;
+        G = sc;
     }
     int rc = leann_internal_score(h->Wf32, h->g.feat_h, h->g.d, h->g.d, d_queries, nq, h->g.d, G, st);
     *out = G;
@@ -478,9 +474,8 @@ extern "C" int leann_backend_filter_create(const leann_backend *hc, const uint8_
     f->device = hc->device;
     f->n = hc->g.n;
     const size_t nbytes = std::max<size_t>((f->n + 7) / 8, 1);
-    if (hipMalloc((void **)&f->d_allow, nbytes) != hipSuccess || hipMemcpy(f->d_allow, allow, (f->n + 7) / 8, hipMemcpyHostToDevice) != hipSuccess) {
+    if (f->d_allow.alloc(nbytes) || hipMemcpy(f->d_allow, allow, (f->n + 7) / 8, hipMemcpyHostToDevice) != hipSuccess) {
         leann_set_error("leann_backend_filter_create: device allocation / copy of %zu bytes failed", nbytes);
-        if (f->d_allow) (void)hipFree(f->d_allow);
         delete f;
         return LEANN_ERR_DEVICE;
     }
@@ -488,7 +483,6 @@ extern "C" int leann_backend_filter_create(const leann_backend *hc, const uint8_
     int rc = leann_internal_and_live_inplace(hc, f->d_allow); // removed positions are never allowed: the bitmap and the list hold live ones only
     if (rc == LEANN_OK && f->n) rc = leann_internal_compact_allow(f->d_allow, f->n, &f->d_list, &f->n_allowed, nullptr);
     if (rc != LEANN_OK) {
-        (void)hipFree(f->d_allow);
         delete f;
         return rc;
     }
@@ -506,8 +500,7 @@ extern "C" void leann_backend_filter_free(leann_filter *f) {
     (void)hipSetDevice(f->device);
     (void)hipDeviceSynchronize(); // searches on any stream may still be reading the bitmap / the list
     leann_internal_scratch_release(f->d_list);
-    if (f->d_allow) (void)hipFree(f->d_allow);
-    delete f;
+    delete f; // the bitmap goes with it, on the filter's device and after the synchronisation above
 }
 extern "C" int leann_backend_search_filter_batch(const leann_backend *hc, const float *queries, size_t nq, size_t top_k, size_t complexity,
                                                  const leann_filter *filter, int mode, uint64_t *keys, float *dists, uint32_t *counts) {
@@ -577,14 +570,14 @@ static int search_filtered_batch_host_impl(const leann_backend *hc, const float 
         return LEANN_OK;
     }
     HIP_CHECK_RET(hipSetDevice(h->device));
-    Workspace *w = nullptr;
+    std::unique_ptr<Workspace> w;
     {
         std::lock_guard<std::mutex> lk(h->mu);
-        if (!h->free_ws.empty()) { w = h->free_ws.back(); h->free_ws.pop_back(); }
+        if (!h->free_ws.empty()) { w = std::move(h->free_ws.back()); h->free_ws.pop_back(); }
     }
-    if (!w) w = new Workspace();
+    if (!w) w.reset(new Workspace());
     int rc = LEANN_OK;
-    auto fail = [&](int code) { std::lock_guard<std::mutex> lk(h->mu); h->free_ws.push_back(w); return code; };
+    auto fail = [&](int code) { std::lock_guard<std::mutex> lk(h->mu); h->free_ws.push_back(std::move(w)); return code; };
     if (!w->stream) {
         if (hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking) != hipSuccess) {
             leann_set_error("hipStreamCreate failed");
@@ -593,15 +586,6 @@ static int search_filtered_batch_host_impl(const leann_backend *hc, const float 
     }
     const size_t d = h->g.d, qf = nq * d, no = nq * top_k;
     const size_t ns = 1; // (a composite handle reduces its per-shard counters to [nq x 4] itself, shard.hip)
-    auto grow = [&](void **p, size_t &cap, size_t need, size_t elt) -> int {
-        if (need <= cap) return 0;
-        (void)hipFree(*p);
-        *p = nullptr;
-        cap = 0;
-        if (hipMalloc(p, need * elt) != hipSuccess) { leann_set_error("hipMalloc(%zu) failed", need * elt); return 1; }
-        cap = need;
-        return 0;
-    };
     // Small call on a plain handle: zero-copy through the workspace's pinned block (internal.h).  Layout, 16-byte aligned pieces:
     const size_t o_keys = (qf * 4 + 15) & ~(size_t)15, o_dists = o_keys + no * 8, o_counts = (o_dists + no * 4 + 15) & ~(size_t)15,
                  o_stats = o_counts + ((nq * 4 + 15) & ~(size_t)15), pin_bytes = o_stats + nq * 16;
@@ -617,17 +601,13 @@ static int search_filtered_batch_host_impl(const leann_backend *hc, const float 
     // (queries: read in place by up to 4 queries' workgroups — every wave of a query reads all of it, and mapped host memory is not
     // cached on the device; larger small calls copy them from the pinned block with one DMA)
     const bool zc_in = zero_copy && nq <= 4;
-    if (zero_copy && !zc_in && grow((void **)&w->d_q, w->cap_q, qf, 4)) return fail(LEANN_ERR_DEVICE);
-    if (!zero_copy && (grow((void **)&w->d_q, w->cap_q, qf, 4) || grow((void **)&w->d_keys, w->cap_keys, no, 8) ||
-        grow((void **)&w->d_dists, w->cap_dists, no, 4) || grow((void **)&w->d_counts, w->cap_counts, nq, 4) ||
-        grow((void **)&w->d_stats, w->cap_stats, ns * nq * 4, 4)))
+    if (zero_copy && !zc_in && w->d_q.grow(qf)) return fail(LEANN_ERR_DEVICE);
+    if (!zero_copy && (w->d_q.grow(qf) || w->d_keys.grow(no) || w->d_dists.grow(no) || w->d_counts.grow(nq) || w->d_stats.grow(ns * nq * 4)))
         return fail(LEANN_ERR_DEVICE);
     hipStream_t st = w->stream;
     if (allow) {
         const size_t total = allow_stride ? allow_stride * nq : (h->g.n + 7) / 8;
-        void *pa = w->d_allow;
-        if (grow(&pa, w->cap_allow, total, 1)) { w->d_allow = (uint8_t *)pa; return fail(LEANN_ERR_DEVICE); }
-        w->d_allow = (uint8_t *)pa;
+        if (w->d_allow.grow(total)) return fail(LEANN_ERR_DEVICE);
         if (hipMemcpyAsync(w->d_allow, allow, total, hipMemcpyHostToDevice, st) != hipSuccess) {
             leann_set_error("H2D copy of the allow-bitmap failed");
             return fail(LEANN_ERR_DEVICE);
@@ -685,7 +665,7 @@ static int search_filtered_batch_host_impl(const leann_backend *hc, const float 
                                           (uint64_t)hstats[i * 4 + 2] * gv.M * 4;
         }
         h->stats.n_queries += nq;
-        h->free_ws.push_back(w);
+        h->free_ws.push_back(std::move(w));
     }
     if (n_lost) { // search.cuh: the last visited-table level filled up (not reachable with the pools ensure_gpool sizes)
         leann_set_error("search: %zu of %zu queries ran out of visited-set space at complexity %zu; lower the complexity", n_lost, nq,
@@ -954,12 +934,7 @@ int leann_internal_from_host(int backend, size_t n, size_t dims, uint32_t M, uin
         leann_set_error("leann_backend_from_arrays: inconsistent graph arrays: %s", why);
         return LEANN_ERR_FORMAT;
     }
-    int ndev = 0;
-    leann_device_count(&ndev);
-    if (device < 0 || device >= ndev) {
-        leann_set_error("HIP device %d not available (%d visible). This library has no CPU fallback.", device, ndev);
-        return LEANN_ERR_DEVICE;
-    }
+    if (int rc = leann_internal_check_device(device)) return rc;
     HIP_CHECK_RET(hipSetDevice(device));
     leann_backend *h = new leann_backend();
     h->kind = backend;

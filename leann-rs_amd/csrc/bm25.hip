@@ -61,15 +61,14 @@ struct leann_bm25 {
     size_t n_docs = 0, n_terms = 0, n_post = 0;
     uint32_t slots = 0;
     std::vector<uint64_t> h_off; // post_off, kept on the host: a query token becomes (begin, len) before it is uploaded
-    uint32_t *d_doc = nullptr, *d_tf = nullptr;
-    float *d_k1n = nullptr, *d_acc = nullptr;                    // acc [slots x n_docs], all zero between calls
-    uint64_t *d_best = nullptr, *d_list = nullptr;               // [slots x BM25_MAX_TOPK], [slots x BM25_CAND_CAP]
-    float *d_thr = nullptr;                                      // [slots]
-    uint32_t *d_cnt = nullptr, *d_stats = nullptr, *d_overflow = nullptr; // [slots], [slots x 4] {P, min, max, -}, [1]
+    DeviceBuf<uint32_t> d_doc, d_tf;
+    DeviceBuf<float> d_k1n, d_acc;                               // acc [slots x n_docs], all zero between calls
+    DeviceBuf<uint64_t> d_best, d_list;                          // [slots x BM25_MAX_TOPK], [slots x BM25_CAND_CAP]
+    DeviceBuf<float> d_thr;                                      // [slots]
+    DeviceBuf<uint32_t> d_cnt, d_stats, d_overflow;              // [slots], [slots x 4] {P, min, max, -}, [1]
     uint32_t *h_overflow = nullptr;                              // pinned
-    Bm25Tok *d_toks = nullptr;                                   // query tokens / offsets of the running batch; grown, never shrunk
-    uint32_t *d_qoff = nullptr;
-    size_t cap_toks = 0, cap_qoff = 0;
+    DeviceBuf<Bm25Tok> d_toks;                                   // query tokens / offsets of the running batch; grown, never shrunk
+    DeviceBuf<uint32_t> d_qoff;
     std::mutex mu;                                               // one batch at a time owns the accumulators
 };
 
@@ -241,13 +240,10 @@ static void bm25_free(leann_bm25 *b) {
     if (!b) return;
     int prev = 0;
     (void)hipGetDevice(&prev);
-    (void)hipSetDevice(b->device);
-    for (void *p : {(void *)b->d_doc, (void *)b->d_tf, (void *)b->d_k1n, (void *)b->d_acc, (void *)b->d_best, (void *)b->d_list, (void *)b->d_thr,
-                    (void *)b->d_cnt, (void *)b->d_stats, (void *)b->d_overflow, (void *)b->d_toks, (void *)b->d_qoff})
-        if (p) (void)hipFree(p);
+    (void)hipSetDevice(b->device); // the owning device is current while `delete b` frees the handle's buffers
     if (b->h_overflow) (void)hipHostFree(b->h_overflow);
-    (void)hipSetDevice(prev);
     delete b;
+    (void)hipSetDevice(prev);
 }
 
 extern "C" int leann_bm25_create(size_t n_docs, size_t n_terms, const uint64_t *post_off, const uint32_t *post_doc, const uint32_t *post_tf,
@@ -336,17 +332,19 @@ extern "C" int leann_bm25_create(size_t n_docs, size_t n_terms, const uint64_t *
     b->slots = (uint32_t)std::min<size_t>(BM25_MAX_SLOTS, std::max<size_t>(1, BM25_ACC_BUDGET / (sizeof(float) * n_docs)));
     const size_t S = b->slots;
     hipError_t e = hipSuccess;
-    auto alloc = [&](void **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, std::max<size_t>(bytes, 256)); };
-    alloc((void **)&b->d_doc, n_post * 4);
-    alloc((void **)&b->d_tf, n_post * 4);
-    alloc((void **)&b->d_k1n, n_docs * 4);
-    alloc((void **)&b->d_acc, S * n_docs * 4);
-    alloc((void **)&b->d_best, S * BM25_MAX_TOPK * 8);
-    alloc((void **)&b->d_list, S * BM25_CAND_CAP * 8);
-    alloc((void **)&b->d_thr, S * 4);
-    alloc((void **)&b->d_cnt, S * 4);
-    alloc((void **)&b->d_stats, S * 16);
-    alloc((void **)&b->d_overflow, 4);
+    auto alloc = [&](auto &buf, size_t count) { // (256 bytes at the least)
+        if (e == hipSuccess && buf.alloc(std::max<size_t>(count, 256 / sizeof(*buf.p)))) e = hipErrorOutOfMemory;
+    };
+    alloc(b->d_doc, n_post);
+    alloc(b->d_tf, n_post);
+    alloc(b->d_k1n, n_docs);
+    alloc(b->d_acc, S * n_docs);
+    alloc(b->d_best, S * BM25_MAX_TOPK);
+    alloc(b->d_list, S * BM25_CAND_CAP);
+    alloc(b->d_thr, S);
+    alloc(b->d_cnt, S);
+    alloc(b->d_stats, S * 4);
+    alloc(b->d_overflow, 1);
     if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_overflow, 4, hipHostMallocDefault);
     if (e == hipSuccess && n_post) e = hipMemcpy(b->d_doc, post_doc, n_post * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess && n_post) e = hipMemcpy(b->d_tf, post_tf, n_post * 4, hipMemcpyHostToDevice);
@@ -389,32 +387,22 @@ struct Bm25Consumer { // what happens to a chunk's best-k while its accumulators
 // best-k of the chunk's nslots accumulators by the segment sorter of the exact scan (no list to overflow)
 static int bm25_select_by_segments(leann_bm25 *b, uint32_t nslots, uint32_t k, hipStream_t st) {
     const size_t segs = (b->n_docs + SEG - 1) / SEG, cand_len = segs * k;
-    uint64_t *candA = nullptr, *candB = nullptr, *keys = nullptr;
-    float *scores = nullptr;
-    uint32_t *counts = nullptr;
-    hipError_t e = hipMalloc((void **)&candA, nslots * cand_len * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&candB, nslots * cand_len * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&keys, (size_t)nslots * k * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&scores, (size_t)nslots * k * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&counts, (size_t)nslots * 4);
-    int rc = LEANN_OK;
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        leann_set_error("leann_bm25: hipMalloc for the segment selection failed: %s", hipGetErrorString(e));
-        rc = LEANN_ERR_DEVICE;
-    }
+    DeviceBuf<uint64_t> candA, candB, keys;
+    DeviceBuf<float> scores;
+    DeviceBuf<uint32_t> counts;
+    if (candA.alloc(nslots * cand_len) || candB.alloc(nslots * cand_len) || keys.alloc((size_t)nslots * k) || scores.alloc((size_t)nslots * k) ||
+        counts.alloc(nslots))
+        return LEANN_ERR_DEVICE;
     size_t segs_out = 0;
-    if (rc == LEANN_OK) rc = leann_internal_topk_chunk(b->d_acc, b->n_docs, nslots, k, nullptr, 0, candA, cand_len, 0, st, &segs_out, nullptr);
+    int rc = leann_internal_topk_chunk(b->d_acc, b->n_docs, nslots, k, nullptr, 0, candA, cand_len, 0, st, &segs_out, nullptr);
     if (rc == LEANN_OK) rc = leann_internal_scan_finish(candA, candB, cand_len, segs_out, nslots, k, 0, keys, scores, counts, st);
     if (rc == LEANN_OK) {
-        hipLaunchKernelGGL(bm25_rebuild_best_kernel, dim3(nslots), dim3(256), 0, st, keys, scores, k, b->d_best);
+        hipLaunchKernelGGL(bm25_rebuild_best_kernel, dim3(nslots), dim3(256), 0, st, keys.p, scores.p, k, b->d_best.p);
         if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
             leann_set_error("leann_bm25: segment selection failed on the device");
             rc = LEANN_ERR_DEVICE;
         }
     }
-    for (void *p : {(void *)candA, (void *)candB, (void *)keys, (void *)scores, (void *)counts})
-        if (p) (void)hipFree(p);
     return rc;
 }
 
@@ -437,20 +425,8 @@ static int bm25_run(leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint3
         leann_set_error("leann_bm25: %s failed: %s", what, hipGetErrorString(e));
         rc = LEANN_ERR_DEVICE;
     };
-    if (b->cap_toks < toks.size()) {
-        if (b->d_toks) (void)hipFree(b->d_toks);
-        b->d_toks = nullptr;
-        b->cap_toks = 0;
-        fail(hipMalloc((void **)&b->d_toks, toks.size() * 2 * sizeof(Bm25Tok)), "hipMalloc");
-        if (rc == LEANN_OK) b->cap_toks = toks.size() * 2;
-    }
-    if (rc == LEANN_OK && b->cap_qoff < nq + 1) {
-        if (b->d_qoff) (void)hipFree(b->d_qoff);
-        b->d_qoff = nullptr;
-        b->cap_qoff = 0;
-        fail(hipMalloc((void **)&b->d_qoff, (nq + 1) * 2 * 4), "hipMalloc");
-        if (rc == LEANN_OK) b->cap_qoff = (nq + 1) * 2;
-    }
+    if (b->d_toks.cap < toks.size()) rc = b->d_toks.grow(toks.size() * 2); // twice what is needed: headroom for the next batch
+    if (rc == LEANN_OK && b->d_qoff.cap < nq + 1) rc = b->d_qoff.grow((nq + 1) * 2);
     Bm25Tok *d_toks = b->d_toks;
     uint32_t *d_qoff = b->d_qoff;
     if (rc == LEANN_OK) fail(hipMemcpy(d_toks, toks.data(), toks.size() * sizeof(Bm25Tok), hipMemcpyHostToDevice), "hipMemcpy");
@@ -560,22 +536,16 @@ extern "C" int leann_bm25_search_batch(const leann_bm25 *b, size_t nq, const uin
     int prev = 0;
     HIP_CHECK_RET(hipGetDevice(&prev));
     HIP_CHECK_RET(hipSetDevice(b->device));
-    unsigned char *d = nullptr;
+    DeviceBuf<unsigned char> d;
     const size_t o_pos = 0, o_sc = o_pos + nq * top_k * 4, o_cnt = o_sc + nq * top_k * 4, o_np = o_cnt + nq * 4, o_mm = o_np + nq * 4,
                  total = o_mm + nq * 8;
-    hipError_t e = hipMalloc((void **)&d, total);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipSetDevice(prev);
-        leann_set_error("leann_bm25_search_batch: hipMalloc(%zu) failed: %s", total, hipGetErrorString(e));
-        return LEANN_ERR_DEVICE;
-    }
+    if ((rc = d.alloc(total))) { (void)hipSetDevice(prev); return rc; }
     Bm25Consumer c;
     c.d_pos = (uint32_t *)(d + o_pos); c.d_scores = (float *)(d + o_sc); c.d_counts = (uint32_t *)(d + o_cnt);
     c.d_npos = (uint32_t *)(d + o_np); c.d_minmax = (float *)(d + o_mm);
     rc = bm25_run(const_cast<leann_bm25 *>(b), nq, q_off, q_term, q_idf, (uint32_t)top_k, c, nullptr);
     if (rc == LEANN_OK) {
-        e = hipMemcpy(pos, d + o_pos, nq * top_k * 4, hipMemcpyDeviceToHost);
+        hipError_t e = hipMemcpy(pos, d + o_pos, nq * top_k * 4, hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipMemcpy(scores, d + o_sc, nq * top_k * 4, hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipMemcpy(counts, d + o_cnt, nq * 4, hipMemcpyDeviceToHost);
         if (e == hipSuccess && n_positive) e = hipMemcpy(n_positive, d + o_np, nq * 4, hipMemcpyDeviceToHost);
@@ -586,7 +556,7 @@ extern "C" int leann_bm25_search_batch(const leann_bm25 *b, size_t nq, const uin
             rc = LEANN_ERR_DEVICE;
         }
     }
-    (void)hipFree(d);
+    d.reset(); // before the caller's device is current again
     (void)hipSetDevice(prev);
     return rc;
 }

@@ -392,31 +392,26 @@ __global__ void __launch_bounds__(256) link_dist_kernel(const float *__restrict_
 struct Builder {
     leann_backend *h;
     ListView lv{};
-    float *adjd0 = nullptr, *adjdU = nullptr;
-    uint32_t *pend = nullptr; float *pendd = nullptr; // Vamana: pending back-edges (ListView)
+    DeviceBuf<float> adjd0, adjdU;
+    DeviceBuf<uint32_t> pend; DeviceBuf<float> pendd; // Vamana: pending back-edges (ListView)
     std::vector<uint8_t> levels;     // host copy
     std::vector<uint32_t> upper_off; // host copy
-    uint32_t *d_order = nullptr;     // insertion order (device copy)
+    DeviceBuf<uint32_t> d_order;     // insertion order (device copy)
     std::vector<uint32_t> order;     // ... host copy: order[j] = position inserted j-th
     std::vector<uint32_t> h_order_first; // only used for Vamana (medoid first)
     // per-batch scratch
     size_t bmax = 0;
-    uint64_t *cand_keys = nullptr; float *cand_d = nullptr; uint32_t *cand_cnt = nullptr;
-    uint64_t *candU_keys = nullptr; float *candU_d = nullptr; uint32_t *candU_cnt = nullptr; uint32_t *d_rowsU = nullptr;
-    uint64_t *prop_key = nullptr, *prop_key2 = nullptr; uint32_t *prop_src = nullptr, *prop_src2 = nullptr;
-    uint32_t *seg_start = nullptr, *nseg = nullptr;
-    uint64_t *exp_keys = nullptr; uint32_t *exp_cnt = nullptr; // Vamana only
-    void *cub_tmp = nullptr; size_t cub_bytes = 0;
+    DeviceBuf<uint64_t> cand_keys, candU_keys, prop_key, prop_key2, exp_keys; // (exp_*: Vamana only)
+    DeviceBuf<float> cand_d, candU_d;
+    DeviceBuf<uint32_t> cand_cnt, candU_cnt, d_rowsU, prop_src, prop_src2, seg_start, nseg, exp_cnt;
+    DeviceBuf<unsigned char> cub_tmp; size_t cub_bytes = 0;
     hipStream_t st = nullptr;
     size_t batch_fraction = 8; // LEANN_BUILD_BATCH_FRACTION, read once per build
     float alpha_now = 1.2f;    // Vamana: RobustPrune's alpha of the pass under way
     Builder() = default;
     Builder(const Builder &) = delete;
     ~Builder() { // every exit of build_on_device, including the error returns, releases the scratch and the stream
-        if (st) (void)hipStreamSynchronize(st);
-        void *ps[] = {cand_keys, cand_d, cand_cnt, candU_keys, candU_d, candU_cnt, d_rowsU, prop_key, prop_key2,
-                      prop_src, prop_src2, seg_start, nseg, cub_tmp, d_order, adjd0, adjdU, exp_keys, exp_cnt, pend, pendd};
-        for (void *p : ps) (void)hipFree(p);
+        if (st) (void)hipStreamSynchronize(st); // in the body: the members are freed after it, when no kernel of the build still runs
         if (st) (void)hipStreamDestroy(st);
     }
 };
@@ -427,10 +422,6 @@ static int env_int(const char *name, int dflt, int lo, int hi) {
     const int v = atoi(e);
     return v >= lo && v <= hi ? v : dflt;
 }
-struct DevTmp { // small scoped device allocation
-    void *p = nullptr;
-    ~DevTmp() { (void)hipFree(p); }
-};
 
 #define BCHECK(expr)                                                                           \
     do {                                                                                       \
@@ -451,7 +442,7 @@ static int link_level(Builder &b, const uint32_t *d_rows, uint32_t nq, uint32_t 
                        ck, cd, cc, efc, msel, alpha, b.prop_key, b.prop_src, ek, ec, (uint32_t)EXPCAP);
     const uint32_t num = nq * msel;
     size_t tmp = b.cub_bytes;
-    BCHECK(hipcub::DeviceRadixSort::SortPairs(b.cub_tmp, tmp, b.prop_key, b.prop_key2, b.prop_src, b.prop_src2, (int)num, 0, 64, b.st));
+    BCHECK(hipcub::DeviceRadixSort::SortPairs(b.cub_tmp.p, tmp, b.prop_key.p, b.prop_key2.p, b.prop_src.p, b.prop_src2.p, (int)num, 0, 64, b.st));
     BCHECK(hipMemsetAsync(b.nseg, 0, 4, b.st));
     hipLaunchKernelGGL(segment_heads_kernel, dim3((num + 255) / 256), dim3(256), 0, b.st, b.prop_key2, num, b.seg_start, b.nseg);
     uint32_t grid = std::min<uint32_t>(num, 256 * 16);
@@ -466,29 +457,17 @@ static int builder_alloc_scratch(Builder &b, size_t bmax) {
     const size_t efc = h->efc, msel = h->g.M;
     b.bmax = bmax;
     const size_t bu = bmax / 16 + 64; // upper-level members per batch (expected bmax/31)
-    BCHECK(hipMalloc((void **)&b.cand_keys, bmax * efc * 8));
-    BCHECK(hipMalloc((void **)&b.cand_d, bmax * efc * 4));
-    BCHECK(hipMalloc((void **)&b.cand_cnt, bmax * 4));
-    BCHECK(hipMalloc((void **)&b.candU_keys, bu * efc * 8 * 16));
-    BCHECK(hipMalloc((void **)&b.candU_d, bu * efc * 4 * 16));
-    BCHECK(hipMalloc((void **)&b.candU_cnt, bu * 4 * 16));
-    BCHECK(hipMalloc((void **)&b.d_rowsU, bu * 4 * 16));
-    BCHECK(hipMalloc((void **)&b.prop_key, bmax * msel * 8));
-    BCHECK(hipMalloc((void **)&b.prop_key2, bmax * msel * 8));
-    BCHECK(hipMalloc((void **)&b.prop_src, bmax * msel * 4));
-    BCHECK(hipMalloc((void **)&b.prop_src2, bmax * msel * 4));
-    BCHECK(hipMalloc((void **)&b.seg_start, bmax * msel * 4));
-    BCHECK(hipMalloc((void **)&b.nseg, 16));
-    if (h->kind == LEANN_BACKEND_DISKANN) {
-        BCHECK(hipMalloc((void **)&b.exp_keys, bmax * EXPCAP * 8));
-        BCHECK(hipMalloc((void **)&b.exp_cnt, bmax * 4));
-    }
+    if (b.cand_keys.alloc(bmax * efc) || b.cand_d.alloc(bmax * efc) || b.cand_cnt.alloc(bmax) || b.candU_keys.alloc(bu * efc * 16) ||
+        b.candU_d.alloc(bu * efc * 16) || b.candU_cnt.alloc(bu * 16) || b.d_rowsU.alloc(bu * 16) || b.prop_key.alloc(bmax * msel) ||
+        b.prop_key2.alloc(bmax * msel) || b.prop_src.alloc(bmax * msel) || b.prop_src2.alloc(bmax * msel) ||
+        b.seg_start.alloc(bmax * msel) || b.nseg.alloc(4))
+        return LEANN_ERR_DEVICE;
+    if (h->kind == LEANN_BACKEND_DISKANN && (b.exp_keys.alloc(bmax * EXPCAP) || b.exp_cnt.alloc(bmax))) return LEANN_ERR_DEVICE;
     size_t tmp = 0;
-    BCHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, b.prop_key, b.prop_key2, b.prop_src, b.prop_src2,
+    BCHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, b.prop_key.p, b.prop_key2.p, b.prop_src.p, b.prop_src2.p,
                                               (int)(bmax * msel), 0, 64, b.st));
     b.cub_bytes = tmp;
-    BCHECK(hipMalloc(&b.cub_tmp, tmp));
-    return LEANN_OK;
+    return b.cub_tmp.alloc(tmp);
 }
 
 // Insert order[s0 .. n) into the graph that already holds order[0 .. s0).
@@ -613,8 +592,7 @@ static int build_on_device(leann_backend *h, size_t n_existing, size_t bmax_hint
     b.lv.M = h->g.M;
     b.lv.M0 = h->g.M0;
     const size_t nu = std::max<size_t>(h->n_upper_lists, 1);
-    BCHECK(hipMalloc((void **)&b.adjd0, std::max<size_t>(n, 1) * h->g.M0 * 4));
-    BCHECK(hipMalloc((void **)&b.adjdU, nu * h->g.M * 4));
+    if (b.adjd0.alloc(std::max<size_t>(n, 1) * h->g.M0) || b.adjdU.alloc(nu * h->g.M)) return LEANN_ERR_DEVICE;
     BCHECK(hipMemset(b.adjd0, 0, std::max<size_t>(n, 1) * h->g.M0 * 4));
     BCHECK(hipMemset(b.adjdU, 0, nu * h->g.M * 4));
     b.lv.adjd0 = b.adjd0;
@@ -628,8 +606,7 @@ static int build_on_device(leann_backend *h, size_t n_existing, size_t bmax_hint
         const uint32_t slack = (uint32_t)env_int("LEANN_VAMANA_PENDING", 4, 0, 32);
         b.lv.P = slack;
         if (slack) {
-            BCHECK(hipMalloc((void **)&b.pend, std::max<size_t>(n, 1) * slack * 4));
-            BCHECK(hipMalloc((void **)&b.pendd, std::max<size_t>(n, 1) * slack * 4));
+            if (b.pend.alloc(std::max<size_t>(n, 1) * slack) || b.pendd.alloc(std::max<size_t>(n, 1) * slack)) return LEANN_ERR_DEVICE;
             BCHECK(hipMemset(b.pend, 0xFF, std::max<size_t>(n, 1) * slack * 4));
             BCHECK(hipMemset(b.pendd, 0, std::max<size_t>(n, 1) * slack * 4));
             b.lv.pend = b.pend;
@@ -638,20 +615,19 @@ static int build_on_device(leann_backend *h, size_t n_existing, size_t bmax_hint
     }
     b.levels.resize(std::max<size_t>(n, 1));
     BCHECK(hipMemcpy(b.levels.data(), h->d_levels, n, hipMemcpyDeviceToHost));
-    BCHECK(hipMalloc((void **)&b.d_order, std::max<size_t>(n, 1) * 4));
+    if (int rc = b.d_order.alloc(std::max<size_t>(n, 1))) return rc;
     int rc = LEANN_OK;
     size_t s0 = n_existing;
     if (n_existing == 0 && n > 0) {
         uint32_t first = 0;
         if (h->kind == LEANN_BACKEND_DISKANN && !h->nav_levels) {
             // medoid: closest row to the mean direction, by the index metric (ties -> lower id)
-            DevTmp t_mean, t_mk, t_ms, t_mc, t_part;
+            DeviceBuf<float> mean, ms;
+            DeviceBuf<uint64_t> mk;
+            DeviceBuf<uint32_t> mc;
+            DeviceBuf<double> part;
             const uint32_t S = 1024;
-            BCHECK(hipMalloc(&t_mean.p, h->g.ld * 4));
-            BCHECK(hipMalloc(&t_mk.p, 8)); BCHECK(hipMalloc(&t_ms.p, 4)); BCHECK(hipMalloc(&t_mc.p, 4));
-            BCHECK(hipMalloc(&t_part.p, (size_t)S * h->g.ld * 8));
-            float *mean = (float *)t_mean.p; uint64_t *mk = (uint64_t *)t_mk.p; float *ms = (float *)t_ms.p; uint32_t *mc = (uint32_t *)t_mc.p;
-            double *part = (double *)t_part.p;
+            if (mean.alloc(h->g.ld) || mk.alloc(1) || ms.alloc(1) || mc.alloc(1) || part.alloc((size_t)S * h->g.ld)) return LEANN_ERR_DEVICE;
             hipLaunchKernelGGL(col_partial_kernel, dim3((h->g.ld + 63) / 64, S), dim3(64), 0, b.st, h->g.X, n, h->g.d, h->g.ld, S, part);
             hipLaunchKernelGGL(col_mean_kernel, dim3((h->g.ld + 63) / 64), dim3(64), 0, b.st, part, n, h->g.ld, S, mean);
             BCHECK(hipStreamSynchronize(b.st));
@@ -716,18 +692,16 @@ static int alloc_graph_arrays(leann_backend *h, uint64_t level_seed) {
         nu += levels[i];
     }
     h->n_upper_lists = nu;
-    uint32_t *adj0 = nullptr, *adjU = nullptr, *duo = nullptr;
-    BCHECK(hipMalloc((void **)&adj0, nn * h->g.M0 * 4));
-    BCHECK(hipMalloc((void **)&adjU, std::max<uint64_t>(nu, 1) * h->g.M * 4));
-    BCHECK(hipMalloc((void **)&duo, nn * 4));
+    DeviceBuf<uint32_t> adj0, adjU, duo; // this call's own until the last lines: an earlier return frees them
+    if (adj0.alloc(nn * h->g.M0) || adjU.alloc(std::max<uint64_t>(nu, 1) * h->g.M) || duo.alloc(nn)) return LEANN_ERR_DEVICE;
     BCHECK(hipMalloc((void **)&h->d_levels, nn));
     BCHECK(hipMemset(adj0, 0xFF, nn * h->g.M0 * 4));
     BCHECK(hipMemset(adjU, 0xFF, std::max<uint64_t>(nu, 1) * h->g.M * 4));
     BCHECK(hipMemcpy(duo, uo.data(), nn * 4, hipMemcpyHostToDevice));
     BCHECK(hipMemcpy(h->d_levels, levels.data(), nn, hipMemcpyHostToDevice));
-    h->g.adj0 = adj0;
-    h->g.adjU = adjU;
-    h->g.upper_off = duo;
+    h->g.adj0 = adj0.release();
+    h->g.adjU = adjU.release();
+    h->g.upper_off = duo.release();
     return LEANN_OK;
 }
 
@@ -786,12 +760,7 @@ static int build_device_impl(int backend, const float *d_vectors, size_t n, size
         return LEANN_ERR_INVALID;
     }
     if (int rc = check_degree(backend, graph_degree, complexity)) return rc;
-    int ndev = 0;
-    leann_device_count(&ndev);
-    if (device < 0 || device >= ndev) {
-        leann_set_error("HIP device %d not available (%d visible). This library has no CPU fallback.", device, ndev);
-        return LEANN_ERR_DEVICE;
-    }
+    if (int rc = leann_internal_check_device(device)) return rc;
     BCHECK(hipSetDevice(device));
     leann_backend *h = new leann_backend();
     h->kind = backend;
@@ -806,16 +775,14 @@ static int build_device_impl(int backend, const float *d_vectors, size_t n, size
     h->g.M0 = backend == LEANN_BACKEND_HNSW ? (uint32_t)(2 * graph_degree) : (uint32_t)graph_degree;
     h->nav_levels = backend == LEANN_BACKEND_DISKANN && env_int("LEANN_VAMANA_NAV", 0, 0, 1) != 0;
     if (take_copy) {
-        float *cp = nullptr;
-        if (hipMalloc((void **)&cp, std::max<size_t>(n * ld, 4) * 4) != hipSuccess ||
-            (n && hipMemcpy(cp, d_vectors, n * ld * 4, hipMemcpyDeviceToDevice) != hipSuccess)) {
+        DeviceBuf<float> cp;
+        if (cp.alloc(std::max<size_t>(n * ld, 4)) || (n && hipMemcpy(cp, d_vectors, n * ld * 4, hipMemcpyDeviceToDevice) != hipSuccess)) {
             leann_set_error("build: copying %zu rows failed: %s", n, hipGetErrorString(hipGetLastError()));
-            (void)hipFree(cp);
             h->owns_rows = false;
             leann_backend_close(h);
             return LEANN_ERR_DEVICE;
         }
-        h->g.X = cp;
+        h->g.X = cp.release();
         h->owns_rows = true;
     } else {
         h->g.X = d_vectors;
@@ -849,8 +816,8 @@ extern "C" int leann_backend_build(int backend, const float *vectors, size_t n, 
     }
     BCHECK(hipSetDevice(0));
     const size_t ld = (dims + 3) & ~(size_t)3;
-    float *dX = nullptr;
-    BCHECK(hipMalloc((void **)&dX, std::max<size_t>(n * ld, 4) * 4));
+    DeviceBuf<float> dX; // this call's own copy: the handle below borrows it and is closed before it goes
+    if (int rc = dX.alloc(std::max<size_t>(n * ld, 4))) return rc;
     if (n) {
         if (ld == dims) BCHECK(hipMemcpy(dX, vectors, n * dims * 4, hipMemcpyHostToDevice));
         else {
@@ -860,8 +827,7 @@ extern "C" int leann_backend_build(int backend, const float *vectors, size_t n, 
     }
     leann_backend *h = nullptr;
     int rc = build_device_guarded(backend, dX, n, dims, ld, graph_degree, complexity, 0, 0, 0, &h, false);
-    if (rc) { (void)hipFree(dX); return rc; }
-    h->owns_rows = true; // dX now belongs to the handle
+    if (rc) return rc;
     rc = leann_backend_save(h, index_path_stem);
     leann_backend_close(h);
     return rc;
@@ -905,13 +871,12 @@ extern "C" int leann_backend_add(int backend, const float *vectors, size_t n, si
     // the builder prunes with are recomputed (link_dist_kernel).  The same algorithm as a one-shot build of the concatenation on a
     // different batch schedule (the appended rows are permuted among themselves only).
     const size_t ld = old->g.ld, nt = n_old + n;
-    float *dX = nullptr;
-    if (hipMalloc((void **)&dX, std::max<size_t>(nt * ld, 4) * 4) != hipSuccess ||
+    DeviceBuf<float> dX; // this call's own: every handle below borrows the rows and is closed before they go
+    if (dX.alloc(std::max<size_t>(nt * ld, 4)) ||
         (n_old && hipMemcpy(dX, old->g.X, n_old * ld * 4, hipMemcpyDeviceToDevice) != hipSuccess) ||
         (n && (hipMemset(dX + n_old * ld, 0, n * ld * 4) != hipSuccess ||
                hipMemcpy2D(dX + n_old * ld, ld * 4, vectors, dims * 4, dims * 4, n, hipMemcpyHostToDevice) != hipSuccess))) {
         leann_set_error("add_to_index: staging %zu rows on the device failed: %s", nt, hipGetErrorString(hipGetLastError()));
-        (void)hipFree(dX);
         leann_backend_close(old);
         return LEANN_ERR_DEVICE;
     }
@@ -925,7 +890,7 @@ extern "C" int leann_backend_add(int backend, const float *vectors, size_t n, si
     h->g.X = dX;
     h->g.n = nt;
     h->g.adj0 = nullptr; h->g.adjU = nullptr; h->g.upper_off = nullptr;
-    h->owns_rows = true;
+    h->owns_rows = false;
     rc = alloc_graph_arrays(h, LEVEL_SEED);
     bool same_levels = true; // an index that did not come from this builder (leann_backend_from_arrays + save) has its own level table
     if (rc == LEANN_OK && n_old) {
@@ -941,12 +906,9 @@ extern "C" int leann_backend_add(int backend, const float *vectors, size_t n, si
     if (rc == LEANN_OK && !same_levels) { // foreign level table: rebuild over the concatenation (the pre-append behaviour)
         const size_t M = old->g.M, efc = old->efc;
         leann_backend_close(old);
-        h->g.X = nullptr;
-        h->owns_rows = false;
         leann_backend_close(h);
         rc = build_device_guarded(backend, dX, nt, dims, ld, M, efc, 0, 0, 0, &h, false);
-        if (rc) { (void)hipFree(dX); return rc; }
-        h->owns_rows = true;
+        if (rc) return rc;
         if (tomb_n) rc = leann_internal_set_removed(h, tomb.data(), tomb_n);
         if (rc == LEANN_OK) rc = leann_backend_save(h, index_path_stem);
         leann_backend_close(h);
@@ -966,7 +928,6 @@ extern "C" int leann_backend_add(int backend, const float *vectors, size_t n, si
     if (rc == LEANN_OK && n) rc = build_on_device(h, n_old, 0);
     if (rc == LEANN_OK && tomb_n) rc = leann_internal_set_removed(h, tomb.data(), tomb_n);
     if (rc) { leann_backend_close(h); return rc; }
-    h->owns_rows = true;
     rc = leann_backend_save(h, index_path_stem);
     leann_backend_close(h);
     return rc;

@@ -215,10 +215,6 @@ __global__ void __launch_bounds__(256) wide_repair_kernel(const float *__restric
             return LEANN_ERR_DEVICE;                                                                                       \
         }                                                                                                                  \
     } while (0)
-struct DevBuf { // scoped device allocation
-    void *p = nullptr;
-    ~DevBuf() { (void)hipFree(p); }
-};
 
 static LevelLists level_lists(const leann_backend *h, uint32_t level) {
     LevelLists L;
@@ -234,18 +230,18 @@ static int count_pending(leann_backend *h, size_t *out) {
     *out = 0;
     const uint32_t n = (uint32_t)h->g.n;
     if (!n || !h->d_live || !h->n_removed) return LEANN_OK;
-    DevBuf flag, cnt;
-    CCHECK(hipMalloc(&flag.p, n));
-    CCHECK(hipMalloc(&cnt.p, 4));
-    CCHECK(hipMemset(flag.p, 0, n));
-    CCHECK(hipMemset(cnt.p, 0, 4));
+    DeviceBuf<uint8_t> flag;
+    DeviceBuf<uint32_t> cnt;
+    if (flag.alloc(n) || cnt.alloc(1)) return LEANN_ERR_DEVICE;
+    CCHECK(hipMemset(flag, 0, n));
+    CCHECK(hipMemset(cnt, 0, 4));
     for (uint32_t l = 0; l <= h->g.max_level; l++)
         hipLaunchKernelGGL(pending_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, l == 0 ? h->g.adj0 : h->g.adjU, level_lists(h, l),
-                           h->d_live, n, (uint8_t *)flag.p);
-    hipLaunchKernelGGL(count_flags_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, (const uint8_t *)flag.p, n, (uint32_t *)cnt.p);
+                           h->d_live, n, flag.p);
+    hipLaunchKernelGGL(count_flags_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, flag.p, n, cnt.p);
     CCHECK(hipGetLastError());
     uint32_t c = 0;
-    CCHECK(hipMemcpy(&c, cnt.p, 4, hipMemcpyDeviceToHost));
+    CCHECK(hipMemcpy(&c, cnt, 4, hipMemcpyDeviceToHost));
     *out = c;
     return LEANN_OK;
 }
@@ -269,7 +265,6 @@ static int upload_live(leann_backend *h) {
 void leann_internal_free_removed(leann_backend *h) {
     (void)hipFree(h->d_live);
     h->d_live = nullptr;
-    for (auto &kv : h->live_scratch) (void)hipFree(kv.second.first);
     h->live_scratch.clear();
 }
 
@@ -301,14 +296,8 @@ int leann_internal_live_allow(leann_backend *h, const uint8_t *d_allow, size_t a
     {
         std::lock_guard<std::mutex> lk(h->mu);
         auto &sc = h->live_scratch[st];
-        if (sc.second < total) { // grows to the largest request of the stream, then allocates nothing
-            (void)hipFree(sc.first);
-            sc.first = nullptr;
-            sc.second = 0;
-            if (hipMalloc((void **)&sc.first, total) != hipSuccess) { leann_set_error("hipMalloc(%zu) failed", total); return LEANN_ERR_DEVICE; }
-            sc.second = total;
-        }
-        buf = sc.first;
+        if (int rc = sc.grow(total)) return rc; // grows to the largest request of the stream, then allocates nothing
+        buf = sc;
     }
     hipLaunchKernelGGL(and_live_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, buf, d_allow, h->d_live, nbytes, allow_stride, total);
     CCHECK(hipGetLastError());
@@ -425,11 +414,9 @@ static int consolidate_plain(leann_backend *h) {
     const uint32_t n = (uint32_t)h->g.n;
     CCHECK(hipSetDevice(h->device));
     CCHECK(hipDeviceSynchronize());
-    DevBuf work, cnt, snap;
+    DeviceBuf<uint32_t> work, cnt, snap;
     const size_t b0 = (size_t)n * h->g.M0 * 4, bU = h->n_upper_lists * (size_t)h->g.M * 4;
-    CCHECK(hipMalloc(&work.p, (size_t)n * 4));
-    CCHECK(hipMalloc(&cnt.p, 4));
-    CCHECK(hipMalloc(&snap.p, std::max<size_t>(std::max(b0, bU), 4)));
+    if (work.alloc(n) || cnt.alloc(1) || snap.alloc(std::max<size_t>(std::max(b0, bU), 4) / 4)) return LEANN_ERR_DEVICE;
     const bool wide = std::max(h->g.M0, h->g.M) > 64;
     const float alpha = h->kind == LEANN_BACKEND_DISKANN ? h->alpha : 0.f;
     for (uint32_t l = 0; l <= h->g.max_level; l++) {
@@ -437,12 +424,12 @@ static int consolidate_plain(leann_backend *h) {
         const LevelLists L = level_lists(h, l);
         // N(.) is read as it was before this consolidate.  The upper lists share one array and the lists of different levels are
         // disjoint, so the snapshot taken at level 1 serves every level above it.
-        if (l <= 1) CCHECK(hipMemcpy(snap.p, adj, l == 0 ? b0 : bU, hipMemcpyDeviceToDevice));
-        CCHECK(hipMemset(cnt.p, 0, 4));
-        hipLaunchKernelGGL(mark_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, adj, L, h->d_live, n, (uint32_t *)work.p, (uint32_t *)cnt.p);
+        if (l <= 1) CCHECK(hipMemcpy(snap, adj, l == 0 ? b0 : bU, hipMemcpyDeviceToDevice));
+        CCHECK(hipMemset(cnt, 0, 4));
+        hipLaunchKernelGGL(mark_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, adj, L, h->d_live, n, work.p, cnt.p);
         CCHECK(hipGetLastError());
         uint32_t nw = 0;
-        CCHECK(hipMemcpy(&nw, cnt.p, 4, hipMemcpyDeviceToHost));
+        CCHECK(hipMemcpy(&nw, cnt, 4, hipMemcpyDeviceToHost));
         if (nw) {
             hipLaunchKernelGGL(wide ? wide_repair_kernel : repair_kernel, dim3(nw), dim3(256), 0, nullptr, h->g.X, h->g.ld, (const uint32_t *)snap.p, adj,
                                L, h->d_live, (const uint32_t *)work.p, nw, alpha, h->two_stage);
@@ -456,15 +443,16 @@ static int consolidate_plain(leann_backend *h) {
     const uint32_t e = h->g.entry;
     if (((h->removed[e >> 3] >> (e & 7)) & 1) && h->n_removed < n) {
         if (h->g.max_level == 0 && h->kind == LEANN_BACKEND_DISKANN) { // the live row nearest to the old medoid's (ties: lower position)
-            DevBuf k, d, c;
-            CCHECK(hipMalloc(&k.p, 8)); CCHECK(hipMalloc(&d.p, 4)); CCHECK(hipMalloc(&c.p, 4));
-            if (int rc = leann_internal_filtered_exact(h->g.X, n, h->g.d, h->g.ld, h->g.X + (size_t)e * h->g.ld, 1, 1, h->d_live, 0, 0, (uint64_t *)k.p,
-                                                       (float *)d.p, (uint32_t *)c.p, nullptr))
+            DeviceBuf<uint64_t> k;
+            DeviceBuf<float> d;
+            DeviceBuf<uint32_t> c;
+            if (k.alloc(1) || d.alloc(1) || c.alloc(1)) return LEANN_ERR_DEVICE;
+            if (int rc = leann_internal_filtered_exact(h->g.X, n, h->g.d, h->g.ld, h->g.X + (size_t)e * h->g.ld, 1, 1, h->d_live, 0, 0, k, d, c, nullptr))
                 return rc;
             uint64_t key = 0;
             uint32_t got = 0;
-            CCHECK(hipMemcpy(&key, k.p, 8, hipMemcpyDeviceToHost));
-            CCHECK(hipMemcpy(&got, c.p, 4, hipMemcpyDeviceToHost));
+            CCHECK(hipMemcpy(&key, k, 8, hipMemcpyDeviceToHost));
+            CCHECK(hipMemcpy(&got, c, 4, hipMemcpyDeviceToHost));
             if (got != 1 || key >= n) { leann_set_error("leann_backend_consolidate: no live row found for the entry point"); return LEANN_ERR_DEVICE; }
             h->g.entry = (uint32_t)key;
         } else { // the live node of the highest level, lowest id on ties; max_level follows it down

@@ -242,20 +242,10 @@ static int rebuild_from_embeddings(const std::string &emb_path, const std::strin
     if (n >= (1ull << 31)) { leann_set_error("%s: too many embeddings (%zu)", emb_path.c_str(), n); return LEANN_ERR_FORMAT; }
     FILE *f = fopen(emb_path.c_str(), "rb");
     if (!f) { leann_set_error("cannot open %s", emb_path.c_str()); return LEANN_ERR_IO; }
-    int ndev = 0;
-    leann_device_count(&ndev);
-    if (device >= ndev) {
-        fclose(f);
-        leann_set_error("HIP device %d not available (%d visible). This library has no CPU fallback.", device, ndev);
-        return LEANN_ERR_DEVICE;
-    }
+    if (int rc = leann_internal_check_device(device)) { fclose(f); return rc; }
     if (hipSetDevice(device) != hipSuccess) { fclose(f); leann_set_error("hipSetDevice(%d) failed", device); return LEANN_ERR_DEVICE; }
-    float *dX = nullptr;
-    if (hipMalloc((void **)&dX, n * ld * 4) != hipSuccess) {
-        fclose(f);
-        leann_set_error("hipMalloc(%zu) for the embeddings failed", n * ld * 4);
-        return LEANN_ERR_DEVICE;
-    }
+    DeviceBuf<float> dX;
+    if (int rc = dX.alloc(n * ld)) { fclose(f); return rc; }
     const size_t slab_rows = std::max<size_t>(1, ((size_t)256 << 20) / (dims * 4));
     std::vector<float> slab(std::min(slab_rows, n) * dims);
     bool ok = ld == dims || hipMemset(dX, 0, n * ld * 4) == hipSuccess;
@@ -265,7 +255,7 @@ static int rebuild_from_embeddings(const std::string &emb_path, const std::strin
              hipMemcpy2D(dX + r0 * ld, ld * 4, slab.data(), dims * 4, dims * 4, rows, hipMemcpyHostToDevice) == hipSuccess;
     }
     fclose(f);
-    if (!ok) { (void)hipFree(dX); leann_set_error("reading %s into device memory failed", emb_path.c_str()); return LEANN_ERR_IO; }
+    if (!ok) { leann_set_error("reading %s into device memory failed", emb_path.c_str()); return LEANN_ERR_IO; }
     // the reference's own build defaults are graph_degree 32, complexity 64 (src/cli/build.rs:78-83); a wider construction beam costs
     // seconds here.  Vamana needs R = 64 beyond ~1M rows.
     size_t degree = backend == LEANN_BACKEND_HNSW ? 32 : 64, complexity = 128;
@@ -273,8 +263,9 @@ static int rebuild_from_embeddings(const std::string &emb_path, const std::strin
     if (const char *e = getenv("LEANN_REBUILD_COMPLEXITY")) complexity = (size_t)atoi(e);
     leann_backend *h = nullptr;
     int rc = leann_backend_build_device(backend, dX, n, dims, ld, degree, complexity, device, 0, 0, &h);
-    if (rc) { (void)hipFree(dX); return rc; }
-    h->owns_rows = true;
+    if (rc) return rc;
+    h->owns_rows = true; // dX now belongs to the handle
+    (void)dX.release();
     if (leann_internal_save_to(h, sidecar) != LEANN_OK) // read-only directory: serve from memory, rebuild again next time
         leann_log(LEANN_LOG_WARN, "could not cache the rebuilt graph as %s (%s); it will be rebuilt on the next open", sidecar.c_str(), leann_last_error());
     *out = h;

@@ -1,6 +1,7 @@
 // internal.h — structs shared by api.hip / build.hip (not part of the C ABI).
 #pragma once
 #include "search.cuh"
+#include "device_mem.h"
 #include "../../include/leann_backend.h"
 #include <atomic>
 #include <map>
@@ -10,18 +11,17 @@
 #include <vector>
 
 struct Workspace { // staging of the host-pointer API; one per concurrent caller
-    float *d_q = nullptr;
-    uint64_t *d_keys = nullptr;
-    float *d_dists = nullptr;
-    uint32_t *d_counts = nullptr, *d_stats = nullptr;
-    uint8_t *d_allow = nullptr; // filtered searches: staged allow-bitmap(s)
-    size_t cap_q = 0, cap_keys = 0, cap_dists = 0, cap_counts = 0, cap_stats = 0, cap_allow = 0;
+    DeviceBuf<float> d_q, d_dists;
+    DeviceBuf<uint64_t> d_keys;
+    DeviceBuf<uint32_t> d_counts, d_stats;
+    DeviceBuf<uint8_t> d_allow; // filtered searches: staged allow-bitmap(s)
     // small calls (a single query is the reference's own call, traits.rs:16-21): one block of pinned, device-mapped host memory
     // {queries | keys | dists | counts | stats}: the kernels read the queries from it and write the results into it, so the call
     // is kernel launches + one stream synchronisation, with no copy engine in between
     unsigned char *pin = nullptr;
     size_t cap_pin = 0;
     hipStream_t stream = nullptr;
+    ~Workspace(); // api.hip: the pinned block and the stream
 };
 
 // Environment knobs of the SEARCH path.  The environment is read ONCE — when the library is first used — into this struct; a search
@@ -60,7 +60,7 @@ struct leann_backend {
     bool nav_levels = false; // Vamana built with entry layers (build.hip); searches need nothing but g.max_level / g.entry
     uint64_t n_upper_lists = 0;
     std::mutex mu;
-    std::vector<Workspace *> free_ws; // host-pointer API: one per concurrent caller
+    std::vector<std::unique_ptr<Workspace>> free_ws; // host-pointer API: one per concurrent caller
     // pooled HBM visited tables (search.cuh): shared by every stream, handed out by in-kernel locks
     unsigned long long *gpool = nullptr, *gpool2 = nullptr;
     uint32_t *gpool_lock = nullptr, *gpool_ctr = nullptr, *gpool2_lock = nullptr;
@@ -69,7 +69,7 @@ struct leann_backend {
     // recompute-on graph mode (g.feat_h != 0): encoder weights as f32 [feat_h x dims] for the query projection and
     // per-stream scratch for the projected queries
     float *Wf32 = nullptr;
-    std::map<hipStream_t, std::pair<float *, size_t>> proj_scratch;
+    std::map<hipStream_t, DeviceBuf<float>> proj_scratch;
     std::shared_ptr<Coalescer> coalescer; // optional request coalescing for single-query callers (api.hip); swapped under `mu`
     // 0 = automatic (default): a leann_backend_search caller that finds another one in flight goes through a dispatcher created on the
     // spot, a lone caller is answered directly; 1 = configured by leann_backend_set_coalescing; 2 = switched off by it
@@ -85,7 +85,7 @@ struct leann_backend {
     size_t n_removed = 0, n_pending = 0;
     uint64_t removal_epoch = 0;
     uint32_t two_stage = 1; // Vamana: the RobustPrune form the build used (LEANN_VAMANA_TWO_STAGE when the handle was made)
-    std::map<hipStream_t, std::pair<uint8_t *, size_t>> live_scratch; // per stream: live AND the caller's bitmap(s)
+    std::map<hipStream_t, DeviceBuf<uint8_t>> live_scratch; // per stream: live AND the caller's bitmap(s)
     // Row screen (planes.hip, row_screen.h): the f32 rows a second time as two planes of 16-bit halves, [n x ldp] u16 each, owned by the
     // handle whoever owns X; planes_src / planes_n / planes_ld name the rows they were cut from.  screen_ctr: device totals
     // {rows ruled out, rows read in full}.  row_screen: 0 off, 1 automatic, 2 on whatever the size (LeannKnobs::row_screen when the
@@ -167,6 +167,7 @@ int leann_internal_from_host(int backend, size_t n, size_t dims, uint32_t M, uin
 //   f32 rows `d_f32_rows` [n x d_f32_ld] (rounded; leann_backend_to_rows) — exactly one of the three.
 int leann_internal_save_to(const leann_backend *h, const std::string &path);
 int leann_internal_parse_device(const char *spec, int *device);
+int leann_internal_check_device(int device); // api.hip: LEANN_ERR_DEVICE and the "no CPU fallback" message unless `device` is a visible one
 // sharded handles (shard.hip)
 bool leann_internal_spec_is_sharded(const char *spec);
 int leann_internal_open_sharded_backend(const char *stem, int backend, size_t dims, const char *spec, leann_backend **out);
@@ -177,7 +178,7 @@ leann_backend *leann_internal_sharded_shard(const leann_sharded *s, size_t g);
 struct leann_filter {
     int device = 0;
     size_t n = 0, n_allowed = 0;
-    uint8_t *d_allow = nullptr;
+    DeviceBuf<uint8_t> d_allow;
     uint32_t *d_list = nullptr; // scratch-pool block (scan.hip), held for the filter's lifetime
     uint64_t epoch = 0;         // the handle's removal_epoch when the filter was made (its bitmap holds live positions only)
     std::vector<leann_filter *> parts;
@@ -217,6 +218,7 @@ int leann_internal_filtered_exact(const float *d_rows, size_t n, size_t dims, si
                                   uint32_t *d_counts, hipStream_t st);
 int leann_internal_compact_allow(const uint8_t *d_allow, size_t n, uint32_t **d_list, size_t *n_list, hipStream_t st);
 int leann_internal_and_live_inplace(const leann_backend *h, uint8_t *d_bitmap);
+int leann_internal_scratch_acquire(void **out, size_t bytes); // scan.hip's pool: blocks are kept for reuse, released after a stream sync
 void leann_internal_scratch_release(void *p);
 extern "C" void leann_sharded_close(leann_sharded *s);
 

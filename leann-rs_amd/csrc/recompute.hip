@@ -251,8 +251,8 @@ __global__ void __launch_bounds__(512) encode_kernel(const uint16_t *__restrict_
 struct leann_recompute {
     int device = 0;
     const uint16_t *F = nullptr; // borrowed [n x h]
-    uint16_t *Wp = nullptr;      // owned, tiled
-    uint16_t *Wraw = nullptr;    // owned copy [h x d] (query projection)
+    DeviceBuf<uint16_t> Wp;      // owned, tiled
+    DeviceBuf<uint16_t> Wraw;    // owned copy [h x d] (query projection)
     size_t n = 0, h = 0, hp = 0, d = 0, dp = 0, ld = 0;
     uint64_t key_offset = 0;
     int ct = 0;                     // dims <= 768: column tiles of the one block (encode_kernel<ct, ..>)
@@ -264,37 +264,24 @@ struct leann_recompute {
     // search scratch, grown on demand and kept (hipMalloc / hipFree of ~1 GB per call costs 2-30 ms depending on the box);
     // one search at a time per handle
     std::mutex mu;
-    float *sS = nullptr;
-    uint16_t *sGp = nullptr;
-    uint64_t *sCandA = nullptr, *sCandB = nullptr, *sBest = nullptr;
-    size_t capS = 0, capGp = 0, capCand = 0, capBest = 0;
-    uint4 *Ft = nullptr;            // fragment-major copy of F (tile_features_kernel), made by the first exhaustive search
-    uint16_t *ownF = nullptr;       // leann_recompute_create_host: the handle's own copy of the features
-    unsigned char *sEmit = nullptr; // [64 f32 thr | 64 u32 cnt | u32 overflow | pad | 64 x EMIT_CAP u64 list]
-    size_t capEmit = 0;
+    DeviceBuf<float> sS;
+    DeviceBuf<uint16_t> sGp;
+    DeviceBuf<uint64_t> sCandA, sCandB, sBest;
+    DeviceBuf<uint4> Ft;            // fragment-major copy of F (tile_features_kernel), made by the first exhaustive search
+    DeviceBuf<uint16_t> ownF;       // leann_recompute_create_host: the handle's own copy of the features
+    DeviceBuf<unsigned char> sEmit; // [64 f32 thr | 64 u32 cnt | u32 overflow | pad | 64 x EMIT_CAP u64 list]
     // sharded form (leann_recompute_create_sharded): the passages live in `parts` (consecutive position ranges, possibly on different
     // devices); this handle owns only the gather block and the per-part staging
     struct Part {
         const leann_recompute *r = nullptr;
         hipStream_t st = nullptr;
         hipEvent_t done = nullptr;
-        unsigned char *stage = nullptr; // remote parts: [queries | keys | scores | counts | mask slice] on the part's device
-        size_t cap_stage = 0;
+        DeviceBuf<unsigned char> stage; // remote parts: [queries | keys | scores | counts | mask slice] on the part's device
     };
     std::vector<Part> parts;
-    unsigned char *gather = nullptr; // [n_parts x {keys | scores | counts}] on `device`
-    size_t cap_gather = 0;
+    DeviceBuf<unsigned char> gather; // [n_parts x {keys | scores | counts}] on `device`
     hipEvent_t ev_q = nullptr;
 };
-static int grow_scratch(void **p, size_t *cap, size_t bytes) {
-    if (bytes <= *cap) return LEANN_OK;
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    HIP_CHECK_RET(hipMalloc(p, bytes));
-    *cap = bytes;
-    return LEANN_OK;
-}
 
 // the feature-stationary fused kernel serves the common shape (one token row per passage, h = 256, dims a multiple of 128);
 // LEANN_DEBUG_FUSED_V1 forces the general kernel (tests compare the two)
@@ -352,12 +339,12 @@ static int launch_encode(const leann_recompute *r, uint64_t row0, uint64_t rows,
         const unsigned grid2 = (unsigned)std::min<uint64_t>(units, (uint64_t)cus);
         const CandEmit em = emit ? *emit : CandEmit{};
         if (idx) // rows [row0, row0 + rows) of the LIST: passage i = row idx[i] of the row-major features
-            return launch_lds(fused_fstat_kernel<16, false, true>, true, grid2, 256, lds2, st, r->F, rows, r->Wp, r->dp, Gp, nq, S, rows, em,
+            return launch_lds(fused_fstat_kernel<16, false, true>, true, grid2, 256, lds2, st, r->F, rows, r->Wp.p, r->dp, Gp, nq, S, rows, em,
                               idx + row0);
         if (r->Ft)
-            return launch_lds(fused_fstat_kernel<16, true>, true, grid2, 256, lds2, st, reinterpret_cast<const uint16_t *>(r->Ft) + row0 * r->h,
-                              rows, r->Wp, r->dp, Gp, nq, S, rows, em, nullptr);
-        return launch_lds(fused_fstat_kernel<16, false>, true, grid2, 256, lds2, st, r->F + row0 * r->h, rows, r->Wp, r->dp, Gp, nq, S, rows, em,
+            return launch_lds(fused_fstat_kernel<16, true>, true, grid2, 256, lds2, st, reinterpret_cast<const uint16_t *>(r->Ft.p) + row0 * r->h,
+                              rows, r->Wp.p, r->dp, Gp, nq, S, rows, em, nullptr);
+        return launch_lds(fused_fstat_kernel<16, false>, true, grid2, 256, lds2, st, r->F + row0 * r->h, rows, r->Wp.p, r->dp, Gp, nq, S, rows, em,
                           nullptr);
     }
     // row0 / rows count PASSAGES; the kernel works on token rows (L per passage, tiles of 128 token rows)
@@ -368,14 +355,14 @@ static int launch_encode(const leann_recompute *r, uint64_t row0, uint64_t rows,
     const bool pool = r->L > 1 || r->mask != nullptr;
     if (r->blocks.n) // dims > 768: column blocks, the LDS ring sized by the widest one
         return launch_lds(encode_find(encode_blocked_rows, 0, fused, pool), true, grid, 512,
-                          encode_lds_bytes(r->hp, (size_t)r->ctb_max * 128, fused), st, F, toks, r->h, r->hp, r->Wp, r->d, r->dp, r->ld, E, Gp,
+                          encode_lds_bytes(r->hp, (size_t)r->ctb_max * 128, fused), st, F, toks, r->h, r->hp, r->Wp.p, r->d, r->dp, r->ld, E, Gp,
                           nq, S, rows, r->L, mk, norms, r->blocks);
     const EncodeKernel kernel = encode_find(encode_rows, r->ct, fused, pool);
     if (!kernel) {
         leann_set_error("recompute: unsupported dims %zu", r->d);
         return LEANN_ERR_INVALID;
     }
-    return launch_lds(kernel, true, grid, 512, encode_lds_bytes(r->hp, r->dp, fused), st, F, toks, r->h, r->hp, r->Wp, r->d, r->ld, E, Gp, nq, S,
+    return launch_lds(kernel, true, grid, 512, encode_lds_bytes(r->hp, r->dp, fused), st, F, toks, r->h, r->hp, r->Wp.p, r->d, r->ld, E, Gp, nq, S,
                       rows, r->L, mk, norms);
 }
 
@@ -385,12 +372,7 @@ extern "C" int leann_recompute_create(const uint16_t *d_features, size_t n, size
         leann_set_error("leann_recompute_create: invalid arguments (n=%zu h=%zu dims=%zu; dims <= %d)", n, h, dims, LEANN_ENCODE_MAX_DIMS);
         return LEANN_ERR_INVALID;
     }
-    int ndev = 0;
-    leann_device_count(&ndev);
-    if (device < 0 || device >= ndev) {
-        leann_set_error("HIP device %d not available (%d visible). This library has no CPU fallback.", device, ndev);
-        return LEANN_ERR_DEVICE;
-    }
+    if (int rc = leann_internal_check_device(device)) return rc;
     HIP_CHECK_RET(hipSetDevice(device));
     // columns -> blocks of compiled widths (encode_plan.h); the LDS check is on the widest BLOCK, not on dp
     const EncodePlan plan = encode_plan(h, dims);
@@ -398,7 +380,7 @@ extern "C" int leann_recompute_create(const uint16_t *d_features, size_t n, size
         leann_set_error("recompute: feature width %zu x dims %zu exceeds the 160 KiB LDS tile", h, dims);
         return LEANN_ERR_INVALID;
     }
-    leann_recompute *r = new leann_recompute();
+    std::unique_ptr<leann_recompute, void (*)(leann_recompute *)> r(new leann_recompute(), leann_recompute_close); // an error return closes it
     r->device = device;
     r->F = d_features;
     r->n = n;
@@ -414,15 +396,14 @@ extern "C" int leann_recompute_create(const uint16_t *d_features, size_t n, size
         for (int b = 0; b < plan.nblk; b++) r->blocks.set((uint32_t)b, (uint32_t)plan.ctb[b]);
     }
     r->key_offset = key_offset;
-    HIP_CHECK_RET(hipMalloc((void **)&r->Wp, r->hp * r->dp * 2));
-    HIP_CHECK_RET(hipMalloc((void **)&r->Wraw, h * dims * 2));
+    if (r->Wp.alloc(r->hp * r->dp) || r->Wraw.alloc(h * dims)) return LEANN_ERR_DEVICE;
     HIP_CHECK_RET(hipMemcpy(r->Wraw, d_weights, h * dims * 2, hipMemcpyDeviceToDevice));
     const uint32_t total = (uint32_t)(r->hp * r->dp);
     hipLaunchKernelGGL(tile_weights_kernel, dim3((total + 255) / 256), dim3(256), 0, nullptr, d_weights, (uint32_t)h, (uint32_t)dims,
-                       (uint32_t)r->hp, (uint32_t)r->dp, r->Wp);
+                       (uint32_t)r->hp, (uint32_t)r->dp, r->Wp.p);
     HIP_CHECK_RET(hipGetLastError());
     HIP_CHECK_RET(hipDeviceSynchronize());
-    *out = r;
+    *out = r.release();
     return LEANN_OK;
 }
 // Token-level provider: features [n x L x h], attention mask [n x L] (0 = padding) -> masked mean pooling
@@ -451,16 +432,10 @@ extern "C" int leann_recompute_create_host(const uint16_t *features, size_t n, s
         leann_set_error("leann_recompute_create_host: invalid arguments (dims=%zu; dims <= %d)", dims, LEANN_ENCODE_MAX_DIMS);
         return LEANN_ERR_INVALID;
     }
-    int ndev = 0;
-    leann_device_count(&ndev);
-    if (device < 0 || device >= ndev) {
-        leann_set_error("HIP device %d not available (%d visible). This library has no CPU fallback.", device, ndev);
-        return LEANN_ERR_DEVICE;
-    }
+    if (int rc = leann_internal_check_device(device)) return rc;
     HIP_CHECK_RET(hipSetDevice(device));
-    uint16_t *dF = nullptr, *dW = nullptr;
-    HIP_CHECK_RET(hipMalloc((void **)&dF, std::max<size_t>(n * h, 8) * 2));
-    if (hipMalloc((void **)&dW, h * dims * 2) != hipSuccess) { (void)hipFree(dF); leann_set_error("hipMalloc failed"); return LEANN_ERR_DEVICE; }
+    DeviceBuf<uint16_t> dF, dW; // dW: copied and re-tiled by create, this call's own to the end
+    if (dF.alloc(std::max<size_t>(n * h, 8)) || dW.alloc(h * dims)) return LEANN_ERR_DEVICE;
     int rc = LEANN_OK;
     if ((n && hipMemcpy(dF, features, n * h * 2, hipMemcpyHostToDevice) != hipSuccess) ||
         hipMemcpy(dW, weights, h * dims * 2, hipMemcpyHostToDevice) != hipSuccess) {
@@ -468,9 +443,8 @@ extern "C" int leann_recompute_create_host(const uint16_t *features, size_t n, s
         rc = LEANN_ERR_DEVICE;
     }
     if (rc == LEANN_OK) rc = leann_recompute_create(dF, n, h, dW, dims, device, key_offset, out);
-    (void)hipFree(dW); // copied and re-tiled by create
-    if (rc != LEANN_OK) { (void)hipFree(dF); return rc; }
-    (*out)->ownF = dF;
+    if (rc != LEANN_OK) return rc;
+    (*out)->ownF = std::move(dF);
     return LEANN_OK;
 }
 extern "C" int leann_recompute_search_batch(const leann_recompute *r, const float *queries, size_t nq, size_t top_k,
@@ -482,10 +456,10 @@ extern "C" int leann_recompute_search_batch(const leann_recompute *r, const floa
     if (nq == 0) return LEANN_OK;
     HIP_CHECK_RET(hipSetDevice(r->device));
     const size_t nmask = allow_mask ? (r->n + 7) / 8 : 0;
-    unsigned char *buf = nullptr; // [queries | keys | scores | counts | mask]
+    DeviceBuf<unsigned char> buf; // [queries | keys | scores | counts | mask]
     const size_t oq = 0, ok = oq + nq * r->d * 4, os = ok + nq * top_k * 8, oc = os + nq * top_k * 4, om = (oc + nq * 4 + 15) & ~(size_t)15;
-    HIP_CHECK_RET(hipMalloc((void **)&buf, om + nmask + 16));
-    int rc = LEANN_OK;
+    int rc = buf.alloc(om + nmask + 16);
+    if (rc) return rc;
     if (hipMemcpy(buf + oq, queries, nq * r->d * 4, hipMemcpyHostToDevice) != hipSuccess ||
         (nmask && hipMemcpy(buf + om, allow_mask, nmask, hipMemcpyHostToDevice) != hipSuccess)) {
         leann_set_error("H2D copy of the queries failed");
@@ -500,7 +474,6 @@ extern "C" int leann_recompute_search_batch(const leann_recompute *r, const floa
         leann_set_error("recompute search: device error: %s", hipGetErrorString(hipGetLastError()));
         rc = LEANN_ERR_DEVICE;
     }
-    (void)hipFree(buf);
     return rc;
 }
 int leann_internal_merge_strided(const void *keys, const void *dists, const void *counts, size_t kstride, size_t dstride, size_t cstride,
@@ -536,7 +509,7 @@ extern "C" int leann_recompute_create_sharded(const leann_recompute *const *part
         r->n += parts[g]->n;
         ok = hipSetDevice(parts[g]->device) == hipSuccess && hipStreamCreateWithFlags(&pt.st, hipStreamNonBlocking) == hipSuccess &&
              hipEventCreateWithFlags(&pt.done, hipEventDisableTiming) == hipSuccess;
-        r->parts.push_back(pt);
+        r->parts.push_back(std::move(pt));
     }
     (void)hipSetDevice(r->device);
     if (!ok) {
@@ -555,7 +528,7 @@ static int sharded_recompute_search(leann_recompute *r, const float *d_queries, 
     std::lock_guard<std::mutex> lk(r->mu); // one search at a time per handle, like a plain handle's scratch
     HIP_CHECK_RET(hipSetDevice(r->device));
     const size_t okeys = 0, oscores = nq * top_k * 8, ocounts = nq * top_k * 12, blk = (nq * top_k * 12 + nq * 4 + 15) & ~(size_t)15;
-    if (int rc = grow_scratch((void **)&r->gather, &r->cap_gather, G * blk)) return rc;
+    if (int rc = r->gather.grow(G * blk)) return rc;
     HIP_CHECK_RET(hipEventRecord(r->ev_q, st)); // queries (and the mask) are ready
     std::vector<int> rcs(G, LEANN_OK);
     std::vector<std::string> errs(G);
@@ -572,11 +545,7 @@ static int sharded_recompute_search(leann_recompute *r, const float *d_queries, 
         unsigned char *outb = r->gather + g * blk;
         if (remote) { // queries (and the part's slice of the mask) travel to the part's device, its lists travel back
             const size_t oq = 0, ob = (nq * r->d * 4 + 15) & ~(size_t)15, om = ob + blk, need = om + mask_b + 16;
-            if (need > pt.cap_stage) {
-                (void)hipFree(pt.stage); pt.stage = nullptr; pt.cap_stage = 0;
-                if (hipMalloc((void **)&pt.stage, need) != hipSuccess) return fail("hipMalloc");
-                pt.cap_stage = need;
-            }
+            if (int rc = pt.stage.grow(need)) return rc;
             if (hipMemcpyPeerAsync(pt.stage + oq, p->device, d_queries, r->device, nq * r->d * 4, pt.st) != hipSuccess) return fail("peer copy of the queries");
             if (mask_b && hipMemcpyPeerAsync(pt.stage + om, p->device, d_allow_mask + mask_off, r->device, mask_b, pt.st) != hipSuccess) return fail("peer copy of the mask");
             q = (const float *)(pt.stage + oq);
@@ -613,22 +582,11 @@ extern "C" void leann_recompute_close(leann_recompute *r) {
         (void)hipSetDevice(pt.r ? pt.r->device : r->device);
         if (pt.st) { (void)hipStreamSynchronize(pt.st); (void)hipStreamDestroy(pt.st); }
         if (pt.done) (void)hipEventDestroy(pt.done);
-        (void)hipFree(pt.stage);
+        pt.stage.reset(); // here: the part's device is current
     }
     if (!r->parts.empty()) (void)hipSetDevice(r->device);
     if (r->ev_q) (void)hipEventDestroy(r->ev_q);
-    (void)hipFree(r->gather);
-    (void)hipFree(r->Wp);
-    (void)hipFree(r->Wraw);
-    (void)hipFree(r->sS);
-    (void)hipFree(r->sGp);
-    (void)hipFree(r->sCandA);
-    (void)hipFree(r->sCandB);
-    (void)hipFree(r->sBest);
-    (void)hipFree(r->sEmit);
-    (void)hipFree(r->Ft);
-    (void)hipFree(r->ownF);
-    delete r;
+    delete r; // the handle's own buffers go with it
 }
 extern "C" size_t leann_recompute_len(const leann_recompute *r) { return r ? r->n : 0; }
 extern "C" int leann_recompute_last_timing(const leann_recompute *r, float *ms3) {
@@ -660,7 +618,6 @@ static int recompute_search_impl(const leann_recompute *r, const float *d_querie
                                  const uint32_t *idx = nullptr, size_t n_list = 0);
 int leann_internal_scan_finish_ex(uint64_t *candA, uint64_t *candB, size_t cand_len, size_t total_segs, size_t nq, uint32_t k, uint64_t key_offset,
                                   uint64_t *d_keys, float *d_scores, uint32_t *d_counts, hipStream_t st, const uint32_t *idx, int as_dist);
-int leann_internal_scratch_acquire(void **out, size_t bytes);
 extern "C" int leann_recompute_search_batch_device(const leann_recompute *r, const float *d_queries, size_t nq, size_t top_k,
                                                    const uint8_t *d_allow_mask, uint64_t *d_keys, float *d_scores,
                                                    uint32_t *d_counts, void *stream) {
@@ -734,25 +691,17 @@ static int recompute_search_impl(const leann_recompute *r, const float *d_querie
         // first exhaustive search on this handle: keep a fragment-major copy of the features (+ n * h * 2 bytes; if HBM is short
         // the kernel reads the caller's row-major array instead, ~10 % slower)
         const uint64_t n_pad = (r->n + 255) / 256 * 256 + 256;
-        if (hipMalloc((void **)&rw->Ft, n_pad * r->h * 2) == hipSuccess) {
-            hipLaunchKernelGGL(tile_features_kernel, dim3(4096), dim3(256), 0, st, r->F, (uint64_t)r->n, (uint32_t)r->h, n_pad, rw->Ft);
+        if (rw->Ft.alloc(n_pad * r->h * 2 / sizeof(uint4)) == LEANN_OK) {
+            hipLaunchKernelGGL(tile_features_kernel, dim3(4096), dim3(256), 0, st, r->F, (uint64_t)r->n, (uint32_t)r->h, n_pad, rw->Ft.p);
             HIP_CHECK_RET(hipGetLastError());
-        } else {
-            (void)hipGetLastError();
-            rw->Ft = nullptr;
         }
     }
     // queries per pass over the passages: the encode GEMM is shared by all of them (fused_fstat_kernel: up to 256, one G sub-slice
     // per 32 queries and unit); the general kernel is built for 64
     const size_t QT = use_fstat(r) ? FSTAT_MAX_QUERIES : 64;
-    if (int e = grow_scratch((void **)&rw->sS, &rw->capS, sizeof(float) * QT * chunk)) return e;
-    if (int e = grow_scratch((void **)&rw->sGp, &rw->capGp, r->hp * QT * 3 * 2 + 1024)) return e; // + the fourth (unused) KiB piece of the last k-step
-    {
-        size_t capB = rw->capCand;
-        if (int e = grow_scratch((void **)&rw->sCandA, &rw->capCand, sizeof(uint64_t) * nq * cand_len)) return e;
-        if (int e = grow_scratch((void **)&rw->sCandB, &capB, sizeof(uint64_t) * nq * cand_len)) return e;
-    }
-    if (int e = grow_scratch((void **)&rw->sBest, &rw->capBest, sizeof(uint64_t) * nq * k)) return e;
+    if (int e = rw->sS.grow(QT * chunk)) return e;
+    if (int e = rw->sGp.grow(r->hp * QT * 3 + 512)) return e; // + the fourth (unused) KiB piece of the last k-step
+    if (rw->sCandA.grow(nq * cand_len) || rw->sCandB.grow(nq * cand_len) || rw->sBest.grow(nq * k)) return LEANN_ERR_DEVICE;
     float *S = rw->sS;
     uint16_t *Gp = rw->sGp;
     uint64_t *candA = rw->sCandA, *candB = rw->sCandB, *best = rw->sBest;
@@ -763,8 +712,8 @@ static int recompute_search_impl(const leann_recompute *r, const float *d_querie
     uint32_t *d_overflow = nullptr;
     if (emit) {
         // [QT f32 thr | QT u32 cnt | u32 overflow | pad to 4 KiB | QT x EMIT_CAP u64 list]
-        if (int e = grow_scratch((void **)&rw->sEmit, &rw->capEmit, 4096 + sizeof(uint64_t) * QT * EMIT_CAP)) return e;
-        em.thr = reinterpret_cast<const float *>(rw->sEmit);
+        if (int e = rw->sEmit.grow(4096 + sizeof(uint64_t) * QT * EMIT_CAP)) return e;
+        em.thr = reinterpret_cast<const float *>(rw->sEmit.p);
         em.cnt = reinterpret_cast<uint32_t *>(rw->sEmit + 1024);
         d_overflow = reinterpret_cast<uint32_t *>(rw->sEmit + 2048);
         em.list = reinterpret_cast<uint64_t *>(rw->sEmit + 4096);
@@ -892,42 +841,41 @@ extern "C" int leann_recompute_build_index(const leann_recompute *r, int backend
     }
     HIP_CHECK_RET(hipSetDevice(r->device));
     const size_t n = r->n, ld = r->ld;
-    float *E = nullptr, *norms = nullptr;
-    HIP_CHECK_RET(hipMalloc((void **)&E, std::max<size_t>(n * ld, 4) * 4));
-    HIP_CHECK_RET(hipMalloc((void **)&norms, std::max<size_t>(n, 1) * 4));
+    DeviceBuf<float> E, norms; // (declared before the handle: it is closed first on an error return)
+    DeviceBuf<unsigned char> rows_b;
+    if (E.alloc(std::max<size_t>(n * ld, 4)) || norms.alloc(std::max<size_t>(n, 1))) return LEANN_ERR_DEVICE;
     int rc = LEANN_OK;
     for (size_t row0 = 0; row0 < n && rc == LEANN_OK; row0 += (size_t)4 << 20) { // transient embeddings, only for construction
         const size_t rows = std::min<size_t>((size_t)4 << 20, n - row0);
         rc = launch_encode(r, row0, rows, E + row0 * ld, nullptr, nullptr, 0, nullptr, norms + row0);
     }
     if (rc == LEANN_OK) HIP_CHECK_RET(hipDeviceSynchronize());
-    leann_backend *h = nullptr;
-    if (rc == LEANN_OK) rc = leann_backend_build_device(backend, E, n, r->d, ld, graph_degree, complexity, r->device, r->key_offset, 0, &h);
-    if (rc != LEANN_OK) { (void)hipFree(E); (void)hipFree(norms); return rc; }
+    leann_backend *built = nullptr;
+    if (rc == LEANN_OK) rc = leann_backend_build_device(backend, E, n, r->d, ld, graph_degree, complexity, r->device, r->key_offset, 0, &built);
+    if (rc != LEANN_OK) return rc;
+    std::unique_ptr<leann_backend, void (*)(leann_backend *)> h(built, leann_backend_close); // borrows E until the swap below
     // swap the rows: features + inline norm replace the embeddings
     const uint32_t hp4 = (uint32_t)((r->h + 3) & ~(size_t)3);
     const bool split = hp4 == 256; // 512-B rows of whole lines + the norms in an array of their own (GraphView::norms)
     const uint32_t row_bytes = split ? 2 * hp4 : (2 * hp4 + 4 + 7) & ~7u;
-    unsigned char *rows_b = nullptr;
-    HIP_CHECK_RET(hipMalloc((void **)&rows_b, std::max<size_t>(n, 1) * row_bytes));
+    if (int e = rows_b.alloc(std::max<size_t>(n, 1) * row_bytes)) return e;
     HIP_CHECK_RET(hipMemset(rows_b, 0, std::max<size_t>(n, 1) * row_bytes));
     const uint64_t total = (uint64_t)n * (hp4 + 2);
     if (total)
-        hipLaunchKernelGGL(pack_feature_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, r->F, norms, (uint64_t)n,
-                           (uint32_t)r->h, hp4, row_bytes, rows_b);
+        hipLaunchKernelGGL(pack_feature_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, r->F, norms.p, (uint64_t)n,
+                           (uint32_t)r->h, hp4, row_bytes, rows_b.p);
     HIP_CHECK_RET(hipMalloc((void **)&h->Wf32, (size_t)hp4 * r->d * 4));
     HIP_CHECK_RET(hipMemset(h->Wf32, 0, (size_t)hp4 * r->d * 4));
     hipLaunchKernelGGL(bf16_to_f32_kernel, dim3((unsigned)((r->h * r->d + 255) / 256)), dim3(256), 0, nullptr, r->Wraw, r->h * r->d, h->Wf32);
     HIP_CHECK_RET(hipGetLastError());
     HIP_CHECK_RET(hipDeviceSynchronize());
-    (void)hipFree(E);
-    if (split) h->g.norms = norms; // (freed with the graph)
-    else (void)hipFree(norms);
-    h->g.X = reinterpret_cast<const float *>(rows_b);
+    E.reset();
+    if (split) h->g.norms = norms.release(); // (freed with the graph)
+    h->g.X = reinterpret_cast<const float *>(rows_b.release()); // now belongs to the handle
     h->owns_rows = true;
     h->g.feat_h = hp4;
     h->g.row_bytes = row_bytes;
-    *out = h;
+    *out = h.release();
     return LEANN_OK;
 }
 

@@ -99,13 +99,10 @@ int leann_internal_bf16_adopt_host(leann_backend *h, const float *f32_rows, cons
     }
     // f32 host rows: through a transient device slab, rounded by the same kernel as every other way in
     const size_t ld = (d + 3) & ~(size_t)3, slab = std::max<size_t>(1, ((size_t)256 << 20) / (ld * 4));
-    float *stage = nullptr;
+    DeviceBuf<float> stage;
     const size_t srows = std::min(slab, n);
-    if (hipMalloc((void **)&stage, srows * ld * 4) != hipSuccess) {
-        leann_set_error("bf16 rows: hipMalloc(%zu) for the staging slab failed: %s", srows * ld * 4, hipGetErrorString(hipGetLastError()));
-        return LEANN_ERR_DEVICE;
-    }
-    int rc = LEANN_OK;
+    int rc = stage.alloc(srows * ld);
+    if (rc) return rc;
     if (ld != d && hipMemset(stage, 0, srows * ld * 4) != hipSuccess) rc = LEANN_ERR_DEVICE;
     for (size_t r0 = 0; rc == LEANN_OK && r0 < n; r0 += slab) {
         const size_t m = std::min(slab, n - r0);
@@ -116,7 +113,6 @@ int leann_internal_bf16_adopt_host(leann_backend *h, const float *f32_rows, cons
         }
         rc = launch_round(stage, m, (uint32_t)d, ld, ldb, store + r0 * ldb, nullptr);
     }
-    (void)hipFree(stage);
     return rc;
 }
 
@@ -188,18 +184,13 @@ extern "C" int leann_backend_build_device_rows(int backend, float *d_vectors, si
         return LEANN_ERR_INVALID;
     }
     if (int rc = leann_internal_check_build_args(backend, graph_degree, complexity)) return rc;
-    int ndev = 0;
-    leann_device_count(&ndev);
-    if (device < 0 || device >= ndev) {
-        leann_set_error("HIP device %d not available (%d visible). This library has no CPU fallback.", device, ndev);
-        return LEANN_ERR_DEVICE;
-    }
+    if (int rc = leann_internal_check_device(device)) return rc;
     HIP_CHECK_RET(hipSetDevice(device));
-    float *rows = d_vectors, *copy = nullptr;
+    float *rows = d_vectors;
+    DeviceBuf<float> copy;
     if (!may_overwrite && n) { // the caller's rows stay as they are: round a transient copy
-        if (hipMalloc((void **)&copy, n * ld * 4) != hipSuccess || hipMemcpy(copy, d_vectors, n * ld * 4, hipMemcpyDeviceToDevice) != hipSuccess) {
+        if (copy.alloc(n * ld) || hipMemcpy(copy, d_vectors, n * ld * 4, hipMemcpyDeviceToDevice) != hipSuccess) {
             leann_set_error("leann_backend_build_device_rows: copying %zu rows failed: %s", n, hipGetErrorString(hipGetLastError()));
-            (void)hipFree(copy);
             return LEANN_ERR_DEVICE;
         }
         rows = copy;
@@ -216,7 +207,7 @@ extern "C" int leann_backend_build_device_rows(int backend, float *d_vectors, si
         h->g.ld = (uint32_t)((dims + 3) & ~(size_t)3); // the store's own geometry: the kernel choice must not depend on the caller's pitch
         rc = leann_internal_bf16_adopt_device(h, rows, ld);
     }
-    (void)hipFree(copy);
+    copy.reset();
     if (rc) { if (h) leann_backend_close(h); return rc; }
     *out = h;
     return LEANN_OK;
@@ -239,17 +230,16 @@ extern "C" int leann_backend_build_rows(int backend, const float *vectors, size_
     }
     HIP_CHECK_RET(hipSetDevice(0));
     const size_t ld = (dims + 3) & ~(size_t)3;
-    float *dX = nullptr;
-    if (hipMalloc((void **)&dX, std::max<size_t>(n * ld, 4) * 4) != hipSuccess ||
+    DeviceBuf<float> dX;
+    if (dX.alloc(std::max<size_t>(n * ld, 4)) ||
         (n && ld != dims && hipMemset(dX, 0, n * ld * 4) != hipSuccess) ||
         (n && hipMemcpy2D(dX, ld * 4, vectors, dims * 4, dims * 4, n, hipMemcpyHostToDevice) != hipSuccess)) {
         leann_set_error("leann_backend_build_rows: upload of %zu rows failed: %s", n, hipGetErrorString(hipGetLastError()));
-        (void)hipFree(dX);
         return LEANN_ERR_DEVICE;
     }
     leann_backend *h = nullptr;
     int rc = leann_backend_build_device_rows(backend, dX, n, dims, ld, graph_degree, complexity, 0, 0, LEANN_ROWS_BF16, 1, &h);
-    (void)hipFree(dX); // the upload was this call's own copy: built on in place, not kept
+    dX.reset(); // the upload was this call's own copy: built on in place, not kept
     if (rc) return rc;
     rc = leann_backend_save(h, index_path_stem);
     leann_backend_close(h);

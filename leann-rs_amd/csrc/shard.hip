@@ -87,15 +87,13 @@ struct ShardDev {
     uint64_t lo = 0;              // first global position of the shard (== h->key_offset)
     hipStream_t st = nullptr;     // traversal stream on the shard's device
     hipEvent_t ev[2] = {nullptr, nullptr};
-    float *d_q = nullptr;         // staged queries (devices other than the first)
-    unsigned char *d_out = nullptr, *d_allow = nullptr; // result block / staged allow-bitmaps (devices other than the first)
-    uint32_t *d_stats = nullptr;  // per-query counters (devices other than the first)
-    size_t cap_q = 0, cap_out = 0, cap_allow = 0, cap_stats = 0;
+    DeviceBuf<float> d_q;         // staged queries (devices other than the first)
+    DeviceBuf<unsigned char> d_out, d_allow; // result block / staged allow-bitmaps (devices other than the first)
+    DeviceBuf<uint32_t> d_stats;  // per-query counters (devices other than the first)
 };
 struct ShardSlot {
-    unsigned char *gather = nullptr, *local = nullptr; // [G x block] on the first device; RCCL mode: this rank's own block
-    uint32_t *stats = nullptr;                          // [G x nq x 4] (one-process mode)
-    size_t cap_gather = 0, cap_local = 0, cap_stats = 0;
+    DeviceBuf<unsigned char> gather, local; // [G x block] on the first device; RCCL mode: this rank's own block
+    DeviceBuf<uint32_t> stats;              // [G x nq x 4] (one-process mode)
     hipEvent_t ev_q = nullptr, done = nullptr;
     bool used = false;
 };
@@ -124,15 +122,6 @@ __global__ void reduce_shard_stats_kernel(const uint32_t *__restrict__ per_shard
         acc = (i & 3) == 3 ? max(acc, v) : acc + v;
     }
     out[i] = acc;
-}
-static int grow_dev(void **p, size_t *cap, size_t bytes) {
-    if (bytes <= *cap) return LEANN_OK;
-    (void)hipFree(*p); // (synchronises the device: nothing still reads the old block)
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc(p, bytes) != hipSuccess) { leann_set_error("hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(hipGetLastError())); return LEANN_ERR_DEVICE; }
-    *cap = bytes;
-    return LEANN_OK;
 }
 
 size_t leann_internal_sharded_count(const leann_sharded *s) { return s ? (s->rccl ? (size_t)s->world : s->shards.size()) : 0; }
@@ -167,14 +156,14 @@ extern "C" void leann_sharded_close(leann_sharded *s) {
         if (const RcclApi *api = rccl_api()) (void)api->CommDestroy(s->comm);
     }
     for (auto &sl : s->slots) {
-        (void)hipFree(sl.gather); (void)hipFree(sl.local); (void)hipFree(sl.stats);
+        sl.gather.reset(); sl.local.reset(); sl.stats.reset(); // here, not in `delete s`: the first device is current
         if (sl.ev_q) (void)hipEventDestroy(sl.ev_q);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
     if (s->xstream) (void)hipStreamDestroy(s->xstream);
     for (auto &sd : s->shards) {
         (void)hipSetDevice(sd.device);
-        (void)hipFree(sd.d_q); (void)hipFree(sd.d_out); (void)hipFree(sd.d_allow); (void)hipFree(sd.d_stats);
+        sd.d_q.reset(); sd.d_out.reset(); sd.d_allow.reset(); sd.d_stats.reset(); // here: the shard's device is current
         for (auto &e : sd.ev) if (e) (void)hipEventDestroy(e);
         if (sd.st) (void)hipStreamDestroy(sd.st);
         if (s->owns_shards && sd.h) leann_backend_close(sd.h);
@@ -204,7 +193,7 @@ extern "C" int leann_sharded_from_handles(leann_backend *const *shards, size_t n
         sd.device = shards[g]->device;
         sd.lo = shards[g]->key_offset;
         s->total_rows += shards[g]->g.n;
-        s->shards.push_back(sd);
+        s->shards.push_back(std::move(sd));
     }
     int rc = init_common(s);
     if (rc) { s->owns_shards = false; leann_sharded_close(s); return rc; }
@@ -356,15 +345,13 @@ static int open_one_shard(const std::string &src, uint64_t src_off, const std::s
         if (rc == LEANN_OK) { leann_backend_close(*out); *out = nullptr; }
         leann_log(LEANN_LOG_WARN, "ignoring stale or unreadable shard cache %s", cache.c_str());
     }
-    int ndev = 0;
-    leann_device_count(&ndev);
-    if (device < 0 || device >= ndev) { leann_set_error("HIP device %d not available (%d visible). This library has no CPU fallback.", device, ndev); return LEANN_ERR_DEVICE; }
+    if (int rc = leann_internal_check_device(device)) return rc;
     HIP_CHECK_RET(hipSetDevice(device));
     const size_t ld = (dims + 3) & ~(size_t)3;
     FILE *f = fopen(src.c_str(), "rb");
     if (!f || fseeko(f, (off_t)(src_off + lo * dims * 4), SEEK_SET) != 0) { if (f) fclose(f); leann_set_error("cannot read %s", src.c_str()); return LEANN_ERR_IO; }
-    float *dX = nullptr;
-    if (hipMalloc((void **)&dX, std::max<size_t>(rows * ld, 4) * 4) != hipSuccess) { fclose(f); leann_set_error("hipMalloc for shard rows failed"); return LEANN_ERR_DEVICE; }
+    DeviceBuf<float> dX;
+    if (int rc = dX.alloc(std::max<size_t>(rows * ld, 4))) { fclose(f); return rc; }
     const size_t slab_rows = std::max<size_t>(1, ((size_t)256 << 20) / (dims * 4));
     std::vector<float> slab(std::min(slab_rows, std::max<size_t>(rows, 1)) * dims);
     bool ok = ld == dims || hipMemset(dX, 0, rows * ld * 4) == hipSuccess;
@@ -374,13 +361,14 @@ static int open_one_shard(const std::string &src, uint64_t src_off, const std::s
              hipMemcpy2D(dX + r0 * ld, ld * 4, slab.data(), dims * 4, dims * 4, nr, hipMemcpyHostToDevice) == hipSuccess;
     }
     fclose(f);
-    if (!ok) { (void)hipFree(dX); leann_set_error("reading rows [%llu, +%zu) of %s failed", (unsigned long long)lo, rows, src.c_str()); return LEANN_ERR_IO; }
+    if (!ok) { leann_set_error("reading rows [%llu, +%zu) of %s failed", (unsigned long long)lo, rows, src.c_str()); return LEANN_ERR_IO; }
     size_t degree = backend == LEANN_BACKEND_HNSW ? 32 : 64, complexity = 128;
     if (const char *e = getenv("LEANN_REBUILD_DEGREE")) degree = (size_t)atoi(e);
     if (const char *e = getenv("LEANN_REBUILD_COMPLEXITY")) complexity = (size_t)atoi(e);
     int rc = leann_backend_build_device(backend, dX, rows, dims, ld, degree, complexity, device, lo, 0, out);
-    if (rc) { (void)hipFree(dX); return rc; }
-    (*out)->owns_rows = true;
+    if (rc) return rc;
+    (*out)->owns_rows = true; // dX now belongs to the handle
+    (void)dX.release();
     if (leann_internal_save_to(*out, cache) != LEANN_OK)
         leann_log(LEANN_LOG_WARN, "could not cache shard graph %s (%s)", cache.c_str(), leann_last_error());
     return LEANN_OK;
@@ -502,7 +490,7 @@ extern "C" int leann_sharded_attach(leann_backend *local, const void *unique_id1
     sd.h = local;
     sd.device = local->device;
     sd.lo = local->key_offset;
-    s->shards.push_back(sd);
+    s->shards.push_back(std::move(sd));
     int rc = init_common(s);
     if (rc) { leann_sharded_close(s); return rc; }
     rcclUniqueId id;
@@ -541,14 +529,14 @@ int leann_internal_sharded_search(leann_sharded *s, const float *d_queries, size
     const uint64_t tk = s->next_ticket++;
     ShardSlot &sl = s->slots[tk & 1];
     const size_t blk = block_bytes(nq, top_k), koff = 0, doff = nq * top_k * 8, coff = nq * top_k * 12;
-    if (int rc = grow_dev((void **)&sl.gather, &sl.cap_gather, G * blk)) return rc;
+    if (int rc = sl.gather.grow(G * blk)) return rc;
     if (d_stats && !s->rccl)
-        if (int rc = grow_dev((void **)&sl.stats, &sl.cap_stats, G * nq * 16)) return rc;
+        if (int rc = sl.stats.grow(G * nq * 4)) return rc;
     HIP_CHECK_RET(hipEventRecord(sl.ev_q, st)); // the queries (and the allow-bitmaps) are ready
     if (s->rccl) {
         const RcclApi *api = rccl_api();
         if (!api) return LEANN_ERR_DEVICE;
-        if (int rc = grow_dev((void **)&sl.local, &sl.cap_local, blk)) return rc;
+        if (int rc = sl.local.grow(blk)) return rc;
         if (sl.used) HIP_CHECK_RET(hipStreamWaitEvent(st, sl.done, 0)); // the all-gather that last read this slot's block has finished
         ShardDev &sd = s->shards[0];
         SearchFilter fg = f;
@@ -571,15 +559,15 @@ int leann_internal_sharded_search(leann_sharded *s, const float *d_queries, size
             const uint8_t *allow_g = d_allow ? d_allow + sd.lo / 8 : nullptr; // the shard's slice of the bitmap(s): its first position is bit 0
             unsigned char *blkp = sl.gather + g * blk;
             if (remote) {
-                if (int rc = grow_dev((void **)&sd.d_q, &sd.cap_q, nq * s->dims * 4)) return rc;
-                if (int rc = grow_dev((void **)&sd.d_out, &sd.cap_out, blk)) return rc;
+                if (int rc = sd.d_q.grow(nq * s->dims)) return rc;
+                if (int rc = sd.d_out.grow(blk)) return rc;
                 HIP_CHECK_RET(hipMemcpyPeerAsync(sd.d_q, sd.device, d_queries, s->primary, nq * s->dims * 4, sd.st));
                 q = sd.d_q;
                 blkp = sd.d_out;
                 if (d_allow) { // only the bytes this shard reads travel: [lo / 8, ceil(hi / 8)) of the shared bitmap, or of the strided block
                     const size_t slice = (sd.h->g.n + 7) / 8;
                     const size_t span = allow_stride ? allow_stride * (nq - 1) + slice : slice;
-                    if (int rc = grow_dev((void **)&sd.d_allow, &sd.cap_allow, span)) return rc;
+                    if (int rc = sd.d_allow.grow(span)) return rc;
                     HIP_CHECK_RET(hipMemcpyPeerAsync(sd.d_allow, sd.device, d_allow + sd.lo / 8, s->primary, span, sd.st));
                     allow_g = sd.d_allow;
                 }
@@ -587,7 +575,7 @@ int leann_internal_sharded_search(leann_sharded *s, const float *d_queries, size
             uint32_t *stats_g = nullptr;
             if (d_stats && !remote) stats_g = sl.stats + g * nq * 4;
             if (d_stats && remote) {
-                if (int rc = grow_dev((void **)&sd.d_stats, &sd.cap_stats, nq * 16)) return rc;
+                if (int rc = sd.d_stats.grow(nq * 4)) return rc;
                 stats_g = sd.d_stats;
             }
             uint64_t *ok = (uint64_t *)(blkp + koff);

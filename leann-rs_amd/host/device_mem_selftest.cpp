@@ -1,0 +1,141 @@
+// device_mem_selftest — the owning buffer type of the host side (csrc/device_mem.h) on the CPU, under AddressSanitizer + UBSan: no
+// GPU, no library.  The two allocation functions the header declares are defined HERE, over malloc / free with counters and a "fail
+// the next N allocations" switch; that link-time seam is the whole hook.  A double free, a leak or a use after free is the
+// sanitizer's to report; the counters check what was asked for and in which order.
+#include "../csrc/device_mem.h"
+
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <map>
+#include <string_view>
+#include <utility>
+
+static long g_live = 0, g_allocs = 0, g_frees = 0;
+static long g_live_at_last_alloc = -1; // blocks alive at the moment of the most recent request
+static size_t g_last_bytes = 0;
+static int g_fail_next = 0;
+static char g_err[256] = "";
+
+extern "C" void leann_set_error(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof g_err, fmt, ap);
+    va_end(ap);
+}
+void *leann_internal_device_alloc(size_t bytes) {
+    g_live_at_last_alloc = g_live;
+    g_last_bytes = bytes;
+    if (g_fail_next > 0) { g_fail_next--; return nullptr; }
+    void *p = malloc(bytes);
+    if (p) { g_live++; g_allocs++; }
+    return p;
+}
+void leann_internal_device_release(void *p) {
+    if (!p) return;
+    g_live--;
+    g_frees++;
+    free(p);
+}
+
+static int g_failed = 0;
+#define CHECK(cond)                                                                  \
+    do {                                                                             \
+        if (!(cond)) { fprintf(stderr, "FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); g_failed++; } \
+    } while (0)
+
+static void takes_pointers(float *a, const float *b) { CHECK(a == b); }
+
+int main() {
+    { // destruction frees exactly once; the conversion hands out the pointer
+        DeviceBuf<float> b;
+        CHECK(b.p == nullptr && b.cap == 0);
+        CHECK(b.alloc(100) == LEANN_OK);
+        CHECK(b.p && b.cap == 100 && g_last_bytes == 400 && g_live == 1);
+        takes_pointers(b, b);
+        b.p[99] = 1.0f; // the block really has 100 elements (AddressSanitizer)
+    }
+    CHECK(g_live == 0 && g_allocs == 1 && g_frees == 1);
+
+    { // move: the source is empty, the moved-to buffer frees
+        DeviceBuf<float> a;
+        CHECK(a.alloc(8) == LEANN_OK);
+        float *p = a.p;
+        DeviceBuf<float> b(std::move(a));
+        CHECK(a.p == nullptr && a.cap == 0 && b.p == p && b.cap == 8 && g_live == 1);
+        DeviceBuf<float> c;
+        CHECK(c.alloc(4) == LEANN_OK && g_live == 2);
+        c = std::move(b); // the assigned-to buffer's own block goes first
+        CHECK(b.p == nullptr && b.cap == 0 && c.p == p && c.cap == 8 && g_live == 1);
+    }
+    CHECK(g_live == 0 && g_allocs == g_frees);
+
+    { // grow at or below the capacity: no request, same pointer; above it: the old block is gone when the new one is asked for
+        DeviceBuf<unsigned long long> b;
+        CHECK(b.grow(10) == LEANN_OK && b.cap == 10 && g_last_bytes == 80);
+        unsigned long long *p = b.p;
+        const long allocs = g_allocs;
+        CHECK(b.grow(10) == LEANN_OK && b.grow(3) == LEANN_OK && b.grow(0) == LEANN_OK);
+        CHECK(b.p == p && b.cap == 10 && g_allocs == allocs);
+        CHECK(b.grow(11) == LEANN_OK);
+        CHECK(g_live_at_last_alloc == 0 && g_allocs == allocs + 1 && b.cap == 11 && g_live == 1);
+        b.p[10] = 1;
+        b.reset();
+        CHECK(b.p == nullptr && b.cap == 0 && g_live == 0);
+        b.reset(); // empty: nothing to free
+        CHECK(g_allocs == g_frees);
+    }
+
+    { // a failed alloc / grow leaves {nullptr, 0} and LEANN_ERR_DEVICE with the byte count in the message; a later grow succeeds
+        DeviceBuf<float> b;
+        g_fail_next = 1;
+        g_err[0] = 0;
+        CHECK(b.alloc(1000) == LEANN_ERR_DEVICE && b.p == nullptr && b.cap == 0 && g_live == 0);
+        CHECK(std::string_view(g_err).find("4000") != std::string_view::npos);
+        CHECK(b.grow(5) == LEANN_OK && b.cap == 5);
+        g_fail_next = 1;
+        g_err[0] = 0;
+        CHECK(b.grow(6) == LEANN_ERR_DEVICE && b.p == nullptr && b.cap == 0 && g_live == 0); // the old block was freed first
+        CHECK(std::string_view(g_err).find("24") != std::string_view::npos);
+        CHECK(b.grow(2) == LEANN_OK && b.p && b.cap == 2 && g_live == 1);
+    }
+    CHECK(g_live == 0);
+
+    { // a zero-size request yields a small non-null block, once
+        DeviceBuf<float> b;
+        CHECK(b.alloc(0) == LEANN_OK && b.p && b.cap == 0 && g_last_bytes > 0 && g_live == 1);
+        const long allocs = g_allocs;
+        CHECK(b.grow(0) == LEANN_OK && g_allocs == allocs);
+        DeviceBuf<float> c;
+        CHECK(c.grow(0) == LEANN_OK && c.p && g_live == 2);
+    }
+    CHECK(g_live == 0);
+
+    { // release: the buffer is empty and the block is the caller's
+        float *p = nullptr;
+        {
+            DeviceBuf<float> b;
+            CHECK(b.alloc(16) == LEANN_OK);
+            p = b.release();
+            CHECK(p && b.p == nullptr && b.cap == 0);
+        }
+        CHECK(g_live == 1);
+        p[15] = 2.0f;
+        leann_internal_device_release(p);
+        CHECK(g_live == 0);
+    }
+
+    { // per-stream scratch: a map entry made by operator[] and grown twice holds one block, none after clear()
+        std::map<int, DeviceBuf<float>> m;
+        CHECK(m[7].grow(10) == LEANN_OK);
+        CHECK(m[7].grow(500) == LEANN_OK);
+        CHECK(m.size() == 1 && m[7].cap == 500 && g_live == 1);
+        m.clear();
+        CHECK(g_live == 0);
+    }
+
+    CHECK(g_live == 0 && g_allocs == g_frees);
+    if (g_failed) { fprintf(stderr, "device_mem_selftest: %d check(s) FAILED\n", g_failed); return 1; }
+    printf("device_mem_selftest ok: %ld blocks allocated and freed\n", g_allocs);
+    return 0;
+}
