@@ -402,7 +402,8 @@ int leann_hybrid_rerank_device(const uint64_t *d_keys, const float *d_dists, con
  * checks of the query arrays are also callable on their own (leann_bm25_check_queries), with no handle and no device.
  * A handle serves one batch at a time (calls on one handle serialise) and holds `leann_bm25_slots` dense accumulators of n_docs
  * floats, sized from a fixed 1 GiB budget (at most 64); a batch is processed in chunks of that many queries.  The *_device calls
- * enqueue on `stream` and return after the stream has finished the batch.  Keys are global positions: the lists of a sharded handle
+ * enqueue on `stream` and return after the stream has finished the batch.  They copy the query tokens and synchronise the stream
+ * inside, so the BM25 *_device calls cannot be captured into a HIP graph.  Keys are global positions: the lists of a sharded handle
  * live on the first device of its list, and a BM25 handle created on that device reranks them unchanged. */
 typedef struct leann_bm25 leann_bm25;
 int leann_bm25_create(size_t n_docs, size_t n_terms, const uint64_t *post_off, const uint32_t *post_doc, const uint32_t *post_tf,
