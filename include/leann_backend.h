@@ -476,6 +476,10 @@ void leann_sharded_close(leann_sharded *s);
 /* Environment knobs (LEANN_COALESCE, LEANN_HNSW_REFERENCE_EF, the LEANN_DEBUG_* test hooks) are read ONCE, when the library is first
  * used — no search call touches the environment.  A test that changes one of them afterwards calls this to have it read again. */
 void leann_debug_reload_env(void);
+/* Test hook: how many device blocks the library owns at this moment — everything its handles, filters and calls in flight hold,
+ * but neither leann_device_malloc memory (the caller's) nor blocks resting in the library's scratch pool.  Back at its earlier
+ * value once whatever was made since has been closed. */
+uint64_t leann_debug_device_blocks(void);
 
 /* raw device memory helpers so that non-torch hosts (the C++ CLI, ctypes tests) need no HIP binding */
 int leann_device_count(int *n);

@@ -33,6 +33,7 @@ SIGNATURES = {
     "leann_last_error": (C.c_char_p, []),
     "leann_version": (C.c_char_p, []),
     "leann_debug_reload_env": (None, []),
+    "leann_debug_device_blocks": (C.c_uint64, []),
     "leann_backend_shard_count": (C.c_size_t, [vp]),
     "leann_backend_shard": (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
     "leann_hybrid_rerank_device": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp, C.c_size_t, C.c_size_t, C.c_float, C.c_int,

@@ -86,6 +86,9 @@ const LeannKnobs &leann_knobs() {
 }
 // test hook: re-read the environment (the previous struct is left alive on purpose: a search in flight may still be reading it)
 extern "C" void leann_debug_reload_env(void) { g_knobs.store(read_knobs_from_env(), std::memory_order_release); }
+// test hook: device blocks the library owns now, through a DeviceBuf or a ScratchLease (blocks idle in the scratch pool do not count)
+std::atomic<uint64_t> leann_internal_device_blocks{0};
+extern "C" uint64_t leann_debug_device_blocks(void) { return leann_internal_device_blocks.load(); }
 
 // ---- raw device helpers ---------------------------------------------------------------------------
 extern "C" int leann_device_count(int *n) {
@@ -108,9 +111,13 @@ extern "C" int leann_device_free(void *p) {
 void *leann_internal_device_alloc(size_t bytes) {
     void *p = nullptr;
     if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    leann_internal_device_blocks++;
     return p;
 }
-void leann_internal_device_release(void *p) { (void)hipFree(p); }
+void leann_internal_device_release(void *p) {
+    if (p) leann_internal_device_blocks--;
+    (void)hipFree(p);
+}
 int leann_internal_check_device(int device) {
     int ndev = 0;
     leann_device_count(&ndev);
@@ -177,38 +184,21 @@ static int ensure_gpool(leann_backend *h) {
     // still being zeroed under them (entries lost -> nodes visited twice -> results off the oracle's; seen once the migration came a
     // few microseconds earlier, tests/test_gpu_parity.py::test_visited_table_overflow_moves_to_hbm_pool).  Once per handle.
     if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize");
-    h->gpool_lock = lock.release(); // now belong to the handle (leann_internal_free_graph)
+    h->gpool_lock = std::move(lock); // now belong to the handle
     h->gpool_ctr = h->gpool_lock + tables;
     h->gpool_bits = bits;
     h->gpool_tables = tables;
-    h->gpool2 = p2.release();
-    h->gpool2_lock = lock2.release();
+    h->gpool2 = std::move(p2);
+    h->gpool2_lock = std::move(lock2);
     h->gpool2_bits = bits2;
     h->gpool2_tables = tables2;
-    h->gpool = p.release();
+    h->gpool = std::move(p);
     return LEANN_OK;
 }
 static void set_pool_args(const leann_backend *h, SearchArgs &a) {
     a.gpool = h->gpool; a.gpool_lock = h->gpool_lock; a.gpool_ctr = h->gpool_ctr;
     a.gpool_bits = h->gpool_bits; a.gpool_tables = h->gpool_tables;
     a.gpool2 = h->gpool2; a.gpool2_lock = h->gpool2_lock; a.gpool2_bits = h->gpool2_bits; a.gpool2_tables = h->gpool2_tables;
-}
-
-void leann_internal_free_graph(leann_backend *h) {
-    if (h->owns_rows) (void)hipFree((void *)h->g.X);
-    (void)hipFree((void *)h->g.norms);
-    (void)hipFree((void *)h->g.adj0);
-    (void)hipFree((void *)h->g.adjU);
-    (void)hipFree((void *)h->g.upper_off);
-    (void)hipFree(h->d_levels);
-    (void)hipFree(h->gpool);
-    (void)hipFree(h->gpool_lock);
-    (void)hipFree(h->gpool2);
-    (void)hipFree(h->gpool2_lock);
-    (void)hipFree(h->Wf32);
-    h->proj_scratch.clear();
-    leann_internal_free_removed(h);
-    leann_internal_free_planes(h);
 }
 
 extern "C" void leann_backend_close(leann_backend *h) {
@@ -218,8 +208,8 @@ extern "C" void leann_backend_close(leann_backend *h) {
     (void)hipDeviceSynchronize(); // before anything the handle owns is freed, here or in `delete h`: no stream still runs on it
     h->free_ws.clear();
     if (h->sharded) leann_sharded_close(h->sharded); // composite handle: the sub-indexes own the device memory
-    else leann_internal_free_graph(h);
-    delete h;
+    else leann_internal_free_planes(h);              // (for its log line)
+    delete h; // every device block of the handle is a member that frees itself
 }
 extern "C" size_t leann_backend_len(const leann_backend *h) { return h ? (size_t)h->g.n : 0; }
 extern "C" size_t leann_backend_dims(const leann_backend *h) { return h ? (size_t)h->g.d : 0; }
@@ -499,8 +489,7 @@ extern "C" void leann_backend_filter_free(leann_filter *f) {
     }
     (void)hipSetDevice(f->device);
     (void)hipDeviceSynchronize(); // searches on any stream may still be reading the bitmap / the list
-    leann_internal_scratch_release(f->d_list);
-    delete f; // the bitmap goes with it, on the filter's device and after the synchronisation above
+    delete f; // the bitmap and the list go with it, on the filter's device and after the synchronisation above
 }
 extern "C" int leann_backend_search_filter_batch(const leann_backend *hc, const float *queries, size_t nq, size_t top_k, size_t complexity,
                                                  const leann_filter *filter, int mode, uint64_t *keys, float *dists, uint32_t *counts) {
@@ -949,18 +938,20 @@ int leann_internal_from_host(int backend, size_t n, size_t dims, uint32_t M, uin
     h->g.entry = entry;
     h->n_upper_lists = n_upper_lists;
     if (const char *e = getenv("LEANN_VAMANA_TWO_STAGE")) h->two_stage = strcmp(e, "0") != 0; // the prune form consolidation repairs with
-    // every allocation lands in the handle at once, so that one leann_backend_close frees whatever a failure leaves behind
-    auto fail = [&](const char *what) {
-        leann_set_error("leann_backend_from_arrays: %s failed: %s", what, hipGetErrorString(hipGetLastError()));
+    // every allocation is a member of the handle, so that one leann_backend_close frees whatever a failure leaves behind
+    auto fail = [&](const char *what) { // (null: a failed allocation, which has set the message)
+        if (what) leann_set_error("leann_backend_from_arrays: %s failed: %s", what, hipGetErrorString(hipGetLastError()));
         leann_backend_close(h);
         return LEANN_ERR_DEVICE;
     };
     const size_t nn = std::max<size_t>(n, 1), nu = std::max<size_t>(n_upper_lists, 1), ld = h->g.ld;
+    GraphStore &st = h->store;
     if (feat) {
         h->g.feat_h = feat_h;
         if (feat_h == 256) { // split device layout (GraphView::norms): 512-B rows of whole lines, norms beside them
             h->g.row_bytes = 512;
-            if (hipMalloc((void **)&h->g.X, nn * 512) != hipSuccess || hipMalloc((void **)&h->g.norms, nn * 4) != hipSuccess) return fail("hipMalloc(rows)");
+            if (st.rows.alloc(nn * 512) || st.norms.alloc(nn)) return fail(nullptr);
+            h->g.norms = st.norms;
             const size_t slab = (size_t)1 << 20; // de-interleaved on the host, uploaded contiguously
             std::vector<unsigned char> fr(std::min(slab, nn) * 512);
             std::vector<float> nr(std::min(slab, nn));
@@ -970,37 +961,38 @@ int leann_internal_from_host(int backend, size_t n, size_t dims, uint32_t M, uin
                     memcpy(fr.data() + i * 512, feat_rows + (s0 + i) * row_bytes, 512);
                     memcpy(&nr[i], feat_rows + (s0 + i) * row_bytes + 512, 4);
                 }
-                if (hipMemcpy((unsigned char *)h->g.X + s0 * 512, fr.data(), m * 512, hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy((void *)(h->g.norms + s0), nr.data(), m * 4, hipMemcpyHostToDevice) != hipSuccess)
+                if (hipMemcpy(st.rows + s0 * 512, fr.data(), m * 512, hipMemcpyHostToDevice) != hipSuccess ||
+                    hipMemcpy(st.norms + s0, nr.data(), m * 4, hipMemcpyHostToDevice) != hipSuccess)
                     return fail("upload of the feature rows");
             }
         } else {
             h->g.row_bytes = row_bytes;
-            if (hipMalloc((void **)&h->g.X, nn * row_bytes) != hipSuccess) return fail("hipMalloc(rows)");
-            if (n && hipMemcpy((void *)h->g.X, feat_rows, n * (size_t)row_bytes, hipMemcpyHostToDevice) != hipSuccess) return fail("upload of the feature rows");
+            if (st.rows.alloc(nn * row_bytes)) return fail(nullptr);
+            if (n && hipMemcpy(st.rows, feat_rows, n * (size_t)row_bytes, hipMemcpyHostToDevice) != hipSuccess) return fail("upload of the feature rows");
         }
-        if (hipMalloc((void **)&h->Wf32, (size_t)feat_h * dims * 4) != hipSuccess) return fail("hipMalloc(weights)");
+        h->g.X = reinterpret_cast<const float *>(st.rows.p);
+        if (h->Wf32.alloc((size_t)feat_h * dims)) return fail(nullptr);
         if (hipMemcpy(h->Wf32, Wf32, (size_t)feat_h * dims * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("upload of the weights");
     } else if (bf16) {
         const int rc = d_f32_rows ? leann_internal_bf16_adopt_device(h, d_f32_rows, d_f32_ld) : leann_internal_bf16_adopt_host(h, vectors, bf16_rows);
         if (rc) { leann_backend_close(h); return rc; }
     } else {
-        if (hipMalloc((void **)&h->g.X, std::max<size_t>(n * ld, 4) * 4) != hipSuccess) return fail("hipMalloc(rows)");
+        if (st.rows.alloc(std::max<size_t>(n * ld, 4) * 4)) return fail(nullptr);
+        h->g.X = reinterpret_cast<const float *>(st.rows.p);
         if (n) {
-            if (ld == dims) { if (hipMemcpy((void *)h->g.X, vectors, n * dims * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("upload of the rows"); }
-            else if (hipMemset((void *)h->g.X, 0, n * ld * 4) != hipSuccess ||
-                     hipMemcpy2D((void *)h->g.X, ld * 4, vectors, dims * 4, dims * 4, n, hipMemcpyHostToDevice) != hipSuccess) return fail("upload of the rows");
+            if (ld == dims) { if (hipMemcpy(st.rows, vectors, n * dims * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("upload of the rows"); }
+            else if (hipMemset(st.rows, 0, n * ld * 4) != hipSuccess ||
+                     hipMemcpy2D(st.rows, ld * 4, vectors, dims * 4, dims * 4, n, hipMemcpyHostToDevice) != hipSuccess) return fail("upload of the rows");
         }
     }
-    if (hipMalloc((void **)&h->g.adj0, nn * M0 * 4) != hipSuccess || hipMalloc((void **)&h->g.adjU, nu * M * 4) != hipSuccess ||
-        hipMalloc((void **)&h->g.upper_off, nn * 4) != hipSuccess || hipMalloc((void **)&h->d_levels, nn) != hipSuccess)
-        return fail("hipMalloc(graph arrays)");
-    if (hipMemset((void *)h->g.adjU, 0xFF, nu * M * 4) != hipSuccess) return fail("hipMemset");
+    if (st.adj0.alloc(nn * M0) || st.adjU.alloc(nu * M) || st.upper_off.alloc(nn) || st.levels.alloc(nn)) return fail(nullptr);
+    h->g.adj0 = st.adj0; h->g.adjU = st.adjU; h->g.upper_off = st.upper_off;
+    if (hipMemset(st.adjU, 0xFF, nu * M * 4) != hipSuccess) return fail("hipMemset");
     if (n) {
-        if (hipMemcpy((void *)h->g.adj0, adj0, n * M0 * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy((void *)h->g.upper_off, upper_off, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            (levels ? hipMemcpy(h->d_levels, levels, n, hipMemcpyHostToDevice) : hipMemset(h->d_levels, 0, n)) != hipSuccess ||
-            (n_upper_lists && hipMemcpy((void *)h->g.adjU, adjU, n_upper_lists * M * 4, hipMemcpyHostToDevice) != hipSuccess))
+        if (hipMemcpy(st.adj0, adj0, n * M0 * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(st.upper_off, upper_off, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            (levels ? hipMemcpy(st.levels, levels, n, hipMemcpyHostToDevice) : hipMemset(st.levels, 0, n)) != hipSuccess ||
+            (n_upper_lists && hipMemcpy(st.adjU, adjU, n_upper_lists * M * 4, hipMemcpyHostToDevice) != hipSuccess))
             return fail("upload of the graph arrays");
     }
     if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize"); // the fills above are null-stream work; searches run on non-blocking streams
@@ -1050,7 +1042,7 @@ extern "C" int leann_backend_graph_export(const leann_backend *h, uint8_t *level
     HIP_CHECK_RET(hipDeviceSynchronize());
     const size_t n = h->g.n;
     if (n == 0) return LEANN_OK;
-    if (levels) HIP_CHECK_RET(hipMemcpy(levels, h->d_levels, n, hipMemcpyDeviceToHost));
+    if (levels) HIP_CHECK_RET(hipMemcpy(levels, h->store.levels, n, hipMemcpyDeviceToHost));
     if (upper_off) HIP_CHECK_RET(hipMemcpy(upper_off, h->g.upper_off, n * 4, hipMemcpyDeviceToHost));
     if (adj0) HIP_CHECK_RET(hipMemcpy(adj0, h->g.adj0, n * h->g.M0 * 4, hipMemcpyDeviceToHost));
     if (adjU && h->n_upper_lists)

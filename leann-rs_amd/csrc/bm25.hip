@@ -44,12 +44,6 @@
 #define BM25_CAND_CAP 8192 // candidate list per slot; also the first two row ranges, which therefore cannot overflow
 #define BM25_MAX_GRID_X 2048
 
-// scan.hip
-int leann_internal_topk_chunk(const float *S, size_t rows, size_t nq, uint32_t k, const uint8_t *allow, uint64_t pos0, uint64_t *cand,
-                              size_t cand_len, size_t seg_off, hipStream_t st, size_t *segs_out, uint64_t *best);
-int leann_internal_scan_finish(uint64_t *candA, uint64_t *candB, size_t cand_len, size_t total_segs, size_t nq, uint32_t k,
-                               uint64_t key_offset, uint64_t *d_keys, float *d_scores, uint32_t *d_counts, hipStream_t st);
-
 struct Bm25Tok { // one known query token: its posting list and idf
     uint64_t begin;
     uint32_t len;

@@ -586,8 +586,8 @@ static int build_on_device(leann_backend *h, size_t n_existing, size_t bmax_hint
     b.batch_fraction = (size_t)env_int("LEANN_BUILD_BATCH_FRACTION", 8, 1, 1 << 20);
     const size_t n = h->g.n;
     BCHECK(hipStreamCreateWithFlags(&b.st, hipStreamNonBlocking));
-    b.lv.adj0 = const_cast<uint32_t *>(h->g.adj0);
-    b.lv.adjU = const_cast<uint32_t *>(h->g.adjU);
+    b.lv.adj0 = h->store.adj0;
+    b.lv.adjU = h->store.adjU;
     b.lv.upper_off = h->g.upper_off;
     b.lv.M = h->g.M;
     b.lv.M0 = h->g.M0;
@@ -614,7 +614,7 @@ static int build_on_device(leann_backend *h, size_t n_existing, size_t bmax_hint
         }
     }
     b.levels.resize(std::max<size_t>(n, 1));
-    BCHECK(hipMemcpy(b.levels.data(), h->d_levels, n, hipMemcpyDeviceToHost));
+    BCHECK(hipMemcpy(b.levels.data(), h->store.levels, n, hipMemcpyDeviceToHost));
     if (int rc = b.d_order.alloc(std::max<size_t>(n, 1))) return rc;
     int rc = LEANN_OK;
     size_t s0 = n_existing;
@@ -647,7 +647,7 @@ static int build_on_device(leann_backend *h, size_t n_existing, size_t bmax_hint
     } else {
         insertion_order(b.order, n_existing, n);
         // append: the existing links' stored distances (read by reverse_merge_kernel when a list is pruned)
-        hipLaunchKernelGGL(link_dist_kernel, dim3((unsigned)((n_existing + 3) / 4)), dim3(256), 0, b.st, h->g.X, h->g.ld, b.lv, h->d_levels,
+        hipLaunchKernelGGL(link_dist_kernel, dim3((unsigned)((n_existing + 3) / 4)), dim3(256), 0, b.st, h->g.X, h->g.ld, b.lv, h->store.levels.p,
                            (uint32_t)n_existing);
         BCHECK(hipGetLastError());
     }
@@ -693,15 +693,16 @@ static int alloc_graph_arrays(leann_backend *h, uint64_t level_seed) {
     }
     h->n_upper_lists = nu;
     DeviceBuf<uint32_t> adj0, adjU, duo; // this call's own until the last lines: an earlier return frees them
-    if (adj0.alloc(nn * h->g.M0) || adjU.alloc(std::max<uint64_t>(nu, 1) * h->g.M) || duo.alloc(nn)) return LEANN_ERR_DEVICE;
-    BCHECK(hipMalloc((void **)&h->d_levels, nn));
+    DeviceBuf<uint8_t> dlv;
+    if (adj0.alloc(nn * h->g.M0) || adjU.alloc(std::max<uint64_t>(nu, 1) * h->g.M) || duo.alloc(nn) || dlv.alloc(nn)) return LEANN_ERR_DEVICE;
     BCHECK(hipMemset(adj0, 0xFF, nn * h->g.M0 * 4));
     BCHECK(hipMemset(adjU, 0xFF, std::max<uint64_t>(nu, 1) * h->g.M * 4));
     BCHECK(hipMemcpy(duo, uo.data(), nn * 4, hipMemcpyHostToDevice));
-    BCHECK(hipMemcpy(h->d_levels, levels.data(), nn, hipMemcpyHostToDevice));
-    h->g.adj0 = adj0.release();
-    h->g.adjU = adjU.release();
-    h->g.upper_off = duo.release();
+    BCHECK(hipMemcpy(dlv, levels.data(), nn, hipMemcpyHostToDevice));
+    h->g.adj0 = h->store.adj0 = std::move(adj0);
+    h->g.adjU = h->store.adjU = std::move(adjU);
+    h->g.upper_off = h->store.upper_off = std::move(duo);
+    h->store.levels = std::move(dlv);
     return LEANN_OK;
 }
 
@@ -726,10 +727,6 @@ int leann_internal_check_build_args(int backend, size_t graph_degree, size_t com
     }
     return check_degree(backend, graph_degree, complexity);
 }
-// the device build WITHOUT the row screen's split planes: for a caller that replaces the f32 rows afterwards (rows_bf16.hip) — the
-// planes would be a second full-size copy of rows that are about to go
-int leann_internal_build_device_no_planes(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld, size_t graph_degree,
-                                          size_t complexity, int device, uint64_t key_offset, leann_backend **out);
 // `planes`: cut the row screen's split planes (planes.hip) for the new handle — not for one that is only saved and closed again
 static int build_device_guarded(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld, size_t graph_degree, size_t complexity,
                                 int device, uint64_t key_offset, int take_copy, leann_backend **out, bool planes) {
@@ -745,6 +742,8 @@ extern "C" int leann_backend_build_device(int backend, const float *d_vectors, s
                                           int take_copy, leann_backend **out) {
     return build_device_guarded(backend, d_vectors, n, dims, ld, graph_degree, complexity, device, key_offset, take_copy, out, true);
 }
+// the device build WITHOUT the row screen's split planes: for a caller that replaces the f32 rows afterwards (rows_bf16.hip) — the
+// planes would be a second full-size copy of rows that are about to go
 int leann_internal_build_device_no_planes(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld, size_t graph_degree,
                                           size_t complexity, int device, uint64_t key_offset, leann_backend **out) {
     return build_device_guarded(backend, d_vectors, n, dims, ld, graph_degree, complexity, device, key_offset, 0, out, false);
@@ -778,15 +777,13 @@ static int build_device_impl(int backend, const float *d_vectors, size_t n, size
         DeviceBuf<float> cp;
         if (cp.alloc(std::max<size_t>(n * ld, 4)) || (n && hipMemcpy(cp, d_vectors, n * ld * 4, hipMemcpyDeviceToDevice) != hipSuccess)) {
             leann_set_error("build: copying %zu rows failed: %s", n, hipGetErrorString(hipGetLastError()));
-            h->owns_rows = false;
             leann_backend_close(h);
             return LEANN_ERR_DEVICE;
         }
-        h->g.X = cp.release();
-        h->owns_rows = true;
+        h->g.X = cp;
+        h->store.rows = DeviceBuf<unsigned char>(std::move(cp));
     } else {
-        h->g.X = d_vectors;
-        h->owns_rows = false;
+        h->g.X = d_vectors; // borrowed: store.rows stays empty
     }
     int rc = alloc_graph_arrays(h, LEVEL_SEED);
     if (rc == LEANN_OK && n) rc = build_on_device(h, 0, 0);
@@ -887,16 +884,15 @@ extern "C" int leann_backend_add(int backend, const float *vectors, size_t n, si
     h->efc = old->efc;
     h->alpha = old->alpha;
     h->g = old->g;
-    h->g.X = dX;
+    h->g.X = dX; // borrowed
     h->g.n = nt;
     h->g.adj0 = nullptr; h->g.adjU = nullptr; h->g.upper_off = nullptr;
-    h->owns_rows = false;
     rc = alloc_graph_arrays(h, LEVEL_SEED);
     bool same_levels = true; // an index that did not come from this builder (leann_backend_from_arrays + save) has its own level table
     if (rc == LEANN_OK && n_old) {
         std::vector<uint8_t> la(n_old), lb(n_old);
-        if (hipMemcpy(la.data(), old->d_levels, n_old, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(lb.data(), h->d_levels, n_old, hipMemcpyDeviceToHost) != hipSuccess) {
+        if (hipMemcpy(la.data(), old->store.levels, n_old, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(lb.data(), h->store.levels, n_old, hipMemcpyDeviceToHost) != hipSuccess) {
             leann_set_error("add_to_index: reading the level tables failed");
             rc = LEANN_ERR_DEVICE;
         } else {
@@ -915,8 +911,8 @@ extern "C" int leann_backend_add(int backend, const float *vectors, size_t n, si
         return rc;
     }
     if (rc == LEANN_OK && n_old) {
-        if (hipMemcpy(const_cast<uint32_t *>(h->g.adj0), old->g.adj0, n_old * h->g.M0 * 4, hipMemcpyDeviceToDevice) != hipSuccess ||
-            (old->n_upper_lists && hipMemcpy(const_cast<uint32_t *>(h->g.adjU), old->g.adjU, old->n_upper_lists * h->g.M * 4,
+        if (hipMemcpy(h->store.adj0, old->g.adj0, n_old * h->g.M0 * 4, hipMemcpyDeviceToDevice) != hipSuccess ||
+            (old->n_upper_lists && hipMemcpy(h->store.adjU, old->g.adjU, old->n_upper_lists * h->g.M * 4,
                                              hipMemcpyDeviceToDevice) != hipSuccess)) {
             leann_set_error("add_to_index: copying the existing graph failed");
             rc = LEANN_ERR_DEVICE;

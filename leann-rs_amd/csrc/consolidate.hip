@@ -219,7 +219,7 @@ __global__ void __launch_bounds__(256) wide_repair_kernel(const float *__restric
 static LevelLists level_lists(const leann_backend *h, uint32_t level) {
     LevelLists L;
     L.upper_off = h->g.upper_off;
-    L.levels = h->d_levels;
+    L.levels = h->store.levels;
     L.level = level;
     L.W = level == 0 ? h->g.M0 : h->g.M;
     return L;
@@ -255,23 +255,17 @@ static int upload_live(leann_backend *h) {
     if (n & 7) live[nbytes - 1] &= (uint8_t)((1u << (n & 7)) - 1u);
     CCHECK(hipSetDevice(h->device));
     CCHECK(hipDeviceSynchronize());
-    if (!h->d_live) CCHECK(hipMalloc((void **)&h->d_live, std::max<size_t>(nbytes, 1) + 16));
+    if (!h->d_live && h->d_live.alloc(std::max<size_t>(nbytes, 1) + 16)) return LEANN_ERR_DEVICE;
     CCHECK(hipMemcpy(h->d_live, live.data(), nbytes, hipMemcpyHostToDevice));
     if (int rc = count_pending(h, &h->n_pending)) return rc;
     CCHECK(hipDeviceSynchronize());
     return LEANN_OK;
 }
 
-void leann_internal_free_removed(leann_backend *h) {
-    (void)hipFree(h->d_live);
-    h->d_live = nullptr;
-    h->live_scratch.clear();
-}
-
 int leann_internal_set_removed(leann_backend *h, const uint8_t *bitmap, size_t n_removed) {
     if (h->sharded) { leann_set_error("tombstones are kept per shard"); return LEANN_ERR_UNSUPPORTED; }
     const size_t nbytes = (h->g.n + 7) / 8;
-    if (h->d_live) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); (void)hipFree(h->d_live); h->d_live = nullptr; }
+    if (h->d_live) { (void)hipSetDevice(h->device); (void)hipDeviceSynchronize(); h->d_live.reset(); }
     h->removed.assign(bitmap, bitmap + nbytes);
     h->n_removed = n_removed;
     h->n_pending = 0;
@@ -420,7 +414,7 @@ static int consolidate_plain(leann_backend *h) {
     const bool wide = std::max(h->g.M0, h->g.M) > 64;
     const float alpha = h->kind == LEANN_BACKEND_DISKANN ? h->alpha : 0.f;
     for (uint32_t l = 0; l <= h->g.max_level; l++) {
-        uint32_t *adj = const_cast<uint32_t *>(l == 0 ? h->g.adj0 : h->g.adjU);
+        uint32_t *adj = l == 0 ? h->store.adj0 : h->store.adjU;
         const LevelLists L = level_lists(h, l);
         // N(.) is read as it was before this consolidate.  The upper lists share one array and the lists of different levels are
         // disjoint, so the snapshot taken at level 1 serves every level above it.
@@ -457,7 +451,7 @@ static int consolidate_plain(leann_backend *h) {
             h->g.entry = (uint32_t)key;
         } else { // the live node of the highest level, lowest id on ties; max_level follows it down
             std::vector<uint8_t> lv(n);
-            CCHECK(hipMemcpy(lv.data(), h->d_levels, n, hipMemcpyDeviceToHost));
+            CCHECK(hipMemcpy(lv.data(), h->store.levels, n, hipMemcpyDeviceToHost));
             int best_l = -1;
             uint32_t best = 0;
             for (uint32_t v = 0; v < n; v++)

@@ -264,8 +264,7 @@ static int rebuild_from_embeddings(const std::string &emb_path, const std::strin
     leann_backend *h = nullptr;
     int rc = leann_backend_build_device(backend, dX, n, dims, ld, degree, complexity, device, 0, 0, &h);
     if (rc) return rc;
-    h->owns_rows = true; // dX now belongs to the handle
-    (void)dX.release();
+    h->store.rows = DeviceBuf<unsigned char>(std::move(dX)); // the handle borrowed dX until here
     if (leann_internal_save_to(h, sidecar) != LEANN_OK) // read-only directory: serve from memory, rebuild again next time
         leann_log(LEANN_LOG_WARN, "could not cache the rebuilt graph as %s (%s); it will be rebuilt on the next open", sidecar.c_str(), leann_last_error());
     *out = h;

@@ -1,4 +1,6 @@
-// internal.h — structs shared by api.hip / build.hip (not part of the C ABI).
+// internal.h — structs and functions shared by the .hip files (not part of the C ABI).  Every leann_internal_* function is declared
+// once, here (the four allocation functions: device_mem.h).  Whatever a handle holds on its device is a DeviceBuf member of
+// leann_backend / GraphStore, or a ScratchLease: `delete` frees it, nothing is freed by hand.
 #pragma once
 #include "search.cuh"
 #include "device_mem.h"
@@ -44,16 +46,24 @@ struct LeannKnobs {
 };
 const LeannKnobs &leann_knobs();
 extern "C" void leann_debug_reload_env(void);
+extern std::atomic<uint64_t> leann_internal_device_blocks; // api.hip: blocks owned through DeviceBuf and ScratchLease (leann_debug_device_blocks)
 
+// What a plain handle's graph owns on its device.  GraphView (search.cuh) is the kernels' read-only view of it: its pointers are set
+// from these members next to the allocation that fills them.  Builder and graph repair write through the members.
+struct GraphStore {
+    DeviceBuf<unsigned char> rows; // f32 rows, the bf16 store or feature rows; EMPTY = g.X names the caller's rows (borrowed)
+    DeviceBuf<float> norms;        // split feat_h == 256 layout only
+    DeviceBuf<uint32_t> adj0, adjU, upper_off;
+    DeviceBuf<uint8_t> levels;
+};
 struct Coalescer;
 struct leann_sharded;
 struct leann_backend {
     leann_sharded *sharded = nullptr; // composite handle (shard.hip): searches fan out to the sub-indexes; g holds only n and d
     int kind = LEANN_BACKEND_HNSW, device = 0;
     GraphView g{};
+    GraphStore store; // (a composite handle's stays empty: the sub-indexes own the device memory)
     uint64_t key_offset = 0;
-    bool owns_rows = true;
-    uint8_t *d_levels = nullptr;
     uint32_t efc = 64;
     float alpha = 1.2f;
     uint32_t fixed_ef = leann_knobs().hnsw_reference_ef ? 64u : 0u; // reference-exact mode, latched when the handle is made (HNSW only)
@@ -62,13 +72,14 @@ struct leann_backend {
     std::mutex mu;
     std::vector<std::unique_ptr<Workspace>> free_ws; // host-pointer API: one per concurrent caller
     // pooled HBM visited tables (search.cuh): shared by every stream, handed out by in-kernel locks
-    unsigned long long *gpool = nullptr, *gpool2 = nullptr;
-    uint32_t *gpool_lock = nullptr, *gpool_ctr = nullptr, *gpool2_lock = nullptr;
+    DeviceBuf<unsigned long long> gpool, gpool2;
+    DeviceBuf<uint32_t> gpool_lock, gpool2_lock;
+    uint32_t *gpool_ctr = nullptr; // inside gpool_lock
     uint32_t gpool_bits = GPOOL_BITS, gpool_tables = GPOOL_TABLES, gpool2_bits = 0, gpool2_tables = 0;
     leann_search_stats stats{};
     // recompute-on graph mode (g.feat_h != 0): encoder weights as f32 [feat_h x dims] for the query projection and
     // per-stream scratch for the projected queries
-    float *Wf32 = nullptr;
+    DeviceBuf<float> Wf32;
     std::map<hipStream_t, DeviceBuf<float>> proj_scratch;
     std::shared_ptr<Coalescer> coalescer; // optional request coalescing for single-query callers (api.hip); swapped under `mu`
     // 0 = automatic (default): a leann_backend_search caller that finds another one in flight goes through a dispatcher created on the
@@ -81,7 +92,7 @@ struct leann_backend {
     // list still names (0 after leann_backend_consolidate: unfiltered walks then run the plain kernel again).  removal_epoch counts
     // the leann_backend_remove calls that removed something; a registered filter remembers the epoch it was made in.
     std::vector<uint8_t> removed;
-    uint8_t *d_live = nullptr;
+    DeviceBuf<uint8_t> d_live;
     size_t n_removed = 0, n_pending = 0;
     uint64_t removal_epoch = 0;
     uint32_t two_stage = 1; // Vamana: the RobustPrune form the build used (LEANN_VAMANA_TWO_STAGE when the handle was made)
@@ -90,11 +101,11 @@ struct leann_backend {
     // handle whoever owns X; planes_src / planes_n / planes_ld name the rows they were cut from.  screen_ctr: device totals
     // {rows ruled out, rows read in full}.  row_screen: 0 off, 1 automatic, 2 on whatever the size (LeannKnobs::row_screen when the
     // handle is made; leann_backend_set_row_screen switches between 0 and 2).
-    uint16_t *x_hi = nullptr, *x_lo = nullptr;
+    DeviceBuf<uint16_t> x_hi, x_lo;
     uint32_t ldp = 0, planes_ld = 0;
     const float *planes_src = nullptr;
     uint64_t planes_n = 0;
-    unsigned long long *screen_ctr = nullptr;
+    DeviceBuf<unsigned long long> screen_ctr;
     std::atomic<int> row_screen{leann_knobs().row_screen};
     // Row type (rows_bf16.hip): LEANN_ROWS_F32, or LEANN_ROWS_BF16 — then g.X names the handle's own bf16 store, [n x g.row_bytes / 2]
     // u16 in rs_plane_pos order (g.row_bytes: a multiple of 128, zero padded), g.feat_h stays 0, no f32 rows exist and no planes are
@@ -140,14 +151,13 @@ int launch_plan(SearchKernel kernel, const SearchPlan &p, const GraphView &g, co
 bool leann_internal_screen_shape(const GraphView &g);      // the row widths and list lengths the screen kernel is compiled for
 void leann_internal_sync_planes(leann_backend *h);          // (re)build the planes of a plain handle; logs and returns on failure
 bool leann_internal_planes_ready(const leann_backend *h);   // planes present and cut from the rows h->g names now
-void leann_internal_free_planes(leann_backend *h);
+void leann_internal_free_planes(leann_backend *h);           // logs what the screen did, then drops the planes
 // Removals (consolidate.hip).  leann_internal_live_allow: the bitmap a search on `h` has to run under — the caller's (may be null)
 // ANDed with the live mask into the stream's scratch; *out = d_allow unchanged for a handle without removals.  `walk`: the search is
 // the graph walk, which needs no mask of its own once no live list names a removed position.  One caller: leann_internal_search_plain.
 int leann_internal_live_allow(leann_backend *h, const uint8_t *d_allow, size_t allow_stride, size_t nq, bool walk, hipStream_t st,
                               const uint8_t **out, size_t *out_stride);
 int leann_internal_set_removed(leann_backend *h, const uint8_t *bitmap, size_t n_removed); // adopt a bitmap (open): device mask + n_pending
-void leann_internal_free_removed(leann_backend *h);
 std::string leann_internal_tombstone_file(const std::string &index_file);
 int leann_internal_tombstones_save(const leann_backend *h, const std::string &index_file); // writes the sidecar, or removes a stale one
 int leann_internal_tombstones_load(leann_backend *h, const std::string &index_file);
@@ -170,6 +180,9 @@ int leann_internal_parse_device(const char *spec, int *device);
 int leann_internal_check_device(int device); // api.hip: LEANN_ERR_DEVICE and the "no CPU fallback" message unless `device` is a visible one
 // sharded handles (shard.hip)
 bool leann_internal_spec_is_sharded(const char *spec);
+int leann_internal_sharded_primary(const leann_sharded *s);
+// indexfile.hip: open one file of this library's own format on `device`; *why says what was wrong with a file that is not one
+int leann_internal_load_own_file(const std::string &path, int backend, size_t dims, int device, leann_backend **out, std::string *why);
 int leann_internal_open_sharded_backend(const char *stem, int backend, size_t dims, const char *spec, leann_backend **out);
 size_t leann_internal_sharded_count(const leann_sharded *s);
 leann_backend *leann_internal_sharded_shard(const leann_sharded *s, size_t g);
@@ -179,7 +192,7 @@ struct leann_filter {
     int device = 0;
     size_t n = 0, n_allowed = 0;
     DeviceBuf<uint8_t> d_allow;
-    uint32_t *d_list = nullptr; // scratch-pool block (scan.hip), held for the filter's lifetime
+    ScratchLease<uint32_t> d_list; // held for the filter's lifetime
     uint64_t epoch = 0;         // the handle's removal_epoch when the filter was made (its bitmap holds live positions only)
     std::vector<leann_filter *> parts;
 };
@@ -216,10 +229,25 @@ int leann_internal_filtered_exact_list(const float *d_rows, size_t dims, size_t 
 int leann_internal_filtered_exact(const float *d_rows, size_t n, size_t dims, size_t ld, const float *d_queries, size_t nq, size_t top_k,
                                   const uint8_t *d_allow, size_t allow_stride, uint64_t key_offset, uint64_t *d_keys, float *d_dists,
                                   uint32_t *d_counts, hipStream_t st);
-int leann_internal_compact_allow(const uint8_t *d_allow, size_t n, uint32_t **d_list, size_t *n_list, hipStream_t st);
+// scan.hip: bitmap over n positions -> *list, the allowed positions ascending (left empty when there are none), *n_list; synchronises
+// the stream once for the count.  The lease ends only once the stream that read the list is synchronised.
+int leann_internal_compact_allow(const uint8_t *d_allow, size_t n, ScratchLease<uint32_t> *list, size_t *n_list, hipStream_t st);
 int leann_internal_and_live_inplace(const leann_backend *h, uint8_t *d_bitmap);
-int leann_internal_scratch_acquire(void **out, size_t bytes); // scan.hip's pool: blocks are kept for reuse, released after a stream sync
-void leann_internal_scratch_release(void *p);
+// scan.hip internals reused per chunk by recompute.hip, bm25.hip and shard.hip
+int leann_internal_topk_chunk(const float *S, size_t rows, size_t nq, uint32_t k, const uint8_t *allow, uint64_t pos0, uint64_t *cand,
+                              size_t cand_len, size_t seg_off, hipStream_t st, size_t *segs_out, uint64_t *best);
+int leann_internal_scan_chunk(const float *d_rows, size_t rows, size_t dims, size_t ld, const float *d_queries, size_t nq, uint32_t k,
+                              const uint8_t *allow, uint64_t pos0, float *S, uint64_t *cand, size_t cand_len, size_t seg_off,
+                              hipStream_t st, size_t *segs_out, hipEvent_t mid = nullptr, uint64_t *best = nullptr,
+                              const uint32_t *idx = nullptr);
+int leann_internal_scan_finish(uint64_t *candA, uint64_t *candB, size_t cand_len, size_t total_segs, size_t nq, uint32_t k,
+                               uint64_t key_offset, uint64_t *d_keys, float *d_scores, uint32_t *d_counts, hipStream_t st);
+int leann_internal_scan_finish_ex(uint64_t *candA, uint64_t *candB, size_t cand_len, size_t total_segs, size_t nq, uint32_t k,
+                                  uint64_t key_offset, uint64_t *d_keys, float *d_scores, uint32_t *d_counts, hipStream_t st,
+                                  const uint32_t *idx, int as_dist);
+int leann_internal_merge_strided(const void *keys, const void *dists, const void *counts, size_t kstride, size_t dstride, size_t cstride,
+                                 size_t n_shards, size_t nq, size_t k_in, size_t k_out, int descending, uint64_t *d_out_keys,
+                                 float *d_out_dists, uint32_t *d_out_counts, hipStream_t st);
 extern "C" void leann_sharded_close(leann_sharded *s);
 
 int leann_internal_launch_search(leann_backend *h, SearchArgs a, hipStream_t st);
@@ -241,7 +269,6 @@ int leann_internal_fold_candidates(const CandEmit &em, uint32_t k, uint32_t nq, 
                                    hipStream_t st);
 int leann_internal_score(const float *X, size_t rows, size_t dims, size_t ld, const float *d_queries, size_t nq, size_t ldq, float *S,
                          hipStream_t st);
-void leann_internal_free_graph(leann_backend *h);
 size_t leann_internal_feat_file_row_bytes(const GraphView &g);
 int leann_internal_feat_rows_to_host(const leann_backend *h, size_t r0, size_t rows, unsigned char *out);
 std::string leann_internal_index_file(const char *stem, int backend);

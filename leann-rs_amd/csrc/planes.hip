@@ -58,11 +58,7 @@ void leann_internal_free_planes(leann_backend *h) {
                       100.0 * (double)c[0] / (double)(c[0] + c[1]));
         else (void)hipGetLastError();
     }
-    (void)hipFree(h->x_hi);
-    (void)hipFree(h->x_lo);
-    (void)hipFree(h->screen_ctr);
-    h->x_hi = h->x_lo = nullptr;
-    h->screen_ctr = nullptr;
+    h->x_hi.reset(); h->x_lo.reset(); h->screen_ctr.reset();
     h->planes_src = nullptr;
     h->planes_n = 0;
 }
@@ -93,18 +89,17 @@ void leann_internal_sync_planes(leann_backend *h) {
     if (!dev.ok) return;
     const uint32_t ldp = (h->g.ld + 63u) & ~63u;
     const size_t bytes = (size_t)h->g.n * ldp * 2;
-    if (hipMalloc((void **)&h->x_hi, bytes) != hipSuccess || hipMalloc((void **)&h->x_lo, bytes) != hipSuccess ||
-        hipMalloc((void **)&h->screen_ctr, 16) != hipSuccess || hipMemset(h->screen_ctr, 0, 16) != hipSuccess) {
-        leann_log(LEANN_LOG_WARN, "row screen: no room for the split planes (2 x %zu bytes: %s); searching whole rows", bytes,
-                  hipGetErrorString(hipGetLastError()));
+    if (h->x_hi.alloc(bytes / 2) || h->x_lo.alloc(bytes / 2) || h->screen_ctr.alloc(2)) {
+        leann_log(LEANN_LOG_WARN, "row screen: no room for the split planes (2 x %zu bytes: %s); searching whole rows", bytes, leann_last_error());
         leann_internal_free_planes(h);
         return;
     }
     const uint64_t items = h->g.n * (uint64_t)(ldp >> 2);
     const unsigned grid = (unsigned)std::min<uint64_t>((items + 255) / 256, 1u << 20);
+    const hipError_t zeroed = hipMemset(h->screen_ctr, 0, 16);
     hipLaunchKernelGGL(split_planes_kernel, dim3(grid), dim3(256), 0, nullptr, h->g.X, h->g.n, h->g.ld, ldp, h->x_hi, h->x_lo);
     // null-stream work; searches run on non-blocking streams that do not wait for it
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    if (zeroed != hipSuccess || hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
         leann_log(LEANN_LOG_WARN, "row screen: splitting the rows failed (%s); searching whole rows", hipGetErrorString(hipGetLastError()));
         leann_internal_free_planes(h);
         return;

@@ -476,9 +476,6 @@ extern "C" int leann_recompute_search_batch(const leann_recompute *r, const floa
     }
     return rc;
 }
-int leann_internal_merge_strided(const void *keys, const void *dists, const void *counts, size_t kstride, size_t dstride, size_t cstride,
-                                 size_t n_shards, size_t nq, size_t k_in, size_t k_out, int descending, uint64_t *d_out_keys,
-                                 float *d_out_dists, uint32_t *d_out_counts, hipStream_t st);
 
 // ---- sharded recompute search -------------------------------------------------------------------
 // RecomputeSearcher::search scores EVERY passage (recompute.rs:86-103); the top-k of a union is the top-k of the per-part top-ks, so the
@@ -604,20 +601,12 @@ extern "C" int leann_recompute_encode_device(const leann_recompute *r, uint64_t 
     return launch_encode(r, row0, rows, d_out, (hipStream_t)stream);
 }
 
-// scan.hip internals reused per chunk
-int leann_internal_topk_chunk(const float *S, size_t rows, size_t nq, uint32_t k, const uint8_t *allow, uint64_t pos0, uint64_t *cand,
-                              size_t cand_len, size_t seg_off, hipStream_t st, size_t *segs_out, uint64_t *best);
-int leann_internal_scan_finish(uint64_t *candA, uint64_t *candB, size_t cand_len, size_t total_segs, size_t nq, uint32_t k,
-                               uint64_t key_offset, uint64_t *d_keys, float *d_scores, uint32_t *d_counts, hipStream_t st);
-
 // RecomputeSearcher::search arithmetic for a batch of queries — recompute.rs:86-109 on the GPU.
 // Per tile of <= 64 queries: G = W Q^T once, then per chunk of passages ONE fused kernel (encode GEMM,
 // row norms, feature-space scoring) + segment top-k; the embeddings are never written anywhere.
 static int recompute_search_impl(const leann_recompute *r, const float *d_queries, size_t nq, size_t top_k, const uint8_t *d_allow_mask,
                                  uint64_t *d_keys, float *d_scores, uint32_t *d_counts, void *stream, bool emit_ok, bool *overflowed,
                                  const uint32_t *idx = nullptr, size_t n_list = 0);
-int leann_internal_scan_finish_ex(uint64_t *candA, uint64_t *candB, size_t cand_len, size_t total_segs, size_t nq, uint32_t k, uint64_t key_offset,
-                                  uint64_t *d_keys, float *d_scores, uint32_t *d_counts, hipStream_t st, const uint32_t *idx, int as_dist);
 extern "C" int leann_recompute_search_batch_device(const leann_recompute *r, const float *d_queries, size_t nq, size_t top_k,
                                                    const uint8_t *d_allow_mask, uint64_t *d_keys, float *d_scores,
                                                    uint32_t *d_counts, void *stream) {
@@ -632,16 +621,15 @@ extern "C" int leann_recompute_search_batch_device(const leann_recompute *r, con
     // The early filter of recompute.rs:62-79: the reference fetches, and therefore embeds, only the passages that pass the filter.
     // A selective mask is compacted into the list of allowed positions and only those rows go through the fused kernel (same
     // per-passage arithmetic, so the same scores as the masked pass over everything); LEANN_RECOMPUTE_NO_LIST=1 keeps the masked pass.
-    uint32_t *list = nullptr;
+    ScratchLease<uint32_t> list;
     size_t n_list = 0;
     if (d_allow_mask && use_fstat(r) && r->n < (1ull << 32) && !leann_knobs().no_list) {
         int rc = leann_internal_compact_allow(d_allow_mask, r->n, &list, &n_list, (hipStream_t)stream);
         if (rc != LEANN_OK) return rc;
         if (n_list > r->n / 2) { // barely selective: the masked pass reads the fragment-major feature copy and skips the gather
-            leann_internal_scratch_release(list); // (compact_allow synchronised the stream)
-            list = nullptr;
+            list.reset(); // (compact_allow synchronised the stream)
         } else if (!list) { // nothing allowed: an empty list still needs a non-null marker for the list path
-            if (int e = leann_internal_scratch_acquire((void **)&list, 4)) return e;
+            if (int e = list.acquire(1)) return e;
         }
     }
     bool overflowed = false;
@@ -649,10 +637,7 @@ extern "C" int leann_recompute_search_batch_device(const leann_recompute *r, con
     // a candidate list overflowed (adversarial score order, e.g. ascending): repeat on the score-slab path
     if (rc == LEANN_OK && overflowed)
         rc = recompute_search_impl(r, d_queries, nq, top_k, d_allow_mask, d_keys, d_scores, d_counts, stream, false, &overflowed, list, n_list);
-    if (list) {
-        (void)hipStreamSynchronize((hipStream_t)stream); // (already idle unless an error cut the search short)
-        leann_internal_scratch_release(list);
-    }
+    if (list) (void)hipStreamSynchronize((hipStream_t)stream); // before the lease ends (already idle unless an error cut the search short)
     return rc;
 }
 static int recompute_search_impl(const leann_recompute *r, const float *d_queries, size_t nq, size_t top_k, const uint8_t *d_allow_mask,
@@ -864,15 +849,15 @@ extern "C" int leann_recompute_build_index(const leann_recompute *r, int backend
     if (total)
         hipLaunchKernelGGL(pack_feature_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, r->F, norms.p, (uint64_t)n,
                            (uint32_t)r->h, hp4, row_bytes, rows_b.p);
-    HIP_CHECK_RET(hipMalloc((void **)&h->Wf32, (size_t)hp4 * r->d * 4));
+    if (int e = h->Wf32.alloc((size_t)hp4 * r->d)) return e;
     HIP_CHECK_RET(hipMemset(h->Wf32, 0, (size_t)hp4 * r->d * 4));
-    hipLaunchKernelGGL(bf16_to_f32_kernel, dim3((unsigned)((r->h * r->d + 255) / 256)), dim3(256), 0, nullptr, r->Wraw, r->h * r->d, h->Wf32);
+    hipLaunchKernelGGL(bf16_to_f32_kernel, dim3((unsigned)((r->h * r->d + 255) / 256)), dim3(256), 0, nullptr, r->Wraw, r->h * r->d, h->Wf32.p);
     HIP_CHECK_RET(hipGetLastError());
     HIP_CHECK_RET(hipDeviceSynchronize());
     E.reset();
-    if (split) h->g.norms = norms.release(); // (freed with the graph)
-    h->g.X = reinterpret_cast<const float *>(rows_b.release()); // now belongs to the handle
-    h->owns_rows = true;
+    if (split) h->g.norms = h->store.norms = std::move(norms);
+    h->g.X = reinterpret_cast<const float *>(rows_b.p);
+    h->store.rows = std::move(rows_b); // (the handle borrowed E until here)
     h->g.feat_h = hp4;
     h->g.row_bytes = row_bytes;
     *out = h.release();

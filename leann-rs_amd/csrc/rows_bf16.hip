@@ -60,15 +60,10 @@ static int launch_round(const float *d_src, size_t n, uint32_t d, size_t ld, uin
 static int alloc_store(leann_backend *h) {
     const uint32_t ldb = store_ld(h->g.d);
     const size_t bytes = std::max<size_t>((size_t)h->g.n * ldb * 2, 128);
-    void *p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) {
-        leann_set_error("bf16 rows: hipMalloc(%zu) for the row store failed: %s", bytes, hipGetErrorString(hipGetLastError()));
-        return LEANN_ERR_DEVICE;
-    }
-    h->g.X = reinterpret_cast<const float *>(p);
+    if (int rc = h->store.rows.alloc(bytes)) return rc; // (empty until here: the handle is new, or borrowed the f32 rows it was built on)
+    h->g.X = reinterpret_cast<const float *>(h->store.rows.p);
     h->g.row_bytes = ldb * 2;
     h->g.feat_h = 0;
-    h->owns_rows = true;
     h->row_type = LEANN_ROWS_BF16;
     return LEANN_OK;
 }

@@ -55,6 +55,7 @@ int leann_internal_scratch_acquire(void **out, size_t bytes) {
             g_scratch_free_bytes -= b.cap;
             g_scratch_out[b.p] = b;
             *out = b.p;
+            leann_internal_device_blocks++;
             return LEANN_OK;
         }
     }
@@ -78,11 +79,13 @@ int leann_internal_scratch_acquire(void **out, size_t bytes) {
     std::lock_guard<std::mutex> lk(g_scratch_mu);
     g_scratch_out[p] = PoolBlock{p, bytes, dev};
     *out = p;
+    leann_internal_device_blocks++;
     return LEANN_OK;
 }
-// the caller has synchronised every stream that touched the block
+// the lease's holder has synchronised every stream that touched the block
 void leann_internal_scratch_release(void *p) {
     if (!p) return;
+    leann_internal_device_blocks--;
     PoolBlock b{p, 0, 0};
     bool keep = false;
     {
@@ -409,8 +412,7 @@ __global__ void update_best_kernel(const uint64_t *__restrict__ cand, uint32_t c
 // one chunk: scores of rows [0, rows) of Xbase against all queries, per-segment top-k appended to cand
 int leann_internal_scan_chunk(const float *Xbase, size_t rows, size_t dims, size_t ld, const float *d_queries, size_t nq, uint32_t k,
                               const uint8_t *allow, uint64_t pos0, float *S, uint64_t *cand, size_t cand_len, size_t seg_off,
-                              hipStream_t st, size_t *segs_out, hipEvent_t mid = nullptr, uint64_t *best = nullptr,
-                              const uint32_t *idx = nullptr) {
+                              hipStream_t st, size_t *segs_out, hipEvent_t mid, uint64_t *best, const uint32_t *idx) {
     launch_score(st, Xbase, rows, dims, ld, d_queries, nq, dims, S, CandEmit{}, idx);
     if (mid) (void)hipEventRecord(mid, st);
     unsigned segs = (unsigned)((rows + SEG - 1) / SEG);
@@ -457,8 +459,6 @@ int leann_internal_topk_chunk(const float *S, size_t rows, size_t nq, uint32_t k
     return LEANN_OK;
 }
 // reduction rounds until one segment per query remains, then keys -> (position + key_offset, score)
-int leann_internal_scan_finish_ex(uint64_t *candA, uint64_t *candB, size_t cand_len, size_t total_segs, size_t nq, uint32_t k, uint64_t key_offset,
-                          uint64_t *d_keys, float *d_scores, uint32_t *d_counts, hipStream_t st, const uint32_t *idx, int as_dist);
 int leann_internal_scan_finish(uint64_t *candA, uint64_t *candB, size_t cand_len, size_t total_segs, size_t nq, uint32_t k,
                                uint64_t key_offset, uint64_t *d_keys, float *d_scores, uint32_t *d_counts, hipStream_t st) {
     return leann_internal_scan_finish_ex(candA, candB, cand_len, total_segs, nq, k, key_offset, d_keys, d_scores, d_counts, st, nullptr, 0);
@@ -527,30 +527,27 @@ static int scan_topk_impl(const float *d_rows, size_t n, size_t dims, size_t ld,
         const size_t cand_len = std::max<size_t>(total_segs * k, k); // per query
         const size_t slots = (nq + 63) / 64 * 64;                     // score_mfma_kernel reads a threshold for every query of a tile
         const uint32_t EMIT_CAP = std::max<uint32_t>(8192, 32 * k); // expected survivors per query ~ k * rows / rows_seen (x19 after 512k of 10M rows)
-        float *S = nullptr;
-        uint64_t *candA = nullptr, *candB = nullptr, *best = nullptr;
-        unsigned char *emb = nullptr; // [slots f32 thr | slots u32 cnt | u32 overflow | pad | slots x EMIT_CAP u64]
+        // every return, early ones included (a failed allocation, a launch error), gives the pass's scratch back
+        ScratchLease<float> S;
+        ScratchLease<uint64_t> candA, candB, best;
+        ScratchLease<unsigned char> emb; // [slots f32 thr | slots u32 cnt | u32 overflow | pad | slots x EMIT_CAP u64]
         const size_t em_hdr = (slots * 8 + 4 + 255) / 256 * 256;
-        struct Scratch { // every early return (a failed allocation, a launch error) gives the pass's scratch back
-            void **p[5];
+        struct SyncFirst { // (declared after the leases, so it runs before them) nothing may still be running on a block that goes back
             hipStream_t st;
-            ~Scratch() {
-                (void)hipStreamSynchronize(st); // nothing may still be running on a block when it goes back to the pool
-                for (void **q : p) { leann_internal_scratch_release(*q); *q = nullptr; }
-            }
-        } scratch{{(void **)&S, (void **)&candA, (void **)&candB, (void **)&best, (void **)&emb}, st};
-        if (int e = leann_internal_scratch_acquire((void **)&S, sizeof(float) * nq * slab_rows)) return e;
-        if (int e = leann_internal_scratch_acquire((void **)&candA, sizeof(uint64_t) * nq * cand_len)) return e;
-        if (int e = leann_internal_scratch_acquire((void **)&candB, sizeof(uint64_t) * nq * cand_len)) return e;
-        if (int e = leann_internal_scratch_acquire((void **)&best, sizeof(uint64_t) * nq * k)) return e;
+            ~SyncFirst() { (void)hipStreamSynchronize(st); }
+        } sync_first{st};
+        if (int e = S.acquire(nq * slab_rows)) return e;
+        if (int e = candA.acquire(nq * cand_len)) return e;
+        if (int e = candB.acquire(nq * cand_len)) return e;
+        if (int e = best.acquire(nq * k)) return e;
         HIP_CHECK_RET(hipMemsetAsync(candA, 0xFF, sizeof(uint64_t) * nq * cand_len, st));
         HIP_CHECK_RET(hipMemsetAsync(best, 0xFF, sizeof(uint64_t) * nq * k, st));
         CandEmit em{};
         uint32_t *d_overflow = nullptr;
         if (emit) {
-            if (int e = leann_internal_scratch_acquire((void **)&emb, em_hdr + sizeof(uint64_t) * slots * EMIT_CAP)) return e;
+            if (int e = emb.acquire(em_hdr + sizeof(uint64_t) * slots * EMIT_CAP)) return e;
             HIP_CHECK_RET(hipMemsetAsync(emb, 0, em_hdr, st));
-            em.thr = reinterpret_cast<const float *>(emb);
+            em.thr = reinterpret_cast<const float *>(emb.p);
             em.cnt = reinterpret_cast<uint32_t *>(emb + slots * 4);
             d_overflow = reinterpret_cast<uint32_t *>(emb + slots * 8);
             em.list = reinterpret_cast<uint64_t *>(emb + em_hdr);
@@ -567,7 +564,7 @@ static int scan_topk_impl(const float *d_rows, size_t n, size_t dims, size_t ld,
                 launch_score(st, idx ? d_rows : d_rows + row0 * ld, rows, dims, ld, d_queries, nq, dims, S, em, idx ? idx + row0 : nullptr);
             } else {
                 rc = leann_internal_scan_chunk(idx ? d_rows : d_rows + row0 * ld, rows, dims, ld, d_queries, nq, k, d_allow_mask, row0, S, candA,
-                                               cand_len, seg_off, st, &segs, nullptr, (n_chunks > 1 || emit) ? best : nullptr,
+                                               cand_len, seg_off, st, &segs, nullptr, (n_chunks > 1 || emit) ? best.p : nullptr,
                                                idx ? idx + row0 : nullptr);
             }
             if (rc == LEANN_OK && emit) rc = leann_internal_fold_candidates(em, k, (uint32_t)nq, (uint32_t)slots, best, d_overflow, st);
@@ -582,7 +579,7 @@ static int scan_topk_impl(const float *d_rows, size_t n, size_t dims, size_t ld,
         (void)hipStreamSynchronize(st);
         uint32_t ov = 0;
         if (emit && rc == LEANN_OK && hipMemcpy(&ov, d_overflow, 4, hipMemcpyDeviceToHost) != hipSuccess) rc = LEANN_ERR_DEVICE;
-        if (rc != LEANN_OK || !emit || ov == 0) return rc; // (~Scratch frees)
+        if (rc != LEANN_OK || !emit || ov == 0) return rc;
     }
     return LEANN_OK;
 }
@@ -655,29 +652,26 @@ __global__ void __launch_bounds__(256) allow_scatter_kernel(const uint8_t *__res
         v &= v - 1;
     }
 }
-// bitmap over n positions -> *d_list (from the scratch pool: give it back with leann_internal_scratch_release once the stream that used
-// it is synchronised), ascending positions, *n_list; synchronises the stream once for the count
-int leann_internal_compact_allow(const uint8_t *d_allow, size_t n, uint32_t **d_list, size_t *n_list, hipStream_t st) {
+int leann_internal_compact_allow(const uint8_t *d_allow, size_t n, ScratchLease<uint32_t> *list, size_t *n_list, hipStream_t st) {
     const uint32_t nb = (uint32_t)((n + 8191) / 8192);
-    uint32_t *blk = nullptr, total = 0;
-    *d_list = nullptr;
+    ScratchLease<uint32_t> blk;
+    uint32_t total = 0;
+    list->reset();
     *n_list = 0;
-    if (int e0 = leann_internal_scratch_acquire((void **)&blk, sizeof(uint32_t) * ((size_t)nb + 1))) return e0;
+    if (int e0 = blk.acquire((size_t)nb + 1)) return e0;
     hipLaunchKernelGGL(allow_count_kernel, dim3(nb), dim3(256), 0, st, d_allow, (uint64_t)n, blk);
     hipLaunchKernelGGL(allow_offsets_kernel, dim3(1), dim3(1024), 0, st, blk, nb);
     hipError_t e = hipMemcpyAsync(&total, blk + nb, 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess && total && leann_internal_scratch_acquire((void **)d_list, sizeof(uint32_t) * (size_t)total) != LEANN_OK) e = hipErrorOutOfMemory;
+    if (e == hipSuccess && total && list->acquire(total) != LEANN_OK) e = hipErrorOutOfMemory;
     if (e == hipSuccess && total) {
-        hipLaunchKernelGGL(allow_scatter_kernel, dim3(nb), dim3(256), 0, st, d_allow, (uint64_t)n, blk, *d_list);
+        hipLaunchKernelGGL(allow_scatter_kernel, dim3(nb), dim3(256), 0, st, d_allow, (uint64_t)n, blk.p, list->p);
         e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(st); // blk goes back to the pool below
+        if (e == hipSuccess) e = hipStreamSynchronize(st); // blk goes back to the pool on return
     }
-    if (e != hipSuccess) (void)hipStreamSynchronize(st);
-    leann_internal_scratch_release(blk);
     if (e != hipSuccess) {
-        leann_internal_scratch_release(*d_list);
-        *d_list = nullptr;
+        (void)hipStreamSynchronize(st);
+        list->reset();
         leann_set_error("HIP error: %s (compact_allow)", hipGetErrorString(e));
         return LEANN_ERR_DEVICE;
     }
@@ -716,7 +710,7 @@ int leann_internal_filtered_exact(const float *d_rows, size_t n, size_t dims, si
     }
     const size_t groups = allow_stride ? nq : 1, per = allow_stride ? 1 : nq;
     for (size_t g = 0; g < groups; g++) {
-        uint32_t *list = nullptr;
+        ScratchLease<uint32_t> list; // ends with the iteration: every path below leaves the stream synchronised or unused
         size_t m = 0;
         int rc = leann_internal_compact_allow(d_allow + g * allow_stride, n, &list, &m, st);
         if (rc != LEANN_OK) return rc;
@@ -731,7 +725,6 @@ int leann_internal_filtered_exact(const float *d_rows, size_t n, size_t dims, si
         }
         rc = scan_topk_impl(d_rows, m, dims, ld, d_queries + g * per * dims, per, top_k, nullptr, key_offset, ok, od, oc, st, list, 1);
         (void)hipStreamSynchronize(st);
-        leann_internal_scratch_release(list);
         if (rc != LEANN_OK) return rc;
     }
     return LEANN_OK;

@@ -27,11 +27,6 @@
 #include <thread>
 #include <vector>
 
-int leann_internal_merge_strided(const void *keys, const void *dists, const void *counts, size_t kstride, size_t dstride, size_t cstride,
-                                 size_t n_shards, size_t nq, size_t k_in, size_t k_out, int descending, uint64_t *d_out_keys,
-                                 float *d_out_dists, uint32_t *d_out_counts, hipStream_t st);
-int leann_internal_load_own_file(const std::string &path, int backend, size_t dims, int device, leann_backend **out, std::string *why);
-
 // ---- RCCL, resolved at run time (the library has no link-time dependency on it; one-process handles never load it) ---------------
 namespace {
 typedef struct { char internal[128]; } rcclUniqueId; // NCCL_UNIQUE_ID_BYTES
@@ -367,8 +362,7 @@ static int open_one_shard(const std::string &src, uint64_t src_off, const std::s
     if (const char *e = getenv("LEANN_REBUILD_COMPLEXITY")) complexity = (size_t)atoi(e);
     int rc = leann_backend_build_device(backend, dX, rows, dims, ld, degree, complexity, device, lo, 0, out);
     if (rc) return rc;
-    (*out)->owns_rows = true; // dX now belongs to the handle
-    (void)dX.release();
+    (*out)->store.rows = DeviceBuf<unsigned char>(std::move(dX)); // the handle borrowed dX until here
     if (leann_internal_save_to(*out, cache) != LEANN_OK)
         leann_log(LEANN_LOG_WARN, "could not cache shard graph %s (%s)", cache.c_str(), leann_last_error());
     return LEANN_OK;
@@ -439,7 +433,6 @@ int leann_internal_open_sharded_backend(const char *stem, int backend, size_t di
     h->g.n = s->total_rows;
     h->g.d = (uint32_t)dims;
     h->g.ld = (uint32_t)((dims + 3) & ~(size_t)3);
-    h->owns_rows = false;
     h->sharded = s;
     *out = h;
     return LEANN_OK;
@@ -452,7 +445,6 @@ extern "C" int leann_sharded_as_backend(leann_sharded *s, leann_backend **out) {
     h->g.n = s->total_rows;
     h->g.d = (uint32_t)s->dims;
     h->g.ld = (uint32_t)((s->dims + 3) & ~(size_t)3);
-    h->owns_rows = false;
     h->sharded = s;
     *out = h;
     return LEANN_OK;

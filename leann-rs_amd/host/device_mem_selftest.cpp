@@ -1,6 +1,6 @@
-// device_mem_selftest — the owning buffer type of the host side (csrc/device_mem.h) on the CPU, under AddressSanitizer + UBSan: no
-// GPU, no library.  The two allocation functions the header declares are defined HERE, over malloc / free with counters and a "fail
-// the next N allocations" switch; that link-time seam is the whole hook.  A double free, a leak or a use after free is the
+// device_mem_selftest — the owning buffer type and the scratch-pool lease of the host side (csrc/device_mem.h) on the CPU, under
+// AddressSanitizer + UBSan: no GPU, no library.  The four functions the header declares (allocation, scratch pool) are defined HERE,
+// over malloc / free with counters and a "fail the next N allocations" switch; that link-time seam is the whole hook.  A double free, a leak or a use after free is the
 // sanitizer's to report; the counters check what was asked for and in which order.
 #include "../csrc/device_mem.h"
 
@@ -35,6 +35,23 @@ void leann_internal_device_release(void *p) {
     if (!p) return;
     g_live--;
     g_frees++;
+    free(p);
+}
+static long g_leased = 0, g_acquires = 0, g_returns = 0; // the "pool": every block is a malloc, handed out and taken back once
+static size_t g_last_lease_bytes = 0;
+int leann_internal_scratch_acquire(void **out, size_t bytes) {
+    *out = nullptr;
+    g_last_lease_bytes = bytes;
+    if (g_fail_next > 0) { g_fail_next--; leann_set_error("pool: %zu bytes failed", bytes); return LEANN_ERR_DEVICE; }
+    *out = malloc(bytes ? bytes : 1);
+    g_leased++;
+    g_acquires++;
+    return LEANN_OK;
+}
+void leann_internal_scratch_release(void *p) {
+    if (!p) return;
+    g_leased--;
+    g_returns++;
     free(p);
 }
 
@@ -134,8 +151,58 @@ int main() {
         CHECK(g_live == 0);
     }
 
+    { // converting move: the same block under another element type, the capacity rescaled, the source empty, freed once
+        DeviceBuf<float> f;
+        CHECK(f.alloc(10) == LEANN_OK);
+        void *p = f.p;
+        const long frees = g_frees;
+        DeviceBuf<unsigned char> bytes(std::move(f));
+        CHECK(f.p == nullptr && f.cap == 0 && bytes.p == p && bytes.cap == 40 && g_live == 1 && g_frees == frees);
+        bytes.p[39] = 1;
+        DeviceBuf<unsigned char> member; // ... and into a member that already exists (a handle adopting a local's rows)
+        DeviceBuf<float> g;
+        CHECK(g.alloc(3) == LEANN_OK && g_live == 2);
+        member = DeviceBuf<unsigned char>(std::move(g));
+        CHECK(g.p == nullptr && member.cap == 12 && g_live == 2);
+        DeviceBuf<unsigned short> halves(std::move(member)); // 12 bytes -> 6 elements
+        CHECK(member.p == nullptr && halves.cap == 6 && g_live == 2);
+    }
+    CHECK(g_live == 0 && g_allocs == g_frees);
+
+    { // lease: acquire asks the pool for count * sizeof(T) bytes; destruction gives the block back exactly once
+        ScratchLease<unsigned long long> a;
+        CHECK(a.p == nullptr);
+        CHECK(a.acquire(5) == LEANN_OK && a.p && g_last_lease_bytes == 40 && g_leased == 1);
+        a.p[4] = 1;
+        unsigned long long *q = a;
+        CHECK(q == a.p);
+    }
+    CHECK(g_leased == 0 && g_acquires == 1 && g_returns == 1);
+
+    { // lease moves: the source is empty; an assigned-to lease gives its own block back first; reset() twice returns once
+        ScratchLease<float> a, c;
+        CHECK(a.acquire(8) == LEANN_OK && c.acquire(2) == LEANN_OK && g_leased == 2);
+        float *p = a.p;
+        ScratchLease<float> b(std::move(a));
+        CHECK(a.p == nullptr && b.p == p && g_leased == 2);
+        c = std::move(b);
+        CHECK(b.p == nullptr && c.p == p && g_leased == 1);
+        const long returns = g_returns;
+        c.reset();
+        c.reset();
+        CHECK(c.p == nullptr && g_leased == 0 && g_returns == returns + 1);
+    }
+
+    { // a failed acquire leaves the lease empty and hands the pool's error code on; a later acquire succeeds
+        ScratchLease<float> a;
+        g_fail_next = 1;
+        CHECK(a.acquire(100) == LEANN_ERR_DEVICE && a.p == nullptr && g_leased == 0);
+        CHECK(a.acquire(1) == LEANN_OK && a.p && g_leased == 1);
+    }
+    CHECK(g_leased == 0 && g_acquires == g_returns);
+
     CHECK(g_live == 0 && g_allocs == g_frees);
     if (g_failed) { fprintf(stderr, "device_mem_selftest: %d check(s) FAILED\n", g_failed); return 1; }
-    printf("device_mem_selftest ok: %ld blocks allocated and freed\n", g_allocs);
+    printf("device_mem_selftest ok: %ld blocks allocated and freed, %ld leases taken and given back\n", g_allocs, g_acquires);
     return 0;
 }

@@ -137,6 +137,9 @@ def test_round3_entry_points_reject_bad_arguments_without_a_gpu(la):
     assert L.leann_recompute_create_sharded(None, 2, C.byref(out)) == 1 and not out.value
     assert L.leann_backend_shard_count(None) == 0
     assert L.leann_backend_shard(None, 0, C.byref(out)) == 1 and b"null" in L.leann_last_error()
+    blocks = L.leann_debug_device_blocks()  # the owned-block count needs no device either, and refused calls leave it alone
+    assert isinstance(blocks, int) and blocks >= 0
+    assert L.leann_backend_shard(None, 0, C.byref(out)) == 1 and L.leann_debug_device_blocks() == blocks
     os.environ["LEANN_HNSW_REFERENCE_EF"] = "1"
     try:
         L.leann_debug_reload_env()  # reads the environment again; no device needed
