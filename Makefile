@@ -12,7 +12,7 @@ HOST     := leann-rs_amd/host
 CXXFLAGS := -O2 -std=c++17 -ffp-contract=off -Wall -Wextra -Wno-unused-parameter
 
 all: $(CSRC)/libleann_hip.so oracle $(HOST)/leann $(HOST)/host_selftest $(HOST)/host_selftest_asan $(HOST)/serve_bench $(HOST)/row_screen_selftest \
-     $(HOST)/encode_plan_selftest $(HOST)/search_plan_selftest $(HOST)/device_mem_selftest
+     $(HOST)/encode_plan_selftest $(HOST)/search_plan_selftest $(HOST)/device_mem_selftest $(HOST)/topk_plan_selftest
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -59,12 +59,18 @@ $(HOST)/device_mem_selftest: $(HOST)/device_mem_selftest.cpp $(CSRC)/device_mem.
 	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -o $@ \
 	    $(HOST)/device_mem_selftest.cpp
 
+# how an exhaustive top-k cuts its rows into chunks and sizes its scratch (csrc/topk_plan.h) over a grid of shapes, on the CPU under
+# AddressSanitizer + UBSan: no GPU, no library
+$(HOST)/topk_plan_selftest: $(HOST)/topk_plan_selftest.cpp $(CSRC)/topk_plan.h
+	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -o $@ \
+	    $(HOST)/topk_plan_selftest.cpp
+
 oracle:
 	$(MAKE) -s -C oracle
 
 clean:
 	rm -f $(CSRC)/*.o $(CSRC)/*.so $(HOST)/leann $(HOST)/host_selftest $(HOST)/host_selftest_asan $(HOST)/serve_bench $(HOST)/row_screen_selftest \
-	      $(HOST)/encode_plan_selftest $(HOST)/search_plan_selftest $(HOST)/device_mem_selftest
+	      $(HOST)/encode_plan_selftest $(HOST)/search_plan_selftest $(HOST)/device_mem_selftest $(HOST)/topk_plan_selftest
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -389,7 +389,7 @@ static int bm25_select_by_segments(leann_bm25 *b, uint32_t nslots, uint32_t k, h
         return LEANN_ERR_DEVICE;
     size_t segs_out = 0;
     int rc = leann_internal_topk_chunk(b->d_acc, b->n_docs, nslots, k, nullptr, 0, candA, cand_len, 0, st, &segs_out, nullptr);
-    if (rc == LEANN_OK) rc = leann_internal_scan_finish(candA, candB, cand_len, segs_out, nslots, k, 0, keys, scores, counts, st);
+    if (rc == LEANN_OK) rc = leann_internal_scan_finish_ex(candA, candB, cand_len, segs_out, nslots, k, 0, keys, scores, counts, st, nullptr, 0);
     if (rc == LEANN_OK) {
         hipLaunchKernelGGL(bm25_rebuild_best_kernel, dim3(nslots), dim3(256), 0, st, keys.p, scores.p, k, b->d_best.p);
         if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {

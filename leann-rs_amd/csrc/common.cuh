@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "topk_plan.h" // SEG
 
 #define LEANN_EMPTY 0xFFFFFFFFu
 #define WAVE 64
@@ -127,7 +128,6 @@ __device__ __forceinline__ float4 vec_load4_guard(const float *__restrict__ v, u
 // ---------------------------------------------------------------------------------------------
 // Block-wide bitonic sort of n (power of two, <= SEG) u64 keys in LDS, ascending (scan.hip / recompute.hip top-k).
 // ---------------------------------------------------------------------------------------------
-#define SEG 2048
 __device__ __forceinline__ void bitonic_sort_lds(uint64_t *k, int n /* power of two */) {
     for (int size = 2; size <= n; size <<= 1) {
         for (int stride = size >> 1; stride > 0; stride >>= 1) {

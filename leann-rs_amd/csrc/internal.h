@@ -4,6 +4,7 @@
 #pragma once
 #include "search.cuh"
 #include "device_mem.h"
+#include "topk_plan.h"
 #include "../../include/leann_backend.h"
 #include <atomic>
 #include <map>
@@ -233,18 +234,13 @@ int leann_internal_filtered_exact(const float *d_rows, size_t n, size_t dims, si
 // the stream once for the count.  The lease ends only once the stream that read the list is synchronised.
 int leann_internal_compact_allow(const uint8_t *d_allow, size_t n, ScratchLease<uint32_t> *list, size_t *n_list, hipStream_t st);
 int leann_internal_and_live_inplace(const leann_backend *h, uint8_t *d_bitmap);
-// scan.hip internals reused per chunk by recompute.hip, bm25.hip and shard.hip
+// scan.hip: segment top-k of a score slab and the reduction of its winners (bm25.hip's segment fallback, and the select step below)
 int leann_internal_topk_chunk(const float *S, size_t rows, size_t nq, uint32_t k, const uint8_t *allow, uint64_t pos0, uint64_t *cand,
                               size_t cand_len, size_t seg_off, hipStream_t st, size_t *segs_out, uint64_t *best);
-int leann_internal_scan_chunk(const float *d_rows, size_t rows, size_t dims, size_t ld, const float *d_queries, size_t nq, uint32_t k,
-                              const uint8_t *allow, uint64_t pos0, float *S, uint64_t *cand, size_t cand_len, size_t seg_off,
-                              hipStream_t st, size_t *segs_out, hipEvent_t mid = nullptr, uint64_t *best = nullptr,
-                              const uint32_t *idx = nullptr);
-int leann_internal_scan_finish(uint64_t *candA, uint64_t *candB, size_t cand_len, size_t total_segs, size_t nq, uint32_t k,
-                               uint64_t key_offset, uint64_t *d_keys, float *d_scores, uint32_t *d_counts, hipStream_t st);
 int leann_internal_scan_finish_ex(uint64_t *candA, uint64_t *candB, size_t cand_len, size_t total_segs, size_t nq, uint32_t k,
                                   uint64_t key_offset, uint64_t *d_keys, float *d_scores, uint32_t *d_counts, hipStream_t st,
                                   const uint32_t *idx, int as_dist);
+// scan.hip: k-way merge of per-shard results (shard.hip, the sharded recompute search)
 int leann_internal_merge_strided(const void *keys, const void *dists, const void *counts, size_t kstride, size_t dstride, size_t cstride,
                                  size_t n_shards, size_t nq, size_t k_in, size_t k_out, int descending, uint64_t *d_out_keys,
                                  float *d_out_dists, uint32_t *d_out_counts, hipStream_t st);
@@ -267,6 +263,38 @@ struct CandEmit {
 };
 int leann_internal_fold_candidates(const CandEmit &em, uint32_t k, uint32_t nq, uint32_t slots, uint64_t *best, uint32_t *d_overflow,
                                    hipStream_t st);
+// The select step of an exhaustive top-k (scan.hip), shared by the exact scan and the recompute search.  The caller plans
+// (topk_plan.h), owns the scratch the plan sizes and scores each chunk itself; a search reads
+//     plan, acquire or grow, begin, per query tile and chunk { score with chunk_emit(c), select_chunk }, finish,
+// once more on the slab schedule (emit = false) if finish reports an overflowed candidate list.
+struct TopkRun {
+    TopkPlan plan;
+    float *S;                   // [q_tile x plan.slab_rows]
+    uint64_t *candA, *candB;    // [nq x plan.cand_len]
+    uint64_t *best;             // [nq x k]
+    unsigned char *emit_block;  // [plan.emit_bytes]; unused (null) unless plan.emit
+    size_t nq;
+    uint32_t k;
+    const uint8_t *allow;       // optional filter over positions
+    hipStream_t st;
+    hipEvent_t done;            // optional: recorded behind finish's last launch, before it waits (the recompute search's timing)
+    // set by begin
+    CandEmit em;
+    uint32_t *d_overflow;
+    size_t seg_off;
+    // what chunk c's scoring launch is given: the emission block for an emitted chunk, none (the kernel writes S) for a slab chunk
+    CandEmit chunk_emit(size_t c) const {
+        CandEmit e = plan.slab_chunk(c) ? CandEmit{} : em;
+        e.pos0 = plan.chunks[c].first;
+        return e;
+    }
+};
+int leann_internal_topk_begin(TopkRun &run);
+// chunk c of the queries [q0, q0 + nqt), scored: segment top-k and running best-k of a slab chunk, then the fold when emitting
+int leann_internal_topk_select_chunk(TopkRun &run, size_t c, size_t q0, uint32_t nqt);
+// the answer (from best under emission, else from all segment winners); waits for the stream; *overflowed: repeat with emit = false
+int leann_internal_topk_finish(TopkRun &run, uint64_t key_offset, const uint32_t *idx, int as_dist, uint64_t *d_keys, float *d_scores,
+                               uint32_t *d_counts, bool *overflowed);
 int leann_internal_score(const float *X, size_t rows, size_t dims, size_t ld, const float *d_queries, size_t nq, size_t ldq, float *S,
                          hipStream_t st);
 size_t leann_internal_feat_file_row_bytes(const GraphView &g);

@@ -269,7 +269,7 @@ struct leann_recompute {
     DeviceBuf<uint64_t> sCandA, sCandB, sBest;
     DeviceBuf<uint4> Ft;            // fragment-major copy of F (tile_features_kernel), made by the first exhaustive search
     DeviceBuf<uint16_t> ownF;       // leann_recompute_create_host: the handle's own copy of the features
-    DeviceBuf<unsigned char> sEmit; // [64 f32 thr | 64 u32 cnt | u32 overflow | pad | 64 x EMIT_CAP u64 list]
+    DeviceBuf<unsigned char> sEmit; // the emission block of topk_plan.h, FSTAT_MAX_QUERIES slots
     // sharded form (leann_recompute_create_sharded): the passages live in `parts` (consecutive position ranges, possibly on different
     // devices); this handle owns only the gather block and the per-part staging
     struct Part {
@@ -605,8 +605,8 @@ extern "C" int leann_recompute_encode_device(const leann_recompute *r, uint64_t 
 // Per tile of <= 64 queries: G = W Q^T once, then per chunk of passages ONE fused kernel (encode GEMM,
 // row norms, feature-space scoring) + segment top-k; the embeddings are never written anywhere.
 static int recompute_search_impl(const leann_recompute *r, const float *d_queries, size_t nq, size_t top_k, const uint8_t *d_allow_mask,
-                                 uint64_t *d_keys, float *d_scores, uint32_t *d_counts, void *stream, bool emit_ok, bool *overflowed,
-                                 const uint32_t *idx = nullptr, size_t n_list = 0);
+                                 uint64_t *d_keys, float *d_scores, uint32_t *d_counts, void *stream, const uint32_t *idx = nullptr,
+                                 size_t n_list = 0);
 extern "C" int leann_recompute_search_batch_device(const leann_recompute *r, const float *d_queries, size_t nq, size_t top_k,
                                                    const uint8_t *d_allow_mask, uint64_t *d_keys, float *d_scores,
                                                    uint32_t *d_counts, void *stream) {
@@ -632,44 +632,16 @@ extern "C" int leann_recompute_search_batch_device(const leann_recompute *r, con
             if (int e = list.acquire(1)) return e;
         }
     }
-    bool overflowed = false;
-    int rc = recompute_search_impl(r, d_queries, nq, top_k, d_allow_mask, d_keys, d_scores, d_counts, stream, true, &overflowed, list, n_list);
-    // a candidate list overflowed (adversarial score order, e.g. ascending): repeat on the score-slab path
-    if (rc == LEANN_OK && overflowed)
-        rc = recompute_search_impl(r, d_queries, nq, top_k, d_allow_mask, d_keys, d_scores, d_counts, stream, false, &overflowed, list, n_list);
+    int rc = recompute_search_impl(r, d_queries, nq, top_k, d_allow_mask, d_keys, d_scores, d_counts, stream, list, n_list);
     if (list) (void)hipStreamSynchronize((hipStream_t)stream); // before the lease ends (already idle unless an error cut the search short)
     return rc;
 }
 static int recompute_search_impl(const leann_recompute *r, const float *d_queries, size_t nq, size_t top_k, const uint8_t *d_allow_mask,
-                                 uint64_t *d_keys, float *d_scores, uint32_t *d_counts, void *stream, bool emit_ok, bool *overflowed,
-                                 const uint32_t *idx, size_t n_list) {
+                                 uint64_t *d_keys, float *d_scores, uint32_t *d_counts, void *stream, const uint32_t *idx, size_t n_list) {
     hipStream_t st = (hipStream_t)stream;
     const size_t N = idx ? n_list : r->n; // passages of this search (idx: the allowed ones, keys are list indices until the finalize step)
     if (idx) d_allow_mask = nullptr;
     const uint32_t k = (uint32_t)top_k;
-    const size_t SEGSZ = 2048;
-    // slab path: geometric chunk schedule 128k, 512k, 2M, 4M, 4M ... : the first small chunks fix the running k-th best, after
-    // which topk_scores_kernel skips almost every segment unsorted
-    std::vector<std::pair<size_t, size_t>> chunks; // (row0, rows)
-    {
-        // with candidate emission only the first chunk needs a score slab: 16k rows fix a first k-th-best bound, the next 496k
-        // tighten it (~k * 496k / 16k survivors per query), everything else goes through ONE persistent launch
-        const bool emit_schedule = emit_ok && use_fstat(r) && !leann_knobs().no_emit;
-        size_t pos = 0, len = emit_schedule ? (size_t)16 << 10 : (size_t)128 << 10;
-        while (pos < N) {
-            size_t rows = std::min(len, N - pos);
-            chunks.emplace_back(pos, rows);
-            pos += rows;
-            if (emit_schedule) len = chunks.size() == 1 ? (size_t)496 << 10 : N;
-            else len = std::min<size_t>(len * 4, (size_t)4 << 20);
-        }
-    }
-    const size_t n_chunks = chunks.size();
-    size_t chunk = 0, total_segs = 0;
-    for (auto &c : chunks) { chunk = std::max(chunk, c.second); total_segs += (c.second + SEGSZ - 1) / SEGSZ; }
-    chunk = std::max<size_t>(chunk, SEGSZ);
-    total_segs = std::max<size_t>(total_segs, 1);
-    const size_t cand_len = std::max<size_t>(total_segs * k, k);
     leann_recompute *rw = const_cast<leann_recompute *>(r);
     std::lock_guard<std::mutex> scratch_lock(rw->mu);
     if (use_fstat(r) && !idx && !rw->Ft && r->n >= 4096 && !leann_knobs().no_tiled) {
@@ -684,77 +656,47 @@ static int recompute_search_impl(const leann_recompute *r, const float *d_querie
     // queries per pass over the passages: the encode GEMM is shared by all of them (fused_fstat_kernel: up to 256, one G sub-slice
     // per 32 queries and unit); the general kernel is built for 64
     const size_t QT = use_fstat(r) ? FSTAT_MAX_QUERIES : 64;
-    if (int e = rw->sS.grow(QT * chunk)) return e;
+    const TopkShape shape = topk_shape_recompute(N, nq, k, QT);
     if (int e = rw->sGp.grow(r->hp * QT * 3 + 512)) return e; // + the fourth (unused) KiB piece of the last k-step
-    if (rw->sCandA.grow(nq * cand_len) || rw->sCandB.grow(nq * cand_len) || rw->sBest.grow(nq * k)) return LEANN_ERR_DEVICE;
-    float *S = rw->sS;
     uint16_t *Gp = rw->sGp;
-    uint64_t *candA = rw->sCandA, *candB = rw->sCandB, *best = rw->sBest;
-    // chunks after the first emit their few survivors straight from the fused kernel (no score slab, no segment sort)
-    const uint32_t EMIT_CAP = std::max<uint32_t>(8192, 32 * k); // expected survivors per query ~ k * rows / rows_seen (x19 after 512k of 10M rows)
-    const bool emit = emit_ok && use_fstat(r) && n_chunks > 1 && k <= 1024 && !leann_knobs().no_emit;
-    CandEmit em{};
-    uint32_t *d_overflow = nullptr;
-    if (emit) {
-        // [QT f32 thr | QT u32 cnt | u32 overflow | pad to 4 KiB | QT x EMIT_CAP u64 list]
-        if (int e = rw->sEmit.grow(4096 + sizeof(uint64_t) * QT * EMIT_CAP)) return e;
-        em.thr = reinterpret_cast<const float *>(rw->sEmit.p);
-        em.cnt = reinterpret_cast<uint32_t *>(rw->sEmit + 1024);
-        d_overflow = reinterpret_cast<uint32_t *>(rw->sEmit + 2048);
-        em.list = reinterpret_cast<uint64_t *>(rw->sEmit + 4096);
-        em.cap = EMIT_CAP;
-        em.allow = d_allow_mask;
-        HIP_CHECK_RET(hipMemsetAsync(rw->sEmit, 0, 4096, st));
-    }
-    HIP_CHECK_RET(hipMemsetAsync(candA, 0xFF, sizeof(uint64_t) * nq * cand_len, st));
-    HIP_CHECK_RET(hipMemsetAsync(best, 0xFF, sizeof(uint64_t) * nq * k, st));
-    int rc = LEANN_OK;
-    const size_t n_tiles = (nq + QT - 1) / QT;
-    struct EventSet { // destroyed on every exit, including the HIP_CHECK_RET returns below
-        std::vector<hipEvent_t> v;
-        ~EventSet() { for (auto &e : v) if (e) (void)hipEventDestroy(e); }
-    } evset;
-    evset.v.assign(n_tiles * n_chunks * 3 + 1, nullptr);
-    std::vector<hipEvent_t> &evs = evset.v;
-    for (auto &e : evs) HIP_CHECK_RET(hipEventCreate(&e));
-    size_t ei = 0;
-    for (size_t q0 = 0; q0 < nq && rc == LEANN_OK; q0 += QT) {
-        const uint32_t nqt = (uint32_t)std::min<size_t>(QT, nq - q0);
-        const uint32_t q_slots = use_fstat(r) ? (nqt + 31) / 32 * 32 : 64; // fused_fstat_kernel sizes its G image by 32-query tiles
-        hipLaunchKernelGGL(project_queries_kernel, dim3((unsigned)((r->hp + 3) / 4), (unsigned)((q_slots + 63) / 64)), dim3(256), 0, st, r->Wraw, (uint32_t)r->h,
-                           (uint32_t)r->hp, (uint32_t)r->d, d_queries + q0 * r->d, (uint32_t)r->d, nqt, Gp, use_fstat(r) ? 1 : 0, q_slots);
-        size_t seg_off = 0;
-        for (size_t c = 0; c < n_chunks && rc == LEANN_OK; c++) {
-            const size_t row0 = chunks[c].first, rows = chunks[c].second;
-            (void)hipEventRecord(evs[ei++], st);
-            const bool emit_chunk = emit && c > 0;
-            em.pos0 = row0;
-            rc = launch_encode(r, row0, rows, nullptr, st, Gp, nqt, S, nullptr, emit_chunk ? &em : nullptr, idx);
-            (void)hipEventRecord(evs[ei++], st);
-            size_t segs = 0;
-            if (rc == LEANN_OK && !emit_chunk)
-                rc = leann_internal_topk_chunk(S, rows, nqt, k, d_allow_mask, row0, candA + q0 * cand_len, cand_len, seg_off, st, &segs,
-                                               best + q0 * k);
-            if (rc == LEANN_OK && emit) // merge the survivors (none after chunk 0), publish the k-th best as the next threshold
-                rc = leann_internal_fold_candidates(em, k, nqt, (uint32_t)QT, best + q0 * k, d_overflow, st);
-            (void)hipEventRecord(evs[ei++], st);
-            seg_off += segs;
+    // only the feature-stationary kernel emits; a candidate list that overflows (adversarial score order, e.g. ascending) makes
+    // the call repeat on the slab schedule
+    for (bool emit = use_fstat(r) && !leann_knobs().no_emit;; emit = false) {
+        TopkRun run{topk_plan(shape, emit)};
+        const TopkPlan &p = run.plan;
+        if (int e = rw->sS.grow(QT * p.slab_rows)) return e;
+        if (rw->sCandA.grow(nq * p.cand_len) || rw->sCandB.grow(nq * p.cand_len) || rw->sBest.grow(nq * k)) return LEANN_ERR_DEVICE;
+        if (p.emit)
+            if (int e = rw->sEmit.grow(p.emit_bytes)) return e;
+        const size_t n_chunks = p.chunks.size(), n_tiles = (nq + QT - 1) / QT;
+        struct EventSet { // destroyed on every exit, including the HIP_CHECK_RET returns below
+            std::vector<hipEvent_t> v;
+            ~EventSet() { for (auto &e : v) if (e) (void)hipEventDestroy(e); }
+        } evset;
+        evset.v.assign(n_tiles * n_chunks * 3 + 1, nullptr);
+        std::vector<hipEvent_t> &evs = evset.v;
+        for (auto &e : evs) HIP_CHECK_RET(hipEventCreate(&e));
+        run.S = rw->sS, run.candA = rw->sCandA, run.candB = rw->sCandB, run.best = rw->sBest, run.emit_block = rw->sEmit;
+        run.nq = nq, run.k = k, run.allow = d_allow_mask, run.st = st, run.done = evs.back();
+        int rc = leann_internal_topk_begin(run);
+        size_t ei = 0;
+        for (size_t q0 = 0; q0 < nq && rc == LEANN_OK; q0 += QT) {
+            const uint32_t nqt = (uint32_t)std::min<size_t>(QT, nq - q0);
+            const uint32_t q_slots = use_fstat(r) ? (nqt + 31) / 32 * 32 : 64; // fused_fstat_kernel sizes its G image by 32-query tiles
+            hipLaunchKernelGGL(project_queries_kernel, dim3((unsigned)((r->hp + 3) / 4), (unsigned)((q_slots + 63) / 64)), dim3(256), 0, st, r->Wraw, (uint32_t)r->h,
+                               (uint32_t)r->hp, (uint32_t)r->d, d_queries + q0 * r->d, (uint32_t)r->d, nqt, Gp, use_fstat(r) ? 1 : 0, q_slots);
+            for (size_t c = 0; c < n_chunks && rc == LEANN_OK; c++) {
+                (void)hipEventRecord(evs[ei++], st);
+                const CandEmit em = run.chunk_emit(c);
+                rc = launch_encode(r, p.chunks[c].first, p.chunks[c].second, nullptr, st, Gp, nqt, run.S, nullptr, &em, idx);
+                (void)hipEventRecord(evs[ei++], st);
+                if (rc == LEANN_OK) rc = leann_internal_topk_select_chunk(run, c, q0, nqt);
+                (void)hipEventRecord(evs[ei++], st);
+            }
         }
-    }
-    if (rc == LEANN_OK) {
-        // `best` is the exact running top-k; without emission the final answer is re-derived from all segment winners
-        if (emit) rc = leann_internal_scan_finish_ex(best, candB, k, 1, nq, k, r->key_offset, d_keys, d_scores, d_counts, st, idx, 0);
-        else rc = leann_internal_scan_finish_ex(candA, candB, cand_len, total_segs, nq, k, r->key_offset, d_keys, d_scores, d_counts, st, idx, 0);
-    }
-    (void)hipEventRecord(evs[ei], st);
-    (void)hipStreamSynchronize(st);
-    *overflowed = false;
-    if (emit && rc == LEANN_OK) {
-        uint32_t ov = 0;
-        HIP_CHECK_RET(hipMemcpy(&ov, d_overflow, 4, hipMemcpyDeviceToHost));
-        *overflowed = ov != 0;
-    }
-    {
+        bool overflowed = false;
+        if (rc == LEANN_OK) rc = leann_internal_topk_finish(run, r->key_offset, idx, 0, d_keys, d_scores, d_counts, &overflowed);
+        else (void)hipStreamSynchronize(st);
         rw->last_ms[0] = rw->last_ms[1] = rw->last_ms[2] = 0.f;
         float ms = 0.f;
         for (size_t i = 0; i + 2 < ei + 1 && rc == LEANN_OK; i += 3) {
@@ -762,8 +704,8 @@ static int recompute_search_impl(const leann_recompute *r, const float *d_querie
             if (hipEventElapsedTime(&ms, evs[i + 1], evs[i + 2]) == hipSuccess) rw->last_ms[2] += ms; // segment top-k
         }
         if (ei >= 3 && rc == LEANN_OK && hipEventElapsedTime(&ms, evs[ei - 1], evs[ei]) == hipSuccess) rw->last_ms[2] += ms;
+        if (rc != LEANN_OK || !overflowed) return rc;
     }
-    return rc;
 }
 
 // ================================================================================================

@@ -407,23 +407,6 @@ int leann_internal_score(const float *X, size_t rows, size_t dims, size_t ld, co
     return LEANN_OK;
 }
 
-__global__ void update_best_kernel(const uint64_t *__restrict__ cand, uint32_t cand_stride_q, uint32_t seg_off, uint32_t n_segs,
-                                   uint32_t k, uint64_t *__restrict__ best);
-// one chunk: scores of rows [0, rows) of Xbase against all queries, per-segment top-k appended to cand
-int leann_internal_scan_chunk(const float *Xbase, size_t rows, size_t dims, size_t ld, const float *d_queries, size_t nq, uint32_t k,
-                              const uint8_t *allow, uint64_t pos0, float *S, uint64_t *cand, size_t cand_len, size_t seg_off,
-                              hipStream_t st, size_t *segs_out, hipEvent_t mid, uint64_t *best, const uint32_t *idx) {
-    launch_score(st, Xbase, rows, dims, ld, d_queries, nq, dims, S, CandEmit{}, idx);
-    if (mid) (void)hipEventRecord(mid, st);
-    unsigned segs = (unsigned)((rows + SEG - 1) / SEG);
-    hipLaunchKernelGGL(topk_scores_kernel, dim3(segs, (unsigned)nq), dim3(256), 0, st, S, (uint32_t)rows, pos0, allow, k, cand,
-                       (uint32_t)cand_len, (uint32_t)seg_off, (const uint64_t *)best);
-    if (best)
-        hipLaunchKernelGGL(update_best_kernel, dim3((unsigned)nq), dim3(256), 0, st, cand, (uint32_t)cand_len, (uint32_t)seg_off, segs, k, best);
-    HIP_CHECK_RET(hipGetLastError());
-    *segs_out = segs;
-    return LEANN_OK;
-}
 // merge this chunk's segment winners into the running per-query best-k (ascending keys)
 __global__ void __launch_bounds__(256) update_best_kernel(const uint64_t *__restrict__ cand, uint32_t cand_stride_q, uint32_t seg_off,
                                                           uint32_t n_segs, uint32_t k, uint64_t *__restrict__ best) {
@@ -459,10 +442,6 @@ int leann_internal_topk_chunk(const float *S, size_t rows, size_t nq, uint32_t k
     return LEANN_OK;
 }
 // reduction rounds until one segment per query remains, then keys -> (position + key_offset, score)
-int leann_internal_scan_finish(uint64_t *candA, uint64_t *candB, size_t cand_len, size_t total_segs, size_t nq, uint32_t k,
-                               uint64_t key_offset, uint64_t *d_keys, float *d_scores, uint32_t *d_counts, hipStream_t st) {
-    return leann_internal_scan_finish_ex(candA, candB, cand_len, total_segs, nq, k, key_offset, d_keys, d_scores, d_counts, st, nullptr, 0);
-}
 // idx: keys are indices into a row list (score_mfma_kernel<true>); as_dist: report 1 - score, the backends' distance
 int leann_internal_scan_finish_ex(uint64_t *candA, uint64_t *candB, size_t cand_len, size_t total_segs, size_t nq, uint32_t k, uint64_t key_offset,
                           uint64_t *d_keys, float *d_scores, uint32_t *d_counts, hipStream_t st, const uint32_t *idx, int as_dist) {
@@ -479,6 +458,60 @@ int leann_internal_scan_finish_ex(uint64_t *candA, uint64_t *candB, size_t cand_
                        d_keys, d_scores, d_counts, idx, as_dist);
     HIP_CHECK_RET(hipGetLastError());
     return LEANN_OK;
+}
+
+// ---- the select step of an exhaustive top-k (TopkRun, internal.h; schedules and scratch: topk_plan.h) ----
+int leann_internal_topk_begin(TopkRun &run) {
+    const TopkPlan &p = run.plan;
+    HIP_CHECK_RET(hipMemsetAsync(run.candA, 0xFF, sizeof(uint64_t) * run.nq * p.cand_len, run.st));
+    HIP_CHECK_RET(hipMemsetAsync(run.best, 0xFF, sizeof(uint64_t) * run.nq * run.k, run.st));
+    run.em = CandEmit{};
+    run.d_overflow = nullptr;
+    run.seg_off = 0;
+    if (p.emit) {
+        unsigned char *b = run.emit_block;
+        HIP_CHECK_RET(hipMemsetAsync(b, 0, p.list_off, run.st)); // thresholds, counters and the overflow word
+        run.em.thr = reinterpret_cast<const float *>(b);
+        run.em.cnt = reinterpret_cast<uint32_t *>(b + p.cnt_off);
+        run.d_overflow = reinterpret_cast<uint32_t *>(b + p.overflow_off);
+        run.em.list = reinterpret_cast<uint64_t *>(b + p.list_off);
+        run.em.cap = p.emit_cap;
+        run.em.allow = run.allow;
+    }
+    return LEANN_OK;
+}
+int leann_internal_topk_select_chunk(TopkRun &run, size_t c, size_t q0, uint32_t nqt) {
+    const TopkPlan &p = run.plan;
+    uint64_t *best = run.best + q0 * run.k;
+    if (c == 0) run.seg_off = 0; // every query tile fills its own rows of candA from segment 0
+    if (p.slab_chunk(c)) {
+        size_t segs = 0;
+        if (int rc = leann_internal_topk_chunk(run.S, p.chunks[c].second, nqt, run.k, run.allow, p.chunks[c].first, run.candA + q0 * p.cand_len,
+                                               p.cand_len, run.seg_off, run.st, &segs, p.track_best() ? best : nullptr))
+            return rc;
+        run.seg_off += segs;
+    }
+    // merge the survivors (none after chunk 0), publish the k-th best as the next threshold
+    return p.emit ? leann_internal_fold_candidates(run.em, run.k, nqt, (uint32_t)p.slots, best, run.d_overflow, run.st) : LEANN_OK;
+}
+int leann_internal_topk_finish(TopkRun &run, uint64_t key_offset, const uint32_t *idx, int as_dist, uint64_t *d_keys, float *d_scores,
+                               uint32_t *d_counts, bool *overflowed) {
+    const TopkPlan &p = run.plan;
+    *overflowed = false;
+    // under emission `best` is the exact running top-k; otherwise the answer is re-derived from all segment winners
+    int rc = p.emit ? leann_internal_scan_finish_ex(run.best, run.candB, run.k, 1, run.nq, run.k, key_offset, d_keys, d_scores, d_counts, run.st, idx, as_dist)
+                    : leann_internal_scan_finish_ex(run.candA, run.candB, p.cand_len, p.total_segs, run.nq, run.k, key_offset, d_keys, d_scores,
+                                                    d_counts, run.st, idx, as_dist);
+    if (run.done) (void)hipEventRecord(run.done, run.st);
+    // the scratch is plain hipMalloc memory that the caller gives back or reuses next: wait for the stream (these entry points are
+    // synchronous; the stream-ordered allocator proved unreliable on this stack)
+    (void)hipStreamSynchronize(run.st);
+    if (p.emit && rc == LEANN_OK) {
+        uint32_t ov = 0;
+        HIP_CHECK_RET(hipMemcpy(&ov, run.d_overflow, 4, hipMemcpyDeviceToHost));
+        *overflowed = ov != 0;
+    }
+    return rc;
 }
 
 // idx != null: exact search over the n listed positions of d_rows (ascending; no allow mask), keys = idx[i] + key_offset.
@@ -502,86 +535,38 @@ static int scan_topk_impl(const float *d_rows, size_t n, size_t dims, size_t ld,
                           const uint8_t *d_allow_mask, uint64_t key_offset, uint64_t *d_keys, float *d_scores, uint32_t *d_counts,
                           hipStream_t st, const uint32_t *idx, int as_dist) {
     const uint32_t k = (uint32_t)top_k;
-    // Pass 1 (emission): a 64k-row slab + segment top-k fixes a first k-th best per query; the following launches (448k rows, then
-    // everything else) emit only the scores that reach it (CandEmit).  A candidate list that overflows (adversarial order) makes the
-    // call repeat on pass 2, the slab path: geometric chunks 128k, 512k, 2M, ... (slab <= 2 GiB) with threshold-pruned segment sorts.
-    for (int pass = (n > ((size_t)64 << 10) && !leann_knobs().no_emit) ? 1 : 2; pass <= 2; pass++) {
-        const bool emit = pass == 1;
-        std::vector<std::pair<size_t, size_t>> chunks;
-        {
-            const size_t cap_rows = std::max<size_t>(SEG, (((size_t)1 << 29) / std::max<size_t>(nq, 1)) / SEG * SEG);
-            size_t pos = 0, len = std::min(cap_rows, emit ? (size_t)64 << 10 : (size_t)128 << 10);
-            while (pos < n) {
-                const size_t rows = std::min(len, n - pos);
-                chunks.emplace_back(pos, rows);
-                pos += rows;
-                if (emit) len = chunks.size() == 1 ? (size_t)448 << 10 : n;
-                else len = std::min(cap_rows, len * 4);
-            }
-        }
-        const size_t n_chunks = chunks.size();
-        size_t slab_rows = SEG, total_segs = 0;
-        for (size_t c = 0; c < n_chunks; c++)
-            if (!emit || c == 0) { slab_rows = std::max(slab_rows, chunks[c].second); total_segs += (chunks[c].second + SEG - 1) / SEG; }
-        total_segs = std::max<size_t>(total_segs, 1);
-        const size_t cand_len = std::max<size_t>(total_segs * k, k); // per query
-        const size_t slots = (nq + 63) / 64 * 64;                     // score_mfma_kernel reads a threshold for every query of a tile
-        const uint32_t EMIT_CAP = std::max<uint32_t>(8192, 32 * k); // expected survivors per query ~ k * rows / rows_seen (x19 after 512k of 10M rows)
+    const TopkShape shape = topk_shape_scan(n, nq, k);
+    // the emission schedule first; a candidate list that overflows (adversarial order) makes the call repeat on the slab schedule
+    for (bool emit = n > shape.emit_first && !leann_knobs().no_emit;; emit = false) {
+        TopkRun run{topk_plan(shape, emit)};
+        const TopkPlan &p = run.plan;
         // every return, early ones included (a failed allocation, a launch error), gives the pass's scratch back
         ScratchLease<float> S;
         ScratchLease<uint64_t> candA, candB, best;
-        ScratchLease<unsigned char> emb; // [slots f32 thr | slots u32 cnt | u32 overflow | pad | slots x EMIT_CAP u64]
-        const size_t em_hdr = (slots * 8 + 4 + 255) / 256 * 256;
+        ScratchLease<unsigned char> emb;
         struct SyncFirst { // (declared after the leases, so it runs before them) nothing may still be running on a block that goes back
             hipStream_t st;
             ~SyncFirst() { (void)hipStreamSynchronize(st); }
         } sync_first{st};
-        if (int e = S.acquire(nq * slab_rows)) return e;
-        if (int e = candA.acquire(nq * cand_len)) return e;
-        if (int e = candB.acquire(nq * cand_len)) return e;
+        if (int e = S.acquire(shape.q_tile * p.slab_rows)) return e;
+        if (int e = candA.acquire(nq * p.cand_len)) return e;
+        if (int e = candB.acquire(nq * p.cand_len)) return e;
         if (int e = best.acquire(nq * k)) return e;
-        HIP_CHECK_RET(hipMemsetAsync(candA, 0xFF, sizeof(uint64_t) * nq * cand_len, st));
-        HIP_CHECK_RET(hipMemsetAsync(best, 0xFF, sizeof(uint64_t) * nq * k, st));
-        CandEmit em{};
-        uint32_t *d_overflow = nullptr;
-        if (emit) {
-            if (int e = emb.acquire(em_hdr + sizeof(uint64_t) * slots * EMIT_CAP)) return e;
-            HIP_CHECK_RET(hipMemsetAsync(emb, 0, em_hdr, st));
-            em.thr = reinterpret_cast<const float *>(emb.p);
-            em.cnt = reinterpret_cast<uint32_t *>(emb + slots * 4);
-            d_overflow = reinterpret_cast<uint32_t *>(emb + slots * 8);
-            em.list = reinterpret_cast<uint64_t *>(emb + em_hdr);
-            em.cap = EMIT_CAP;
-            em.allow = d_allow_mask;
+        if (p.emit)
+            if (int e = emb.acquire(p.emit_bytes)) return e;
+        run.S = S, run.candA = candA, run.candB = candB, run.best = best, run.emit_block = emb;
+        run.nq = nq, run.k = k, run.allow = d_allow_mask, run.st = st;
+        int rc = leann_internal_topk_begin(run);
+        for (size_t c = 0; c < p.chunks.size() && rc == LEANN_OK; c++) {
+            const size_t row0 = p.chunks[c].first;
+            launch_score(st, idx ? d_rows : d_rows + row0 * ld, p.chunks[c].second, dims, ld, d_queries, nq, dims, S, run.chunk_emit(c),
+                         idx ? idx + row0 : nullptr);
+            rc = leann_internal_topk_select_chunk(run, c, 0, (uint32_t)nq);
         }
-        size_t seg_off = 0;
-        int rc = LEANN_OK;
-        for (size_t c = 0; c < n_chunks && rc == LEANN_OK; c++) {
-            const size_t row0 = chunks[c].first, rows = chunks[c].second;
-            size_t segs = 0;
-            if (emit && c > 0) {
-                em.pos0 = row0;
-                launch_score(st, idx ? d_rows : d_rows + row0 * ld, rows, dims, ld, d_queries, nq, dims, S, em, idx ? idx + row0 : nullptr);
-            } else {
-                rc = leann_internal_scan_chunk(idx ? d_rows : d_rows + row0 * ld, rows, dims, ld, d_queries, nq, k, d_allow_mask, row0, S, candA,
-                                               cand_len, seg_off, st, &segs, nullptr, (n_chunks > 1 || emit) ? best.p : nullptr,
-                                               idx ? idx + row0 : nullptr);
-            }
-            if (rc == LEANN_OK && emit) rc = leann_internal_fold_candidates(em, k, (uint32_t)nq, (uint32_t)slots, best, d_overflow, st);
-            seg_off += segs;
-        }
-        if (rc == LEANN_OK) {
-            if (emit) rc = leann_internal_scan_finish_ex(best, candB, k, 1, nq, k, key_offset, d_keys, d_scores, d_counts, st, idx, as_dist); // best = exact running top-k
-            else rc = leann_internal_scan_finish_ex(candA, candB, cand_len, total_segs, nq, k, key_offset, d_keys, d_scores, d_counts, st, idx, as_dist);
-        }
-        // scratch is plain hipMalloc memory: wait for the stream before giving it back (this entry point
-        // is synchronous; the stream-ordered allocator proved unreliable on this stack)
-        (void)hipStreamSynchronize(st);
-        uint32_t ov = 0;
-        if (emit && rc == LEANN_OK && hipMemcpy(&ov, d_overflow, 4, hipMemcpyDeviceToHost) != hipSuccess) rc = LEANN_ERR_DEVICE;
-        if (rc != LEANN_OK || !emit || ov == 0) return rc;
+        bool overflowed = false;
+        if (rc == LEANN_OK) rc = leann_internal_topk_finish(run, key_offset, idx, as_dist, d_keys, d_scores, d_counts, &overflowed);
+        if (rc != LEANN_OK || !overflowed) return rc;
     }
-    return LEANN_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
