@@ -186,6 +186,42 @@ int leann_backend_consolidate(leann_backend *h);
 size_t leann_backend_live_len(const leann_backend *h);
 int leann_backend_removed_bitmap(const leann_backend *h, uint8_t *out /* ceil(len/8) */, size_t *n_pending);
 int leann_backend_remove_from_index(int backend, const uint64_t *keys, size_t n, size_t dims, const char *index_path_stem);
+/* ---- compaction: remove -> consolidate -> compact (csrc/compact.hip, DESIGN.md §5b "Compaction") ----------------------------------
+ * A NEW handle holding only the live positions of `h`, renumbered 0 .. live-1 in their old order; `h` is left as it is (close it to
+ * give its memory back).  new_to_old (may be NULL): [leann_backend_live_len(h)] OLD global keys, ascending — the caller rewrites its
+ * positional id map with it.  key_offset: the new handle's (a shard that moves down after its predecessors shrank);
+ * LEANN_KEY_OFFSET_KEEP = that of `h`.
+ * Definition.  Let p_0 < p_1 < ... be the live positions of `h`.  The result is the leann_backend_from_arrays[_rows] handle over
+ *     rows          row p_j at new position j, byte for byte (the row type is unchanged; the result always owns its rows)
+ *     levels        level of p_j at j
+ *     level-0 list  of j: the list of p_j, slot for slot, every id mapped through old -> new; 0xFFFFFFFF slots stay where they are
+ *     upper lists   the upper lists of p_j in level order, mapped the same way; upper_off = the exclusive prefix sum of the levels
+ *     entry         map(entry);  M, M0, max_level and the kind are unchanged
+ *     efc, alpha, the Vamana prune form, entry layers and the reference-ef latch are unchanged: with the row type this is every
+ *                   piece of state leann_backend_to_rows copies, so a later remove + consolidate on the result repairs by the build's rule
+ *     removal state none: nothing removed, no live mask, live_len == len; leann_backend_save writes an ordinary file and deletes a
+ *                   stale sidecar.  (leann_backend_add on such a file rebuilds over the concatenation: its levels are no longer the
+ *                   builder's hash of the position.)
+ * Rows large enough for the row screen get their planes cut by the rule of leann_backend_build_device.  Nothing is searched, pruned
+ * or rounded: a walk of the result returns, through the map, the keys, f32 distance bits, counts and counters of the same walk of `h`
+ * (the map is monotone, so ties broken by the lower key stay).
+ * Checked before any device work, each message naming the way out:  live lists still name removed positions (n_pending > 0), or the
+ * entry point is removed -> LEANN_ERR_INVALID (call leann_backend_consolidate first);  nothing live -> LEANN_ERR_INVALID;  NULL `h` /
+ * `out` -> LEANN_ERR_INVALID;  a composite handle -> LEANN_ERR_UNSUPPORTED (compact each leann_backend_shard with key_offset = the
+ * running sum of the live lengths, then leann_sharded_from_handles);  a recompute-on handle -> LEANN_ERR_UNSUPPORTED (it cannot
+ * consolidate, so its lists keep naming removed positions).  A live list that names a removed id although n_pending == 0 is found on
+ * the device -> LEANN_ERR_INVALID ("inconsistent graph"), no handle made.
+ * Allowed: f32 handles with owned or borrowed rows; bf16 handles with n_pending == 0 (e.g. f32 -> remove -> consolidate ->
+ * leann_backend_to_rows, which carries the removals over); a handle without removals (a plain copy, identity map).
+ * Not concurrent with searches on `h`, like remove and consolidate.  Peak device memory is `h` plus the result; compacting in place
+ * is out of scope. */
+#define LEANN_KEY_OFFSET_KEEP UINT64_MAX
+int leann_backend_compact(const leann_backend *h, uint64_t key_offset, leann_backend **out, uint64_t *new_to_old);
+/* file twin, like leann_backend_remove_from_index: open -> consolidate if lists still name removed positions -> compact -> save.
+ * new_to_old (may be NULL) holds `cap` entries; *n_live (may be NULL) = the live positions, set whenever the file opens.
+ * cap < live positions -> LEANN_ERR_INVALID naming the size needed, nothing written.  Nothing removed: identity map, file untouched. */
+int leann_backend_compact_index(int backend, size_t dims, const char *index_path_stem,
+                                uint64_t *new_to_old, size_t cap, size_t *n_live);
 /* the sidecar's writer and validator on their own (no handle, no device): `bitmap` / `bitmap_out` hold ceil(n/8) bytes */
 int leann_tombstones_write(const char *path, const uint8_t *bitmap, uint64_t n, uint64_t n_pending);
 int leann_tombstones_read(const char *path, uint64_t n_expected, uint8_t *bitmap_out, uint64_t *n_removed, uint64_t *n_pending);

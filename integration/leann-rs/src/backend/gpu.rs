@@ -65,6 +65,12 @@ extern "C" {
     #[allow(dead_code)]
     fn leann_backend_removed_bitmap(h: *const LeannBackend, out: *mut u8, n_pending: *mut usize) -> c_int;
     fn leann_backend_remove_from_index(backend: c_int, keys: *const u64, n: usize, dims: usize, stem: *const c_char) -> c_int;
+    // compaction (additive): a new handle over the live positions only, renumbered 0 .. live-1 in their old order; new_to_old holds
+    // the old global key of every new position
+    #[allow(dead_code)]
+    fn leann_backend_compact(h: *const LeannBackend, key_offset: u64, out: *mut *mut LeannBackend, new_to_old: *mut u64) -> c_int;
+    fn leann_backend_compact_index(backend: c_int, dims: usize, stem: *const c_char, new_to_old: *mut u64, cap: usize,
+                                   n_live: *mut usize) -> c_int;
     // row types (additive): 0 = f32 (the default: the calls above), 1 = bf16 rows — half the device memory and index file; a bf16
     // index answers bit for bit like the f32 index over the rounded rows.  leann_backend_open detects the type from the file.
     #[allow(dead_code)]
@@ -185,4 +191,31 @@ pub fn remove_from_index(backend: c_int, keys: &[u64], index_path: &Path, dimens
         return Err(last_error());
     }
     Ok(())
+}
+
+/// Compact the index on disk after removals: open -> consolidate if need be -> compact -> save.  Returns new_to_old: entry j is the
+/// OLD position of the passage that now sits at position j (ascending; the identity, and an untouched file, when nothing was removed).
+///
+/// The id map above the backend is positional (searcher.rs:83-92), so the caller applies the map before the next open: the new
+/// `<stem>.ids.txt` has line new_to_old[j] of the old one as its line j.  The passage-offset table (`passages.idx.json`) is keyed by
+/// passage id, not by position: it stays valid as it is, and the entries of the ids that left `ids.txt` may be dropped from it — the
+/// offsets that remain still point into the unchanged `passages.jsonl`, whose removed records are then simply unreferenced (rewriting
+/// that file is a separate, optional step).  The passage count in the meta file becomes the map's length.  Write the new `ids.txt`
+/// beside the old one and rename it once this call has returned.
+pub fn compact_index(backend: c_int, index_path: &Path, dimensions: usize) -> anyhow::Result<Vec<u64>> {
+    let stem = CString::new(index_path.to_string_lossy().as_bytes())?;
+    // a map without room changes nothing on disk and reports the size needed
+    let mut live = 0usize;
+    let mut probe = [0u64; 1];
+    let rc = unsafe { leann_backend_compact_index(backend, dimensions, stem.as_ptr(), probe.as_mut_ptr(), 0, &mut live) };
+    if rc != 0 && live == 0 {
+        return Err(last_error());
+    }
+    let mut map = vec![0u64; live.max(1)];
+    let rc = unsafe { leann_backend_compact_index(backend, dimensions, stem.as_ptr(), map.as_mut_ptr(), map.len(), &mut live) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    map.truncate(live);
+    Ok(map)
 }

@@ -268,6 +268,18 @@ class BackendSearcher:
         N.check(N.lib().leann_backend_removed_bitmap(self._h, _p(bm, u8p), C.byref(pend)))
         return bm[: (self.len() + 7) // 8], int(pend.value)
 
+    def compact(self, key_offset=None):
+        """(a new searcher of the same class over the live positions only, renumbered 0 .. live-1 in their old order; new_to_old
+        [live] uint64: the OLD global key of every new position).  Needs a consolidated handle; this one is left as it is.
+        key_offset: the new searcher's (None: this one's)."""
+        if key_offset is None:
+            key_offset = np.iinfo(np.uint64).max  # LEANN_KEY_OFFSET_KEEP
+        m = np.zeros(max(self.live_len(), 1), np.uint64)
+        h = C.c_void_p()
+        N.check(N.lib().leann_backend_compact(self._h, int(key_offset), C.byref(h), _p(m, u64p)))
+        s = type(self)(h, self.backend_type)
+        return s, m[: s.len()]
+
     # -- extras -------------------------------------------------------------------------------
     def stats(self, reset=False):
         s = N.SearchStats()
@@ -385,6 +397,19 @@ class BackendBuilder:
         N.check(N.lib().leann_backend_remove_from_index(int(self.backend_type), _p(k, u64p), k.shape[0], dimensions,
                                                         os.fsencode(str(index_path))))
 
+    def compact_index(self, index_path, dimensions):
+        """the file twin of BackendSearcher.compact: open -> consolidate if need be -> compact -> save.  Returns new_to_old [live]
+        uint64 (the identity, and an untouched file, when nothing was removed)."""
+        stem = os.fsencode(str(index_path))
+        live = C.c_size_t(0)
+        m = np.zeros(1, np.uint64)
+        # a map without room changes nothing and reports the size needed (a file that does not open raises here)
+        rc = N.lib().leann_backend_compact_index(int(self.backend_type), dimensions, stem, _p(m, u64p), 0, C.byref(live))
+        if rc != 0 and live.value == 0:
+            N.check(rc)
+        m = np.zeros(max(live.value, 1), np.uint64)
+        N.check(N.lib().leann_backend_compact_index(int(self.backend_type), dimensions, stem, _p(m, u64p), m.shape[0], C.byref(live)))
+        return m[: live.value]
 
 
 class Filter:

@@ -888,7 +888,8 @@ extern "C" int leann_backend_add(int backend, const float *vectors, size_t n, si
     h->g.n = nt;
     h->g.adj0 = nullptr; h->g.adjU = nullptr; h->g.upper_off = nullptr;
     rc = alloc_graph_arrays(h, LEVEL_SEED);
-    bool same_levels = true; // an index that did not come from this builder (leann_backend_from_arrays + save) has its own level table
+    bool same_levels = true; // an index that did not come from this builder (leann_backend_from_arrays + save) has its own level
+                             // table; so has a compacted one (compact.hip): its levels moved with the rows to new positions
     if (rc == LEANN_OK && n_old) {
         std::vector<uint8_t> la(n_old), lb(n_old);
         if (hipMemcpy(la.data(), old->store.levels, n_old, hipMemcpyDeviceToHost) != hipSuccess ||
