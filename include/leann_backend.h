@@ -222,6 +222,44 @@ int leann_backend_compact(const leann_backend *h, uint64_t key_offset, leann_bac
  * cap < live positions -> LEANN_ERR_INVALID naming the size needed, nothing written.  Nothing removed: identity map, file untouched. */
 int leann_backend_compact_index(int backend, size_t dims, const char *index_path_stem,
                                 uint64_t *new_to_old, size_t cap, size_t *n_live);
+/* ---- appending to a handle (csrc/build.hip, DESIGN.md §5 "Append to a handle") -----------------------------------------------------
+ * A NEW handle that continues the build of `h` with n more rows; `h` is only read and left as it is (close it to give its memory
+ * back).  leann_backend_append takes host rows [n x dims]; leann_backend_append_device rows on h's device, [n x ld] with ld >= dims
+ * and ld % 4 == 0.  leann_backend_add is the file twin (HNSW only, and it rebuilds an index whose levels are not the builder's hash).
+ * Definition.  Let n_old = leann_backend_len(h).  The result is a handle over n_old + n positions, on h's device, with h's key
+ * offset: the key of new row i is key_offset + n_old + i.
+ *     rows          [0, n_old): h's rows, byte for byte (also when h borrowed them); then the new rows at h's pitch, zero padded.  The
+ *                   result always owns its rows.
+ *     levels        positions < n_old keep the level they have in h, whatever made it (the builder, leann_backend_from_arrays, a
+ *                   compaction); positions >= n_old get the builder's hash of the position.  upper_off = the exclusive prefix sum of
+ *                   that table, which needs h's upper_off to be the prefix sum of h's levels: so for every built, opened or compacted
+ *                   handle; a leann_backend_from_arrays handle where it is not -> LEANN_ERR_INVALID naming upper_off.  There is no
+ *                   rebuild path: an append always continues.
+ *     graph         what the builder makes when it continues from h's lists: the stored link distances recomputed from the rows, the
+ *                   pending area empty, the new positions inserted in the builder's hash order among themselves, in batches of at
+ *                   most 1 / LEANN_BUILD_BATCH_FRACTION (default 1/8) of the positions linked so far.  HNSW starts from h's entry and
+ *                   max_level, which move to a new row that hashes to a higher level.  Vamana keeps h's medoid as the entry (not
+ *                   recomputed), uses h's alpha and prunes by the form h RECORDED (one- or two-stage), whatever
+ *                   LEANN_VAMANA_TWO_STAGE says now; LEANN_VAMANA_PENDING is read as for a build, there are no refine passes, and
+ *                   the final flush runs over all positions.
+ *     carried over  efc, alpha, the kind, M, M0, the Vamana prune form, the reference-ef latch and h's coalescing configuration (or
+ *                   the default): the state leann_backend_to_rows copies.
+ *     removals      carried over: the bitmap extended with zero bits, the live mask uploaded, n_pending counted again on the device
+ *                   (lists of new rows may name removed positions that walks still route through, as after leann_backend_add);
+ *                   live_len = h's + n.  A later remove, consolidate or compact on the result behaves as on any handle.
+ * Rows large enough for the row screen get their planes cut by the rule of leann_backend_build_device.  A leann_filter registered on
+ * `h` stays valid for `h` only: on the result it is refused with LEANN_ERR_INVALID ("filter belongs to another handle").  n == 0
+ * gives a plain copy.
+ * Checked before any device work, each message naming the way out:  NULL `h` / `out`, n > 0 rows with a NULL pointer, ld < dims,
+ * ld % 4 != 0, n_old + n >= 2^31 -> LEANN_ERR_INVALID;  a bf16 handle -> LEANN_ERR_UNSUPPORTED (the builder reads f32 rows: rebuild with
+ * leann_backend_build_rows);  a recompute-on handle -> LEANN_ERR_UNSUPPORTED (leann_recompute_build_index);  a composite handle ->
+ * LEANN_ERR_UNSUPPORTED (append to the last leann_backend_shard, then leann_sharded_from_handles);  a Vamana handle built with
+ * LEANN_VAMANA_NAV=1 -> LEANN_ERR_UNSUPPORTED (an experiment knob: rebuild).  On any error *out is NULL, nothing of the call's stays
+ * allocated and `h` answers as before.
+ * Not concurrent with remove, consolidate or searches on `h`, like compact.  Peak device memory is `h` plus the result plus the
+ * builder's scratch; appending in place is out of scope. */
+int leann_backend_append(const leann_backend *h, const float *vectors, size_t n, leann_backend **out);
+int leann_backend_append_device(const leann_backend *h, const float *d_vectors, size_t n, size_t ld, leann_backend **out);
 /* the sidecar's writer and validator on their own (no handle, no device): `bitmap` / `bitmap_out` hold ceil(n/8) bytes */
 int leann_tombstones_write(const char *path, const uint8_t *bitmap, uint64_t n, uint64_t n_pending);
 int leann_tombstones_read(const char *path, uint64_t n_expected, uint8_t *bitmap_out, uint64_t *n_removed, uint64_t *n_pending);
@@ -295,7 +333,7 @@ const float *leann_backend_device_rows(const leann_backend *h);
  * On a bf16 handle: leann_backend_graph_export with vectors != NULL writes w(rows); leann_backend_device_rows returns NULL; removal
  * (leann_backend_remove, live_len, removed_bitmap, the tombstone sidecar) works; filter mode 2 picks the walk.
  * LEANN_ERR_UNSUPPORTED with a message naming the way out: exact filtered search and filter mode 1 (use the walk), leann_backend_
- * consolidate (removals stay tombstones), leann_backend_add and leann_backend_remove_from_index (rebuild; or remove + save),
+ * consolidate (removals stay tombstones), leann_backend_add, leann_backend_append and leann_backend_remove_from_index (rebuild; or remove + save),
  * leann_backend_set_row_screen (no f32 planes exist), leann_backend_open with a device list on a version-3 file (build the shards
  * and use leann_sharded_from_handles: bf16 shards work, mixing row types -> LEANN_ERR_INVALID).
  * An unknown row_type -> LEANN_ERR_INVALID before any device work. */

@@ -69,6 +69,8 @@ SIGNATURES = {
     "leann_backend_remove_from_index": (C.c_int, [C.c_int, u64p, C.c_size_t, C.c_size_t, C.c_char_p]),
     "leann_backend_compact": (C.c_int, [vp, C.c_uint64, C.POINTER(vp), u64p]),
     "leann_backend_compact_index": (C.c_int, [C.c_int, C.c_size_t, C.c_char_p, u64p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "leann_backend_append": (C.c_int, [vp, f32p, C.c_size_t, C.POINTER(vp)]),
+    "leann_backend_append_device": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(vp)]),
     "leann_tombstones_write": (C.c_int, [C.c_char_p, u8p, C.c_uint64, C.c_uint64]),
     "leann_tombstones_read": (C.c_int, [C.c_char_p, C.c_uint64, u8p, u64p, u64p]),
     "leann_backend_stats": (C.c_int, [vp, C.POINTER(SearchStats), C.c_int]),

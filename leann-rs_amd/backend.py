@@ -280,6 +280,22 @@ class BackendSearcher:
         s = type(self)(h, self.backend_type)
         return s, m[: s.len()]
 
+    def append(self, vectors):
+        """a new searcher of the same class over this one's positions plus the rows of `vectors` [n x dims] (host), whose keys
+        continue the sequence; the graph is this one's, continued by the builder.  This searcher is left as it is."""
+        X = np.ascontiguousarray(vectors, np.float32)
+        if X.ndim != 2 or X.shape[1] != self.dims():
+            raise LeannError(1, f"vectors must be [n x {self.dims()}]")
+        h = C.c_void_p()
+        N.check(N.lib().leann_backend_append(self._h, _p(X, f32p) if X.shape[0] else None, X.shape[0], C.byref(h)))
+        return type(self)(h, self.backend_type)
+
+    def append_device(self, d_vectors_ptr, n, ld):
+        """append() for n rows already on this searcher's device: [n x ld] f32, ld >= dims, ld % 4 == 0"""
+        h = C.c_void_p()
+        N.check(N.lib().leann_backend_append_device(self._h, d_vectors_ptr, n, ld, C.byref(h)))
+        return type(self)(h, self.backend_type)
+
     # -- extras -------------------------------------------------------------------------------
     def stats(self, reset=False):
         s = N.SearchStats()

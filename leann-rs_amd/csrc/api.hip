@@ -452,6 +452,7 @@ extern "C" int leann_backend_filter_create(const leann_backend *hc, const uint8_
         }
         (void)hipSetDevice(hc->device);
         f->epoch = hc->removal_epoch;
+        f->owner = hc->serial;
         *out = f;
         return LEANN_OK;
     }
@@ -470,6 +471,7 @@ extern "C" int leann_backend_filter_create(const leann_backend *hc, const uint8_
         return LEANN_ERR_DEVICE;
     }
     f->epoch = hc->removal_epoch;
+    f->owner = hc->serial;
     int rc = leann_internal_and_live_inplace(hc, f->d_allow); // removed positions are never allowed: the bitmap and the list hold live ones only
     if (rc == LEANN_OK && f->n) rc = leann_internal_compact_allow(f->d_allow, f->n, &f->d_list, &f->n_allowed, nullptr);
     if (rc != LEANN_OK) {
@@ -497,6 +499,10 @@ extern "C" int leann_backend_search_filter_batch(const leann_backend *hc, const 
         filter->parts.empty() != (hc->sharded == nullptr)) { // (a filter registered on a sharded handle holds one sub-filter per shard, and only those)
         leann_set_error("leann_backend_search_filter_batch: null / foreign filter (made for %zu rows, the index has %zu) or bad mode %d",
                         filter ? filter->n : (size_t)0, hc ? (size_t)hc->g.n : (size_t)0, mode);
+        return LEANN_ERR_INVALID;
+    }
+    if (filter->owner != hc->serial) { // (same length, same device: a copy of the handle the filter was registered on)
+        leann_set_error("leann_backend_search_filter_batch: filter belongs to another handle; register it on this one");
         return LEANN_ERR_INVALID;
     }
     bool stale = filter->epoch != hc->removal_epoch;
@@ -787,6 +793,18 @@ extern "C" int leann_backend_set_coalescing(leann_backend *h, uint32_t wait_us, 
     }
     retire_coalescer(old);
     return LEANN_OK;
+}
+int leann_internal_copy_coalescing(const leann_backend *srcc, leann_backend *dst) {
+    leann_backend *src = const_cast<leann_backend *>(srcc);
+    int mode = 0;
+    uint32_t wait_us = 0, max_batch = 0;
+    {
+        std::lock_guard<std::mutex> lk(src->mu);
+        mode = src->coalesce_mode;
+        if (mode == 1 && src->coalescer) { wait_us = src->coalescer->wait_us; max_batch = src->coalescer->max_batch; }
+    }
+    if (mode == 0) return LEANN_OK; // automatic: the default of a new handle
+    return leann_backend_set_coalescing(dst, wait_us, max_batch); // (mode 2: (0, 0) switches it off)
 }
 // Automatic mode (the default; LEANN_COALESCE=off in the environment or leann_backend_set_coalescing(h, 0, 0) switch it off): the
 // reference's server calls search from many threads without knowing about batches (cli/serve.rs:289-292).  The first caller that

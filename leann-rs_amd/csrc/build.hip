@@ -19,6 +19,8 @@
 // so against them graphs are compared by invariants + recall.  The batched schedule itself is restated
 // in tests/build_ref.py: on rows with exact f32 dot products a build equals it list for list
 // (tests/test_gpu_build_parity.py); inexact rows keep the quality bar.
+// An existing graph is continued by continue_build (below): the body of leann_backend_add (a file) and of leann_backend_append[_device]
+// (an open handle; tests/test_gpu_append.py, tests/append_ref.py).
 #include "common.cuh"
 #include "search.cuh"
 #include "internal.h"
@@ -578,9 +580,10 @@ static uint32_t insertion_order(std::vector<uint32_t> &order, size_t lo, size_t 
     return order[lo];
 }
 
-static int build_on_device(leann_backend *h, size_t n_existing, size_t bmax_hint) {
+static int build_on_device(leann_backend *h, size_t n_existing, size_t bmax_hint, bool keep_prune_form = false) {
     // h->g.X / n / d / ld / M / M0 / kind / efc / alpha are set; adjacency arrays allocated & initialised
-    // for nodes < n_existing (append) or empty.
+    // for nodes < n_existing (append) or empty.  keep_prune_form: Vamana prunes by h->two_stage as it stands (the form the graph
+    // being continued was built with), not by LEANN_VAMANA_TWO_STAGE.
     Builder b;
     b.h = h;
     b.batch_fraction = (size_t)env_int("LEANN_BUILD_BATCH_FRACTION", 8, 1, 1 << 20);
@@ -601,7 +604,7 @@ static int build_on_device(leann_backend *h, size_t n_existing, size_t bmax_hint
         // 10M x 1536, R = 64, recall@10 at L = 72 over 2 000 queries (scripts/exp/vamana_slack.sh): strict (0 pending) 185.8 s / 0.9600;
         // 4 pending 82.2 s / 0.9596; 8: 65.3 s / 0.9531; 16: 56.1 s / 0.9547.  Back-edges that wait are invisible to the construction
         // searches of later points, which costs about half a point of recall from 8 on; 4 keeps the strict rule's recall at 2.3x its speed.
-        b.lv.two_stage = (uint32_t)env_int("LEANN_VAMANA_TWO_STAGE", 1, 0, 1);
+        b.lv.two_stage = keep_prune_form ? h->two_stage : (uint32_t)env_int("LEANN_VAMANA_TWO_STAGE", 1, 0, 1);
         h->two_stage = b.lv.two_stage; // delete consolidation repairs with the rule the build used
         const uint32_t slack = (uint32_t)env_int("LEANN_VAMANA_PENDING", 4, 0, 32);
         b.lv.P = slack;
@@ -681,13 +684,14 @@ static int build_on_device(leann_backend *h, size_t n_existing, size_t bmax_hint
 }
 
 // levels / upper_off on host (orc_level twin: common.cuh:node_level), uploaded once
-static int alloc_graph_arrays(leann_backend *h, uint64_t level_seed) {
+// `levels`: at least max(n, 1) entries; positions from `hash_from` on get the builder's hash of the position (what is in front of
+// them is the caller's: the levels of an existing graph), upper_off is the exclusive prefix sum of the whole table
+static int alloc_graph_arrays(leann_backend *h, uint64_t level_seed, std::vector<uint8_t> &levels, size_t hash_from) {
     const size_t n = h->g.n, nn = std::max<size_t>(n, 1);
-    std::vector<uint8_t> levels(nn, 0);
     std::vector<uint32_t> uo(nn, 0);
     uint64_t nu = 0;
     for (size_t i = 0; i < n; i++) {
-        levels[i] = (h->kind == LEANN_BACKEND_HNSW || h->nav_levels) ? (uint8_t)node_level(level_seed, i, h->g.M) : 0;
+        if (i >= hash_from) levels[i] = (h->kind == LEANN_BACKEND_HNSW || h->nav_levels) ? (uint8_t)node_level(level_seed, i, h->g.M) : 0;
         uo[i] = (uint32_t)nu;
         nu += levels[i];
     }
@@ -704,6 +708,10 @@ static int alloc_graph_arrays(leann_backend *h, uint64_t level_seed) {
     h->g.upper_off = h->store.upper_off = std::move(duo);
     h->store.levels = std::move(dlv);
     return LEANN_OK;
+}
+static int alloc_graph_arrays(leann_backend *h, uint64_t level_seed) { // a fresh build: every level is the hash
+    std::vector<uint8_t> levels(std::max<size_t>(h->g.n, 1), 0);
+    return alloc_graph_arrays(h, level_seed, levels, 0);
 }
 
 static constexpr uint64_t LEVEL_SEED = 0x5EED0003ull;
@@ -830,6 +838,72 @@ extern "C" int leann_backend_build(int backend, const float *vectors, size_t n, 
     return rc;
 }
 
+// Continue a build from an existing handle over a caller-staged row block: the one body behind leann_backend_add and
+// leann_backend_append[_device].  rows: f32 [nt x src->g.ld] on src's device (selected by the caller), src's rows first, then the new
+// ones, zero padded.  *out is a new handle over nt positions that BORROWS the block: the caller keeps it alive or hands it to the
+// handle afterwards.  Positions below n_old = src->g.n keep src's levels and lists, whatever made them; positions from n_old on get
+// the builder's hash of the position, and upper_off is the prefix sum of that table — which takes src's upper_off to be the prefix sum
+// of src's levels (so for every built, opened or compacted handle), the old upper lists then keeping their places in front of the new
+// ones.  The stored link distances are recomputed from the rows (link_dist_kernel), the pending area starts empty, and the batched
+// insertion goes on from src's entry and max_level in insertion_order(n_old, nt), batches by LEANN_BUILD_BATCH_FRACTION, Vamana
+// pruning by the form src recorded and flushing over all positions at the end.  nt == n_old: a copy of src's graph.  efc, alpha, the
+// prune form, the reference-ef latch, key offset and device are src's; removals, planes and coalescing are the caller's business.
+// src is only read; on an error nothing of the call's stays allocated and *out stays null.
+static int continue_build(const leann_backend *src, const float *rows, size_t nt, const char *who, leann_backend **out) {
+    *out = nullptr;
+    const size_t n_old = src->g.n;
+    std::vector<uint8_t> levels(std::max<size_t>(nt, 1), 0);
+    uint64_t old_lists = 0;
+    if (n_old) {
+        std::vector<uint32_t> uo(n_old);
+        if (hipMemcpy(levels.data(), src->store.levels, n_old, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(uo.data(), src->g.upper_off, n_old * 4, hipMemcpyDeviceToHost) != hipSuccess) {
+            leann_set_error("%s: reading the level tables failed: %s", who, hipGetErrorString(hipGetLastError()));
+            return LEANN_ERR_DEVICE;
+        }
+        for (size_t i = 0; i < n_old; i++) {
+            if (uo[i] != old_lists) {
+                leann_set_error("%s: upper_off[%zu] is %u where the prefix sum of the levels is %llu; an append keeps the old upper lists in "
+                                "place, which needs upper_off to be that prefix sum (re-make the handle with such a table)",
+                                who, i, uo[i], (unsigned long long)old_lists);
+                return LEANN_ERR_INVALID;
+            }
+            old_lists += levels[i];
+        }
+        if (old_lists > src->n_upper_lists) {
+            leann_set_error("%s: inconsistent level table: the levels name %llu upper lists, the index holds %llu", who,
+                            (unsigned long long)old_lists, (unsigned long long)src->n_upper_lists);
+            return LEANN_ERR_INVALID;
+        }
+    }
+    // every allocation of the result is a member of the handle: one leann_backend_close frees whatever a failure leaves behind
+    std::unique_ptr<leann_backend, void (*)(leann_backend *)> h(new leann_backend(), leann_backend_close);
+    h->kind = src->kind;
+    h->device = src->device;
+    h->key_offset = src->key_offset;
+    h->efc = src->efc;
+    h->alpha = src->alpha;
+    h->two_stage = src->two_stage;
+    h->nav_levels = src->nav_levels;
+    h->fixed_ef = src->fixed_ef;
+    h->g = src->g; // d, ld, M, M0, entry, max_level
+    h->g.X = rows; // borrowed
+    h->g.n = nt;
+    h->g.adj0 = nullptr; h->g.adjU = nullptr; h->g.upper_off = nullptr; h->g.norms = nullptr;
+    if (int rc = alloc_graph_arrays(h.get(), LEVEL_SEED, levels, n_old)) return rc;
+    if (n_old) {
+        if (hipMemcpy(h->store.adj0, src->g.adj0, n_old * h->g.M0 * 4, hipMemcpyDeviceToDevice) != hipSuccess ||
+            (old_lists && hipMemcpy(h->store.adjU, src->g.adjU, old_lists * h->g.M * 4, hipMemcpyDeviceToDevice) != hipSuccess)) {
+            leann_set_error("%s: copying the existing graph failed: %s", who, hipGetErrorString(hipGetLastError()));
+            return LEANN_ERR_DEVICE;
+        }
+    }
+    if (nt > n_old)
+        if (int rc = build_on_device(h.get(), n_old, 0, true)) return rc;
+    *out = h.release();
+    return LEANN_OK;
+}
+
 // BackendBuilder::add_to_index — src/backend/mod.rs:82-100, hnsw.rs:142-191
 extern "C" int leann_backend_add(int backend, const float *vectors, size_t n, size_t dims, size_t start_id,
                                  const char *index_path_stem) {
@@ -877,33 +951,21 @@ extern "C" int leann_backend_add(int backend, const float *vectors, size_t n, si
         leann_backend_close(old);
         return LEANN_ERR_DEVICE;
     }
-    leann_backend *h = new leann_backend();
-    h->kind = backend;
-    h->device = old->device;
-    h->key_offset = old->key_offset;
-    h->efc = old->efc;
-    h->alpha = old->alpha;
-    h->g = old->g;
-    h->g.X = dX; // borrowed
-    h->g.n = nt;
-    h->g.adj0 = nullptr; h->g.adjU = nullptr; h->g.upper_off = nullptr;
-    rc = alloc_graph_arrays(h, LEVEL_SEED);
     bool same_levels = true; // an index that did not come from this builder (leann_backend_from_arrays + save) has its own level
                              // table; so has a compacted one (compact.hip): its levels moved with the rows to new positions
-    if (rc == LEANN_OK && n_old) {
-        std::vector<uint8_t> la(n_old), lb(n_old);
-        if (hipMemcpy(la.data(), old->store.levels, n_old, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(lb.data(), h->store.levels, n_old, hipMemcpyDeviceToHost) != hipSuccess) {
+    if (n_old) {
+        std::vector<uint8_t> la(n_old);
+        if (hipMemcpy(la.data(), old->store.levels, n_old, hipMemcpyDeviceToHost) != hipSuccess) {
             leann_set_error("add_to_index: reading the level tables failed");
-            rc = LEANN_ERR_DEVICE;
-        } else {
-            same_levels = la == lb;
+            leann_backend_close(old);
+            return LEANN_ERR_DEVICE;
         }
+        for (size_t i = 0; i < n_old && same_levels; i++) same_levels = la[i] == (uint8_t)node_level(LEVEL_SEED, i, old->g.M);
     }
-    if (rc == LEANN_OK && !same_levels) { // foreign level table: rebuild over the concatenation (the pre-append behaviour)
+    leann_backend *h = nullptr;
+    if (!same_levels) { // foreign level table: rebuild over the concatenation (the pre-append behaviour; leann_backend_append continues)
         const size_t M = old->g.M, efc = old->efc;
         leann_backend_close(old);
-        leann_backend_close(h);
         rc = build_device_guarded(backend, dX, nt, dims, ld, M, efc, 0, 0, 0, &h, false);
         if (rc) return rc;
         if (tomb_n) rc = leann_internal_set_removed(h, tomb.data(), tomb_n);
@@ -911,21 +973,110 @@ extern "C" int leann_backend_add(int backend, const float *vectors, size_t n, si
         leann_backend_close(h);
         return rc;
     }
-    if (rc == LEANN_OK && n_old) {
-        if (hipMemcpy(h->store.adj0, old->g.adj0, n_old * h->g.M0 * 4, hipMemcpyDeviceToDevice) != hipSuccess ||
-            (old->n_upper_lists && hipMemcpy(h->store.adjU, old->g.adjU, old->n_upper_lists * h->g.M * 4,
-                                             hipMemcpyDeviceToDevice) != hipSuccess)) {
-            leann_set_error("add_to_index: copying the existing graph failed");
-            rc = LEANN_ERR_DEVICE;
-        }
+    try {
+        rc = continue_build(old, dX, nt, "add_to_index", &h); // h borrows dX
+    } catch (const std::exception &e) {
+        leann_set_error("add_to_index: %s", e.what());
+        rc = LEANN_ERR_DEVICE;
     }
-    const size_t old_lists = old->n_upper_lists;
     leann_backend_close(old);
-    if (rc == LEANN_OK && old_lists > h->n_upper_lists) { leann_set_error("add_to_index: inconsistent level table"); rc = LEANN_ERR_INVALID; }
-    if (rc == LEANN_OK && n) rc = build_on_device(h, n_old, 0);
-    if (rc == LEANN_OK && tomb_n) rc = leann_internal_set_removed(h, tomb.data(), tomb_n);
-    if (rc) { leann_backend_close(h); return rc; }
-    rc = leann_backend_save(h, index_path_stem);
+    if (rc) return rc;
+    if (tomb_n) rc = leann_internal_set_removed(h, tomb.data(), tomb_n);
+    if (rc == LEANN_OK) rc = leann_backend_save(h, index_path_stem);
     leann_backend_close(h);
     return rc;
+}
+
+// ---- leann_backend_append[_device]: a NEW handle that continues h's build with n more rows (include/leann_backend.h) ---------------
+namespace {
+// everything that needs no device, in the header's order; `ld`: the pitch of the new rows
+int append_check(const char *who, const leann_backend *h, const float *vectors, size_t n, size_t ld, leann_backend **out) {
+    if (!h || !out || (n && !vectors)) {
+        leann_set_error("%s: null argument (a handle, the address of the result and, for n > 0, the rows are needed)", who);
+        return LEANN_ERR_INVALID;
+    }
+    if (h->sharded) {
+        leann_set_error("%s: not available on a composite handle; append to its last shard (leann_backend_shard), then "
+                        "leann_sharded_from_handles over the shards", who);
+        return LEANN_ERR_UNSUPPORTED;
+    }
+    if (h->g.feat_h) {
+        leann_set_error("%s: this index stores no vectors (recompute-on); rebuild it from the encoder inputs (leann_recompute_build_index)", who);
+        return LEANN_ERR_UNSUPPORTED;
+    }
+    if (leann_internal_bf16(h)) {
+        leann_set_error("%s: this index stores bf16 rows and the builder reads f32 rows; rebuild it from all the rows (leann_backend_build_rows)", who);
+        return LEANN_ERR_UNSUPPORTED;
+    }
+    if (h->nav_levels) {
+        leann_set_error("%s: this Vamana index was built with entry layers (LEANN_VAMANA_NAV=1, an experiment knob); rebuild it "
+                        "(leann_backend_build_device) over all the rows", who);
+        return LEANN_ERR_UNSUPPORTED;
+    }
+    if (ld < h->g.d || (ld & 3)) {
+        leann_set_error("%s: ld = %zu; the rows need a pitch of at least %u floats (the index's dims) that is a multiple of 4", who, ld, h->g.d);
+        return LEANN_ERR_INVALID;
+    }
+    if ((uint64_t)h->g.n + n >= (1ull << 31)) {
+        leann_set_error("%s: %llu + %zu rows reach 2^31 positions; split the index into shards (leann_sharded_from_handles)", who,
+                        (unsigned long long)h->g.n, n);
+        return LEANN_ERR_INVALID;
+    }
+    return LEANN_OK;
+}
+
+// `vectors`: n rows at pitch `ld` floats, on the host (`on_host`) or on h's device
+int append_impl(const char *who, const leann_backend *hc, const float *vectors, size_t n, size_t ld, bool on_host, leann_backend **out) {
+    if (out) *out = nullptr;
+    if (int rc = append_check(who, hc, vectors, n, ld, out)) return rc;
+    if (int rc = leann_internal_check_device(hc->device)) return rc;
+    BCHECK(hipSetDevice(hc->device));
+    BCHECK(hipDeviceSynchronize());
+    leann_backend *src = const_cast<leann_backend *>(hc);
+    const size_t n_old = hc->g.n, nt = n_old + n, gld = hc->g.ld, d = hc->g.d;
+    std::vector<uint8_t> removed; // the source's removal state, snapshot under its lock (leann_backend_remove takes it)
+    size_t n_removed = 0;
+    {
+        std::lock_guard<std::mutex> lk(src->mu);
+        removed = src->removed;
+        n_removed = src->n_removed;
+    }
+    // rows: h's, byte for byte, then the new ones at h's pitch, zero padded
+    DeviceBuf<float> rows;
+    if (int rc = rows.alloc(std::max<size_t>(nt * gld, 4))) return rc;
+    if (n_old) BCHECK(hipMemcpy(rows, hc->g.X, n_old * gld * 4, hipMemcpyDeviceToDevice));
+    if (n) {
+        BCHECK(hipMemset(rows + n_old * gld, 0, n * gld * 4));
+        BCHECK(hipMemcpy2D(rows + n_old * gld, gld * 4, vectors, (on_host ? d : ld) * 4, d * 4, n, // (host rows are [n x dims], unpadded)
+                           on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice));
+    }
+    leann_backend *raw = nullptr;
+    if (int rc = continue_build(hc, rows, nt, who, &raw)) return rc;
+    std::unique_ptr<leann_backend, void (*)(leann_backend *)> h(raw, leann_backend_close);
+    h->store.rows = DeviceBuf<unsigned char>(std::move(rows)); // the result always owns its rows (g.X names this block already)
+    if (n_removed) { // removals are carried over: zero bits for the new rows, the live mask uploaded, n_pending counted on the device
+        removed.resize((nt + 7) / 8, 0);
+        if (int rc = leann_internal_set_removed(h.get(), removed.data(), n_removed)) return rc;
+    }
+    if (int rc = leann_internal_copy_coalescing(hc, h.get())) return rc;
+    leann_internal_sync_planes(h.get());
+    *out = h.release();
+    return LEANN_OK;
+}
+int append_guarded(const char *who, const leann_backend *h, const float *vectors, size_t n, size_t ld, bool on_host, leann_backend **out) {
+    try { // host-side bookkeeping allocates: nothing may be thrown across the C ABI
+        return append_impl(who, h, vectors, n, ld, on_host, out);
+    } catch (const std::exception &e) {
+        if (out) *out = nullptr;
+        leann_set_error("%s: %s", who, e.what());
+        return LEANN_ERR_DEVICE;
+    }
+}
+} // namespace
+
+extern "C" int leann_backend_append(const leann_backend *h, const float *vectors, size_t n, leann_backend **out) {
+    return append_guarded("leann_backend_append", h, vectors, n, h ? (size_t)((h->g.d + 3u) & ~3u) : 0, true, out);
+}
+extern "C" int leann_backend_append_device(const leann_backend *h, const float *d_vectors, size_t n, size_t ld, leann_backend **out) {
+    return append_guarded("leann_backend_append_device", h, d_vectors, n, ld, false, out);
 }

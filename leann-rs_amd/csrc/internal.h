@@ -59,7 +59,9 @@ struct GraphStore {
 };
 struct Coalescer;
 struct leann_sharded;
+inline std::atomic<uint64_t> leann_internal_handle_serial{0};
 struct leann_backend {
+    const uint64_t serial = ++leann_internal_handle_serial; // never reused: a registered filter names the handle it was made for by it
     leann_sharded *sharded = nullptr; // composite handle (shard.hip): searches fan out to the sub-indexes; g holds only n and d
     int kind = LEANN_BACKEND_HNSW, device = 0;
     GraphView g{};
@@ -123,6 +125,8 @@ int leann_internal_bf16_adopt_device(leann_backend *h, const float *d_src, size_
 int leann_internal_bf16_adopt_host(leann_backend *h, const float *f32_rows, const uint16_t *bf16_rows);
 int leann_internal_bf16_to_host(const leann_backend *h, size_t r0, size_t rows, uint16_t *out);
 int leann_internal_check_build_args(int backend, size_t graph_degree, size_t complexity); // build.hip: backend and list lengths
+// api.hip: dst takes src's coalescing configuration (automatic, configured with src's window and batch, or switched off)
+int leann_internal_copy_coalescing(const leann_backend *src, leann_backend *dst);
 // build.hip: leann_backend_build_device (rows borrowed) without cutting the row screen's planes
 int leann_internal_build_device_no_planes(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld, size_t graph_degree,
                                           size_t complexity, int device, uint64_t key_offset, leann_backend **out);
@@ -195,6 +199,7 @@ struct leann_filter {
     DeviceBuf<uint8_t> d_allow;
     ScratchLease<uint32_t> d_list; // held for the filter's lifetime
     uint64_t epoch = 0;         // the handle's removal_epoch when the filter was made (its bitmap holds live positions only)
+    uint64_t owner = 0;         // that handle's serial: a copy of it of the same length (leann_backend_append with n == 0) is another handle
     std::vector<leann_filter *> parts;
 };
 // How one search call filters — the same description for every entry point, for a plain handle and for a composite one.

@@ -515,6 +515,15 @@ inline std::vector<std::string> read_id_map(const std::string &index_path, const
     return ids;
 }
 
+// leann_backend_append: a new backend handle over h's positions plus the n rows of `rows` ([n x dims], keys continue the sequence);
+// `h` is left as it is.  Extending ids.txt, the passages and the meta file is the caller's (`leann update` is not part of this CLI).
+inline std::shared_ptr<leann_backend> append_rows(const leann_backend *h, const std::vector<float> &rows, size_t n) {
+    if (h && rows.size() != n * leann_backend_dims(h)) throw Error("append_rows: rows must hold n x dims floats");
+    leann_backend *out = nullptr;
+    check(leann_backend_append(h, n ? rows.data() : nullptr, n, &out));
+    return std::shared_ptr<leann_backend>(out, leann_backend_close);
+}
+
 class IndexSearcher {
   public:
     static IndexSearcher load(const std::string &index_path, const IndexMeta &meta, const char *device = "0") {
