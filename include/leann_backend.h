@@ -504,6 +504,69 @@ int leann_bm25_hybrid_rerank_device(const leann_bm25 *b, size_t nq, const uint32
                                     float alpha, int compat_polarity, size_t top_k,
                                     uint64_t *d_out_keys, float *d_out_scores, uint32_t *d_out_counts, void *stream);
 
+/* ---- metadata filters evaluated on the device (src/index/filter.rs:328-418) ---------------------------------------------
+ * A leann_meta is a columnar copy of the passages' metadata in HBM: one column per field (a dotted path, get_nested_value,
+ * filter.rs:376-388), per row a tag, a number and a string code.  The caller hands over each row's string (str_blob bytes
+ * [str_off[i], str_off[i + 1]) for a STRING row); the library builds the column's dictionary — the distinct strings sorted bytewise
+ * ascending, which is Rust's str::cmp order — and the codes.  The dictionary stays on the host, tags / numbers / codes go to the device.
+ * `valid`: optional bitmap of the rows whose metadata could be read; an invalid row passes no filter, not even Ne / NotIn / a filter
+ * on a missing field.  All arrays are host pointers, copied.  Every argument is validated before any device work (LEANN_ERR_INVALID
+ * with a message naming it): a tag above LEANN_META_OTHER, STRING rows without str_off, non-monotone str_off, a duplicate field,
+ * n >= 2^32.  A NUMBER row's num is the value's as_f64(); num == NULL with NUMBER rows -> LEANN_ERR_INVALID. */
+enum { LEANN_META_MISSING = 0, LEANN_META_NULL = 1, LEANN_META_FALSE = 2, LEANN_META_TRUE = 3, LEANN_META_NUMBER = 4,
+       LEANN_META_STRING = 5, LEANN_META_OTHER = 6 /* array / object */ };
+typedef struct leann_meta leann_meta;
+int leann_meta_create(size_t n, const uint8_t *valid, int device, leann_meta **out);
+int leann_meta_add_column(leann_meta *m, const char *field, const uint8_t *tag, const double *num, const char *str_blob,
+                          const uint64_t *str_off);
+size_t leann_meta_len(const leann_meta *m);
+int leann_meta_has_column(const leann_meta *m, const char *field); /* 1 / 0 */
+void leann_meta_close(leann_meta *m); /* when no evaluation is in flight */
+/* A filter is passed PARSED, as its tree in prefix order: a node, then its n_children subtrees.  The mini-language parser stays above
+ * the ABI.  A COND node names a field, one of the twelve FilterOp and a value; a LIST value (In / NotIn) holds `len` scalar values.
+ * Limits (csrc/meta_plan.h; LEANN_ERR_INVALID naming the limit): 32 conditions, nesting depth 8, 8 distinct fields, 2^20 32-bit words
+ * of number sets and dictionary bitsets per filter; a field without a column is refused by name. */
+enum { LEANN_META_COND = 0, LEANN_META_AND = 1, LEANN_META_OR = 2 };
+enum { LEANN_META_OP_EQ = 0, LEANN_META_OP_NE, LEANN_META_OP_GT, LEANN_META_OP_GTE, LEANN_META_OP_LT, LEANN_META_OP_LTE, LEANN_META_OP_IN,
+       LEANN_META_OP_NOT_IN, LEANN_META_OP_CONTAINS, LEANN_META_OP_STARTS_WITH, LEANN_META_OP_ENDS_WITH, LEANN_META_OP_EXISTS };
+enum { LEANN_META_VAL_NULL = 0, LEANN_META_VAL_BOOL = 1, LEANN_META_VAL_NUMBER = 2, LEANN_META_VAL_STRING = 3, LEANN_META_VAL_LIST = 4 };
+typedef struct leann_meta_value {
+    int32_t type;    /* LEANN_META_VAL_* */
+    int32_t boolean; /* BOOL */
+    double num;      /* NUMBER */
+    const char *str; /* STRING: len bytes, no terminator needed */
+    size_t len;      /* STRING: bytes; LIST: elements */
+    const struct leann_meta_value *list; /* LIST: elements of the scalar types (a nested list equals nothing) */
+} leann_meta_value;
+typedef struct leann_meta_node {
+    int32_t kind;        /* LEANN_META_COND / AND / OR */
+    uint32_t n_children; /* AND / OR */
+    const char *field;   /* COND */
+    int32_t op;          /* COND: LEANN_META_OP_* */
+    leann_meta_value value; /* COND */
+} leann_meta_node;
+/* MetadataFilter::matches for every row at once: bit i of bitmap = row i is valid and matches.  bitmap: host, ceil(n / 8) bytes, pad
+ * bits zero; n_allowed: optional.  One kernel (meta_eval_kernel) reads only the columns the filter names. */
+int leann_meta_eval(const leann_meta *m, const leann_meta_node *nodes, size_t n_nodes, uint8_t *bitmap, size_t *n_allowed);
+/* The same into device memory on the store's device: d_bitmap [ceil(n / 8)] = valid AND match AND d_and (optional device bitmap);
+ * no byte behind ceil(n / 8) is written.  d_n_allowed: optional device counter, set to the number of allowed rows.  The filter is
+ * compiled on the host, the work is enqueued on `stream` and the call returns without waiting for it.  A filter that needs number
+ * sets or dictionary bitsets (In / NotIn lists, Contains, EndsWith) copies them to the device from pageable host memory with a
+ * stream-ordered copy, so leann_meta_eval_device cannot be captured into a HIP graph; calls on one store and one stream reuse one
+ * scratch block, calls on different streams do not disturb each other.  The bitmap is an ordinary allow-bitmap: it feeds
+ * leann_backend_search_filtered[_exact]_batch_device, leann_scan_topk_device and leann_recompute_search_batch_device. */
+int leann_meta_eval_device(const leann_meta *m, const leann_meta_node *nodes, size_t n_nodes, const uint8_t *d_and, uint8_t *d_bitmap,
+                           uint32_t *d_n_allowed, void *stream);
+/* leann_backend_filter_create with the bitmap evaluated on the device (valid AND match, then the index's live mask) instead of
+ * uploaded: the resulting leann_filter is the one leann_backend_filter_create makes from the same bitmap.  leann_meta_len(m) !=
+ * leann_backend_len(h) or a store on another device than the handle's (a composite handle: its first device) -> LEANN_ERR_INVALID.
+ * A composite handle: evaluated once on the store's device, downloaded, then registered per shard as leann_backend_filter_create does. */
+int leann_backend_filter_create_meta(const leann_backend *h, const leann_meta *m, const leann_meta_node *nodes, size_t n_nodes,
+                                     leann_filter **out);
+/* 0 when LEANN_META_DEVICE=0 is set in the environment (read once, with the other knobs), else 1.  The library's own entry points do
+ * not look at it: it is for a host that keeps a per-passage loop beside the device path (host/leann_host.hpp) and wants one switch. */
+int leann_meta_device_enabled(void);
+
 /* ---- sharded indexes (the reference has no counterpart: IndexSearcher owns one Box<dyn BackendSearcher>,
  * src/index/searcher.rs:68) --------------------------------------------------------------------------------------------------
  * One process, G devices: the composite handle leann_backend_open returns for a device list, or built here from rows / handles.

@@ -25,6 +25,36 @@ pub struct LeannBm25 {
     _p: [u8; 0],
 }
 
+// Metadata filters evaluated on the device: a columnar copy of the passages' metadata and the parsed filter tree.
+#[repr(C)]
+pub struct LeannMeta {
+    _p: [u8; 0],
+}
+#[repr(C)]
+pub struct LeannFilter {
+    _p: [u8; 0],
+}
+/// leann_meta_value: type 0 null, 1 bool, 2 number, 3 string (`len` bytes at `str`), 4 list (`len` scalar values at `list`)
+#[repr(C)]
+pub struct LeannMetaValue {
+    pub type_: i32,
+    pub boolean: i32,
+    pub num: f64,
+    pub str_: *const c_char,
+    pub len: usize,
+    pub list: *const LeannMetaValue,
+}
+/// leann_meta_node, the MetadataFilter tree in prefix order: kind 0 condition (field, op = FilterOp in declaration order, value),
+/// 1 And / 2 Or with `n_children` subtrees behind it
+#[repr(C)]
+pub struct LeannMetaNode {
+    pub kind: i32,
+    pub n_children: u32,
+    pub field: *const c_char,
+    pub op: i32,
+    pub value: LeannMetaValue,
+}
+
 #[link(name = "leann_hip")]
 extern "C" {
     fn leann_last_error() -> *const c_char;
@@ -43,6 +73,32 @@ extern "C" {
                                            d_out_counts: *mut u32, stream: *mut std::ffi::c_void) -> c_int;
     #[allow(dead_code)]
     pub fn leann_bm25_close(b: *mut LeannBm25);
+    // Metadata filters on the device.  IndexSearcher::load would make the store lazily, beside the passage store: the first filter that
+    // names a field costs one pass over the passages extracting that field (tag 0 missing, 1 null, 2 false, 3 true, 4 number, 5 string,
+    // 6 array / object; the number as as_f64(); the string's bytes), `valid` = the passages whose metadata could be read.  After that,
+    // IndexSearcher::search_with_options (src/index/searcher.rs:123-210) flattens its MetadataFilter into LeannMetaNode and calls
+    // leann_backend_filter_create_meta instead of looping over the passages; the LeannFilter goes into the per-filter cache.
+    #[allow(dead_code)]
+    pub fn leann_meta_create(n: usize, valid: *const u8, device: c_int, out: *mut *mut LeannMeta) -> c_int;
+    #[allow(dead_code)]
+    pub fn leann_meta_add_column(m: *mut LeannMeta, field: *const c_char, tag: *const u8, num: *const f64, str_blob: *const c_char,
+                                 str_off: *const u64) -> c_int;
+    #[allow(dead_code)]
+    pub fn leann_meta_has_column(m: *const LeannMeta, field: *const c_char) -> c_int;
+    #[allow(dead_code)]
+    pub fn leann_meta_len(m: *const LeannMeta) -> usize;
+    #[allow(dead_code)]
+    pub fn leann_meta_close(m: *mut LeannMeta);
+    #[allow(dead_code)]
+    pub fn leann_meta_eval(m: *const LeannMeta, nodes: *const LeannMetaNode, n_nodes: usize, bitmap: *mut u8, n_allowed: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    pub fn leann_meta_eval_device(m: *const LeannMeta, nodes: *const LeannMetaNode, n_nodes: usize, d_and: *const u8, d_bitmap: *mut u8,
+                                  d_n_allowed: *mut u32, stream: *mut std::ffi::c_void) -> c_int;
+    #[allow(dead_code)]
+    pub fn leann_backend_filter_create_meta(h: *const LeannBackend, m: *const LeannMeta, nodes: *const LeannMetaNode, n_nodes: usize,
+                                            out: *mut *mut LeannFilter) -> c_int;
+    #[allow(dead_code)]
+    pub fn leann_backend_filter_free(f: *mut LeannFilter);
     fn leann_backend_open(stem: *const c_char, backend: c_int, dims: usize, device_spec: *const c_char,
                           out: *mut *mut LeannBackend) -> c_int;
     fn leann_backend_search(h: *const LeannBackend, query: *const f32, top_k: usize, complexity: usize,

@@ -8,6 +8,7 @@ from .backend import (BackendBuilder, BackendSearcher, BackendType, DiskAnnSearc
                       HnswSearcher, RowType, ShardedIndex, round_bf16)
 from .bm25 import Bm25Index  # noqa: F401
 from .device import DeviceArray, sync  # noqa: F401
+from .metadata import MetaColumns, parse_filter  # noqa: F401
 
 
 def __getattr__(name):  # torch is only needed for the multi-GPU helpers: import them lazily

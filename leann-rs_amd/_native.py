@@ -99,6 +99,16 @@ SIGNATURES = {
     "leann_backend_filter_count": (C.c_size_t, [vp]),
     "leann_backend_filter_free": (None, [vp]),
     "leann_backend_search_filter_batch": (C.c_int, [vp, f32p, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_int, u64p, f32p, u32p]),
+    "leann_meta_create": (C.c_int, [C.c_size_t, u8p, C.c_int, C.POINTER(vp)]),
+    "leann_meta_add_column": (C.c_int, [vp, C.c_char_p, u8p, C.POINTER(C.c_double), C.c_char_p, u64p]),
+    "leann_meta_len": (C.c_size_t, [vp]),
+    "leann_meta_device_enabled": (C.c_int, []),
+    "leann_meta_has_column": (C.c_int, [vp, C.c_char_p]),
+    "leann_meta_close": (None, [vp]),
+    # (the filter tree is an array of leann_meta_node: metadata.MetaNode)
+    "leann_meta_eval": (C.c_int, [vp, vp, C.c_size_t, u8p, C.POINTER(C.c_size_t)]),
+    "leann_meta_eval_device": (C.c_int, [vp, vp, C.c_size_t, vp, vp, vp, vp]),
+    "leann_backend_filter_create_meta": (C.c_int, [vp, vp, vp, C.c_size_t, C.POINTER(vp)]),
     "leann_backend_search_filtered_exact_batch_device": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp]),
     "leann_backend_search_filtered_batch_device": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t,
                                                             vp, vp, vp, vp, vp]),

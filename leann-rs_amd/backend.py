@@ -193,6 +193,15 @@ class BackendSearcher:
         N.check(N.lib().leann_backend_filter_create(self._h, _p(allow, u8p), C.byref(h)))
         return Filter(h)
 
+    def register_meta_filter(self, meta, flt):
+        """register_filter with the bitmap evaluated on the device from a metadata.MetaColumns store; `flt`: a filter tree or its text"""
+        from .metadata import encode_tree
+        nodes, k, keep = encode_tree(flt)
+        h = C.c_void_p()
+        N.check(N.lib().leann_backend_filter_create_meta(self._h, meta._h, nodes, k, C.byref(h)))
+        del keep
+        return Filter(h)
+
     def search_filter_batch(self, queries, top_k, complexity, flt, mode="auto"):
         """nq queries under a registered filter; mode: "walk" | "exact" | "auto" (the library chooses by the filter's selectivity)"""
         Q = np.ascontiguousarray(queries, np.float32)

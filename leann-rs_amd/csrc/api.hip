@@ -71,6 +71,7 @@ static LeannKnobs *read_knobs_from_env() {
     if (const char *e = getenv("LEANN_ROW_SCREEN")) k->row_screen = (!strcmp(e, "0") || !strcasecmp(e, "off")) ? 0 : (!strcmp(e, "1") || !strcasecmp(e, "on")) ? 2 : 1;
     if (const char *e = getenv("LEANN_COALESCE")) k->coalesce_off = !strcmp(e, "off") || !strcmp(e, "0");
     if (const char *e = getenv("LEANN_STAMP_BUF")) k->stamp_buf = strtoull(e, nullptr, 0);
+    if (const char *e = getenv("LEANN_META_DEVICE")) k->meta_device = strcmp(e, "0") != 0;
     return k;
 }
 static std::atomic<const LeannKnobs *> g_knobs{nullptr};
@@ -427,6 +428,41 @@ static int search_filtered_batch_host(const leann_backend *hc, const float *quer
                                       const uint8_t *allow, size_t allow_stride, uint64_t *keys, float *dists, uint32_t *counts, int mode,
                                       const leann_filter *flt = nullptr);
 
+// The two ends of registering a filter on a plain handle, shared by leann_backend_filter_create (the bitmap is uploaded in between) and
+// leann_backend_filter_create_meta (meta.hip: it is evaluated there).  begin: h's device current, a filter with room for the bitmap.
+int leann_internal_filter_begin(const leann_backend *hc, const char *who, leann_filter **out) {
+    *out = nullptr;
+    if (hc->g.n >= (1ull << 32)) {
+        leann_set_error("%s: the index has 2^32 rows or more", who);
+        return LEANN_ERR_INVALID;
+    }
+    HIP_CHECK_RET(hipSetDevice(hc->device));
+    leann_filter *f = new leann_filter();
+    f->device = hc->device;
+    f->n = hc->g.n;
+    const size_t nbytes = std::max<size_t>((f->n + 7) / 8, 1);
+    if (f->d_allow.alloc(nbytes)) {
+        leann_set_error("%s: device allocation of %zu bytes failed", who, nbytes);
+        delete f;
+        return LEANN_ERR_DEVICE;
+    }
+    *out = f;
+    return LEANN_OK;
+}
+// finish: f->d_allow holds the bitmap.  Epoch and owner, live mask, list of allowed positions; on failure f is deleted.
+int leann_internal_filter_finish(const leann_backend *hc, leann_filter *f, leann_filter **out) {
+    f->epoch = hc->removal_epoch;
+    f->owner = hc->serial;
+    int rc = leann_internal_and_live_inplace(hc, f->d_allow); // removed positions are never allowed: the bitmap and the list hold live ones only
+    if (rc == LEANN_OK && f->n) rc = leann_internal_compact_allow(f->d_allow, f->n, &f->d_list, &f->n_allowed, nullptr);
+    if (rc != LEANN_OK) {
+        delete f;
+        return rc;
+    }
+    *out = f;
+    return LEANN_OK;
+}
+
 // Registered filters: a server that answers many queries under the same metadata filter uploads and compacts the bitmap once
 // (the host-pointer calls above re-send N/8 bytes and re-compact them for every query: 1.25 MB at 10M rows).
 extern "C" int leann_backend_filter_create(const leann_backend *hc, const uint8_t *allow, leann_filter **out) {
@@ -456,30 +492,14 @@ extern "C" int leann_backend_filter_create(const leann_backend *hc, const uint8_
         *out = f;
         return LEANN_OK;
     }
-    if (hc->g.n >= (1ull << 32)) {
-        leann_set_error("leann_backend_filter_create: the index has 2^32 rows or more");
-        return LEANN_ERR_INVALID;
-    }
-    HIP_CHECK_RET(hipSetDevice(hc->device));
-    leann_filter *f = new leann_filter();
-    f->device = hc->device;
-    f->n = hc->g.n;
-    const size_t nbytes = std::max<size_t>((f->n + 7) / 8, 1);
-    if (f->d_allow.alloc(nbytes) || hipMemcpy(f->d_allow, allow, (f->n + 7) / 8, hipMemcpyHostToDevice) != hipSuccess) {
-        leann_set_error("leann_backend_filter_create: device allocation / copy of %zu bytes failed", nbytes);
+    leann_filter *f = nullptr;
+    if (int rc = leann_internal_filter_begin(hc, "leann_backend_filter_create", &f)) return rc;
+    if (hipMemcpy(f->d_allow, allow, (f->n + 7) / 8, hipMemcpyHostToDevice) != hipSuccess) {
+        leann_set_error("leann_backend_filter_create: copy of %zu bytes to the device failed", (f->n + 7) / 8);
         delete f;
         return LEANN_ERR_DEVICE;
     }
-    f->epoch = hc->removal_epoch;
-    f->owner = hc->serial;
-    int rc = leann_internal_and_live_inplace(hc, f->d_allow); // removed positions are never allowed: the bitmap and the list hold live ones only
-    if (rc == LEANN_OK && f->n) rc = leann_internal_compact_allow(f->d_allow, f->n, &f->d_list, &f->n_allowed, nullptr);
-    if (rc != LEANN_OK) {
-        delete f;
-        return rc;
-    }
-    *out = f;
-    return LEANN_OK;
+    return leann_internal_filter_finish(hc, f, out);
 }
 extern "C" size_t leann_backend_filter_count(const leann_filter *f) { return f ? f->n_allowed : 0; }
 extern "C" void leann_backend_filter_free(leann_filter *f) {

@@ -44,6 +44,8 @@ struct LeannKnobs {
     bool hnsw_reference_ef = false;  // LEANN_HNSW_REFERENCE_EF=1: HNSW handles opened from now on search with ef = 64 whatever
                                      // `complexity` says, as the reference does (hnsw.rs:49 expansion_search: 64, :83 _complexity unused)
     unsigned long long stamp_buf = 0; // LEANN_STAMP_BUF (diagnostic builds only)
+    bool meta_device = true;         // LEANN_META_DEVICE=0: a host that evaluates metadata filters on the device (the C++ IndexSearcher)
+                                     // takes its per-passage loop instead (A/B runs; leann_meta_device_enabled)
 };
 const LeannKnobs &leann_knobs();
 extern "C" void leann_debug_reload_env(void);
@@ -202,6 +204,11 @@ struct leann_filter {
     uint64_t owner = 0;         // that handle's serial: a copy of it of the same length (leann_backend_append with n == 0) is another handle
     std::vector<leann_filter *> parts;
 };
+// api.hip: the two ends of registering a filter on a plain handle (leann_backend_filter_create uploads the bitmap in between,
+// leann_backend_filter_create_meta evaluates it there).  _begin: h's device current, *out a filter with room for the bitmap.  _finish:
+// epoch, owner, live mask, list of allowed positions; on failure f is deleted and *out stays null.
+int leann_internal_filter_begin(const leann_backend *h, const char *who, leann_filter **out);
+int leann_internal_filter_finish(const leann_backend *h, leann_filter *f, leann_filter **out);
 // How one search call filters — the same description for every entry point, for a plain handle and for a composite one.
 // Nothing set: no filter.  d_allow: a device bitmap over the handle's positions (a composite handle: GLOBAL positions on its first
 // device, sliced per shard at byte boundaries); allow_stride == 0: one bitmap for the batch, else bytes from one query's to the next.

@@ -15,10 +15,12 @@
 #include "json.hpp"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <fstream>
 #include <limits>
 #include <map>
@@ -339,6 +341,14 @@ class MetadataFilter {
         }
         return false;
     }
+
+    // read access to the tree (the device path walks it: IndexSearcher::device_filter)
+    bool is_condition() const { return kind_ == Cond; }
+    bool is_and() const { return kind_ == And; }
+    const std::string &field() const { return field_; }
+    Op op() const { return op_; }
+    const lj::Value &value() const { return value_; }
+    const std::vector<MetadataFilter> &children() const { return children_; }
 
   private:
     enum Kind { Cond, And, Or } kind_ = Cond;
@@ -783,6 +793,16 @@ class IndexSearcher {
             if (it != filters_->end()) return it->second;
         }
         const size_t n = leann_backend_len(backend_.get());
+        leann_filter *raw = nullptr;
+        const auto t0 = std::chrono::steady_clock::now();
+        auto ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+        if (!leann_meta_device_enabled()) {
+            if (host_log_debug()) fprintf(stderr, "DEBUG leann: filter evaluated on the host, passage by passage (LEANN_META_DEVICE=0)\n");
+        } else if (meta_filter(f, n, &raw)) {
+            if (host_log_debug())
+                fprintf(stderr, "DEBUG leann: filter evaluated on the device from %zu metadata columns, registered in %.3f ms\n", meta_->fields.size(), ms());
+            return remember(key, raw);
+        } else if (host_log_debug()) fprintf(stderr, "DEBUG leann: filter evaluated on the host, passage by passage: %s\n", leann_last_error());
         std::vector<uint8_t> bm((n + 7) / 8 + 1, 0);
         for (size_t i = 0; i < n; i++) {
             std::string id = i < id_map_.size() ? id_map_[i] : std::to_string(i);
@@ -790,14 +810,124 @@ class IndexSearcher {
                 if (f.matches(passages_.get(id).metadata)) bm[i >> 3] |= (uint8_t)(1u << (i & 7));
             } catch (...) {} // unreadable passage: never returned (the post-filter path skips it with a warning too)
         }
-        leann_filter *raw = nullptr;
         check(leann_backend_filter_create(backend_.get(), bm.data(), &raw));
+        if (host_log_debug()) fprintf(stderr, "DEBUG leann: host pass over %zu passages, filter registered in %.3f ms\n", n, ms());
+        return remember(key, raw);
+    }
+    RegisteredFilter remember(const std::string &key, leann_filter *raw) const {
         RegisteredFilter rf;
         rf.handle = std::shared_ptr<leann_filter>(raw, [](leann_filter *p) { leann_backend_filter_free(p); });
         rf.allowed = leann_backend_filter_count(raw);
         if (filters_->size() >= 16) filters_->clear();
         return (*filters_)[key.empty() ? std::string("\x01anon") : key] = std::move(rf);
     }
+    // The device path of device_filter (include/leann_backend.h "metadata filters evaluated on the device"): the open index keeps one
+    // columnar store; a field gets its column the first time a filter names it, by ONE pass over the passages that extracts the fields
+    // still missing (the store's own first pass also records which passages could be read); after that a new filter costs a compile
+    // and a kernel, no passage is touched.  false (leann_last_error says why): the store could not be made or the filter exceeds a
+    // limit of the compiler — the caller falls back to the per-passage loop.  Called under bm25_mu_.
+    struct MetaStore {
+        std::shared_ptr<leann_meta> handle;
+        bool failed = false;
+        std::vector<std::string> fields;
+    };
+    static const lj::Value *nested(const lj::Value &metadata, const std::string &path) { // get_nested_value, filter.rs:376-388
+        const lj::Value *v = &metadata;
+        size_t start = 0;
+        for (;;) {
+            const size_t dot = path.find('.', start);
+            v = v->get(path.substr(start, dot == std::string::npos ? std::string::npos : dot - start));
+            if (!v || dot == std::string::npos) return v;
+            start = dot + 1;
+        }
+    }
+    static void collect_fields(const MetadataFilter &f, std::vector<std::string> &out) {
+        if (!f.is_condition()) { for (auto &c : f.children()) collect_fields(c, out); return; }
+        if (std::find(out.begin(), out.end(), f.field()) == out.end()) out.push_back(f.field());
+    }
+    static leann_meta_value meta_value(const lj::Value &v, std::deque<std::vector<leann_meta_value>> &lists, bool in_list = false) {
+        leann_meta_value out{};
+        switch (v.kind) {
+        case lj::Value::Null: out.type = LEANN_META_VAL_NULL; break;
+        case lj::Value::Bool: out.type = LEANN_META_VAL_BOOL; out.boolean = v.b; break;
+        case lj::Value::Int:
+        case lj::Value::Float: out.type = LEANN_META_VAL_NUMBER; out.num = v.as_f64(); break;
+        case lj::Value::String: out.type = LEANN_META_VAL_STRING; out.str = v.s.data(); out.len = v.s.size(); break;
+        default: // an array; an element that is itself an array (or an object) equals nothing: an empty list
+            out.type = LEANN_META_VAL_LIST;
+            if (!in_list && v.kind == lj::Value::Arr) {
+                lists.emplace_back();
+                std::vector<leann_meta_value> &l = lists.back();
+                for (auto &x : *v.a) l.push_back(meta_value(x, lists, true));
+                out.len = l.size();
+                out.list = l.data();
+            }
+        }
+        return out;
+    }
+    static void flatten(const MetadataFilter &f, std::vector<leann_meta_node> &nodes, std::deque<std::vector<leann_meta_value>> &lists) {
+        leann_meta_node nd{};
+        if (f.is_condition()) {
+            nd.kind = LEANN_META_COND;
+            nd.field = f.field().c_str();
+            nd.op = (int32_t)f.op(); // MetadataFilter::Op is in the order of LEANN_META_OP_*
+            nd.value = meta_value(f.value(), lists);
+            nodes.push_back(nd);
+            return;
+        }
+        nd.kind = f.is_and() ? LEANN_META_AND : LEANN_META_OR;
+        nd.n_children = (uint32_t)f.children().size();
+        nodes.push_back(nd);
+        for (auto &c : f.children()) flatten(c, nodes, lists);
+    }
+    bool meta_filter(const MetadataFilter &f, size_t n, leann_filter **out) const {
+        if (meta_->failed) return false;
+        std::vector<std::string> fields, missing;
+        collect_fields(f, fields);
+        for (auto &fl : fields)
+            if (std::find(meta_->fields.begin(), meta_->fields.end(), fl) == meta_->fields.end()) missing.push_back(fl);
+        const bool first = !meta_->handle;
+        if (first || !missing.empty()) { // one pass over the passages: the missing fields' columns, and readability the first time
+            std::vector<uint8_t> valid((n + 7) / 8 + 1, 0);
+            std::vector<std::vector<uint8_t>> tag(missing.size(), std::vector<uint8_t>(n, LEANN_META_MISSING));
+            std::vector<std::vector<double>> num(missing.size(), std::vector<double>(n, 0.0));
+            std::vector<std::string> blob(missing.size());
+            std::vector<std::vector<uint64_t>> off(missing.size(), std::vector<uint64_t>(n + 1, 0));
+            for (size_t i = 0; i < n; i++) {
+                const std::string id = i < id_map_.size() ? id_map_[i] : std::to_string(i);
+                try {
+                    const lj::Value metadata = passages_.get(id).metadata;
+                    valid[i >> 3] |= (uint8_t)(1u << (i & 7));
+                    for (size_t c = 0; c < missing.size(); c++) {
+                        const lj::Value *v = nested(metadata, missing[c]);
+                        uint8_t t = LEANN_META_OTHER;
+                        if (!v) t = LEANN_META_MISSING;
+                        else if (v->is_null()) t = LEANN_META_NULL;
+                        else if (v->kind == lj::Value::Bool) t = v->b ? LEANN_META_TRUE : LEANN_META_FALSE;
+                        else if (v->is_number()) { t = LEANN_META_NUMBER; num[c][i] = v->as_f64(); }
+                        else if (v->is_string()) { t = LEANN_META_STRING; blob[c] += v->s; }
+                        tag[c][i] = t;
+                    }
+                } catch (...) {} // unreadable passage: invalid, passes no filter
+                for (size_t c = 0; c < missing.size(); c++) off[c][i + 1] = blob[c].size();
+            }
+            if (first) {
+                leann_meta *m = nullptr;
+                if (leann_meta_create(n, valid.data(), bm25_device_id_, &m) != LEANN_OK) { meta_->failed = true; return false; }
+                meta_->handle.reset(m, leann_meta_close);
+            }
+            for (size_t c = 0; c < missing.size(); c++) {
+                if (leann_meta_add_column(meta_->handle.get(), missing[c].c_str(), tag[c].data(), num[c].data(), blob[c].data(), off[c].data()) != LEANN_OK)
+                    return false;
+                meta_->fields.push_back(missing[c]);
+            }
+        }
+        std::vector<leann_meta_node> nodes;
+        std::deque<std::vector<leann_meta_value>> lists;
+        flatten(f, nodes, lists);
+        return leann_backend_filter_create_meta(backend_.get(), meta_->handle.get(), nodes.data(), nodes.size(), out) == LEANN_OK;
+    }
+    std::shared_ptr<MetaStore> meta_ = std::make_shared<MetaStore>();
     PassageStore passages_;
     std::shared_ptr<leann_backend> backend_;
     std::vector<std::string> id_map_;
