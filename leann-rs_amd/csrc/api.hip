@@ -1,5 +1,6 @@
-// api.hip — C ABI (include/leann_backend.h) over the gfx950 kernels: handle lifetime, index files,
-// host<->HBM staging, kernel dispatch.  No CPU fallback exists in this library by design: every
+// api.hip — C ABI (include/leann_backend.h) over the gfx950 kernels: errors, logging and knobs, raw device helpers, closing a
+// handle, the search entry points with their host<->HBM staging, kernel dispatch, request coalescing, registered filters, graph export.
+// (Making a handle: handle.hip; index files: indexfile.hip.)  No CPU fallback exists in this library by design: every
 // search / scan / build entry point runs HIP kernels or returns LEANN_ERR_DEVICE.
 #include "common.cuh"
 #include "search.cuh"
@@ -902,141 +903,6 @@ extern "C" int leann_backend_search_filtered(const leann_backend *hc, const floa
     int rc = leann_backend_search_filtered_batch(hc, query, 1, top_k, complexity, allow, 0, keys, dists, &cnt);
     *n_out = cnt;
     return rc;
-}
-
-// ---- in-memory construction from host arrays ----------------------------------------------------------
-// Every array is checked against n BEFORE anything is uploaded: the traversal kernel indexes rows by neighbour id, upper lists by
-// upper_off[node] + level - 1 and trusts both (search.cuh), so one bad entry in an index file would be an out-of-bounds read on the GPU.
-static const char *validate_graph(size_t n, uint32_t M, uint32_t M0, uint32_t max_level, uint32_t entry, const uint8_t *levels,
-                                  const uint32_t *upper_off, const uint32_t *adj0, const uint32_t *adjU, size_t n_upper_lists) {
-    if (M == 0 || M0 == 0 || M > 128 || M0 > 128) return "graph degree outside [1, 128]";
-    if (max_level > 15) return "max_level > 15";
-    if (n == 0) return nullptr;
-    if (entry >= n) return "entry point is not a row of the index";
-    if (!levels && (max_level != 0 || n_upper_lists != 0)) return "upper levels without a level table";
-    if (n_upper_lists && !adjU) return "upper lists missing";
-    if (levels && levels[entry] < max_level) return "the entry point does not reach max_level";
-    for (size_t v = 0; v < n; v++) {
-        const uint32_t lv = levels ? levels[v] : 0;
-        if (lv > 15) return "node level > 15";
-        if (lv && (size_t)upper_off[v] + lv > n_upper_lists) return "upper_off + level runs past the upper lists";
-        const uint32_t *l0 = adj0 + v * (size_t)M0;
-        for (uint32_t j = 0; j < M0; j++)
-            if (l0[j] != LEANN_EMPTY && l0[j] >= n) return "level-0 neighbour id >= n";
-        for (uint32_t l = 1; l <= lv; l++) {
-            const uint32_t *lu = adjU + ((size_t)upper_off[v] + l - 1) * M;
-            for (uint32_t j = 0; j < M; j++) {
-                const uint32_t e = lu[j];
-                if (e == LEANN_EMPTY) continue;
-                if (e >= n) return "upper-level neighbour id >= n";
-                if (levels[e] < l) return "upper-level neighbour does not exist on that level";
-            }
-        }
-    }
-    return nullptr;
-}
-
-int leann_internal_from_host(int backend, size_t n, size_t dims, uint32_t M, uint32_t M0, uint32_t max_level, uint32_t entry,
-                             const uint8_t *levels, const uint32_t *upper_off, const uint32_t *adj0, const uint32_t *adjU,
-                             size_t n_upper_lists, const float *vectors, const unsigned char *feat_rows, uint32_t feat_h, uint32_t row_bytes,
-                             const float *Wf32, int device, uint64_t key_offset, leann_backend **out, int row_type, const uint16_t *bf16_rows,
-                             const float *d_f32_rows, size_t d_f32_ld) {
-    const bool feat = feat_rows != nullptr, bf16 = row_type == LEANN_ROWS_BF16;
-    if (row_type != LEANN_ROWS_F32 && row_type != LEANN_ROWS_BF16) {
-        leann_set_error("leann_backend_from_arrays: unknown row type %d (LEANN_ROWS_F32 or LEANN_ROWS_BF16)", row_type);
-        return LEANN_ERR_INVALID;
-    }
-    if ((bf16 && (feat || (vectors != nullptr) + (bf16_rows != nullptr) + (d_f32_rows != nullptr) > 1 || (d_f32_rows && d_f32_ld < dims))) ||
-        (!bf16 && (bf16_rows || d_f32_rows))) {
-        leann_set_error("leann_backend_from_arrays: invalid arguments");
-        return LEANN_ERR_INVALID;
-    }
-    if (!out || dims == 0 || dims > 4096 || n >= (1ull << 31) || (n && ((!vectors && !feat && !bf16_rows && !d_f32_rows) || !adj0 || !upper_off)) ||
-        (backend != LEANN_BACKEND_HNSW && backend != LEANN_BACKEND_DISKANN) ||
-        (feat && (!Wf32 || feat_h == 0 || (feat_h & 3) || feat_h > 1024 || row_bytes < 2 * feat_h + 4 || (row_bytes & 7)))) {
-        leann_set_error("leann_backend_from_arrays: invalid arguments");
-        return LEANN_ERR_INVALID;
-    }
-    if (const char *why = validate_graph(n, M, M0, max_level, entry, levels, upper_off, adj0, adjU, n_upper_lists)) {
-        leann_set_error("leann_backend_from_arrays: inconsistent graph arrays: %s", why);
-        return LEANN_ERR_FORMAT;
-    }
-    if (int rc = leann_internal_check_device(device)) return rc;
-    HIP_CHECK_RET(hipSetDevice(device));
-    leann_backend *h = new leann_backend();
-    h->kind = backend;
-    h->device = device;
-    h->key_offset = key_offset;
-    h->g.n = n;
-    h->g.d = (uint32_t)dims;
-    h->g.ld = (uint32_t)((dims + 3) & ~(size_t)3);
-    h->g.M = M;
-    h->g.M0 = M0;
-    h->g.max_level = max_level;
-    h->g.entry = entry;
-    h->n_upper_lists = n_upper_lists;
-    if (const char *e = getenv("LEANN_VAMANA_TWO_STAGE")) h->two_stage = strcmp(e, "0") != 0; // the prune form consolidation repairs with
-    // every allocation is a member of the handle, so that one leann_backend_close frees whatever a failure leaves behind
-    auto fail = [&](const char *what) { // (null: a failed allocation, which has set the message)
-        if (what) leann_set_error("leann_backend_from_arrays: %s failed: %s", what, hipGetErrorString(hipGetLastError()));
-        leann_backend_close(h);
-        return LEANN_ERR_DEVICE;
-    };
-    const size_t nn = std::max<size_t>(n, 1), nu = std::max<size_t>(n_upper_lists, 1), ld = h->g.ld;
-    GraphStore &st = h->store;
-    if (feat) {
-        h->g.feat_h = feat_h;
-        if (feat_h == 256) { // split device layout (GraphView::norms): 512-B rows of whole lines, norms beside them
-            h->g.row_bytes = 512;
-            if (st.rows.alloc(nn * 512) || st.norms.alloc(nn)) return fail(nullptr);
-            h->g.norms = st.norms;
-            const size_t slab = (size_t)1 << 20; // de-interleaved on the host, uploaded contiguously
-            std::vector<unsigned char> fr(std::min(slab, nn) * 512);
-            std::vector<float> nr(std::min(slab, nn));
-            for (size_t s0 = 0; s0 < n; s0 += slab) {
-                const size_t m = std::min(slab, n - s0);
-                for (size_t i = 0; i < m; i++) {
-                    memcpy(fr.data() + i * 512, feat_rows + (s0 + i) * row_bytes, 512);
-                    memcpy(&nr[i], feat_rows + (s0 + i) * row_bytes + 512, 4);
-                }
-                if (hipMemcpy(st.rows + s0 * 512, fr.data(), m * 512, hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(st.norms + s0, nr.data(), m * 4, hipMemcpyHostToDevice) != hipSuccess)
-                    return fail("upload of the feature rows");
-            }
-        } else {
-            h->g.row_bytes = row_bytes;
-            if (st.rows.alloc(nn * row_bytes)) return fail(nullptr);
-            if (n && hipMemcpy(st.rows, feat_rows, n * (size_t)row_bytes, hipMemcpyHostToDevice) != hipSuccess) return fail("upload of the feature rows");
-        }
-        h->g.X = reinterpret_cast<const float *>(st.rows.p);
-        if (h->Wf32.alloc((size_t)feat_h * dims)) return fail(nullptr);
-        if (hipMemcpy(h->Wf32, Wf32, (size_t)feat_h * dims * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("upload of the weights");
-    } else if (bf16) {
-        const int rc = d_f32_rows ? leann_internal_bf16_adopt_device(h, d_f32_rows, d_f32_ld) : leann_internal_bf16_adopt_host(h, vectors, bf16_rows);
-        if (rc) { leann_backend_close(h); return rc; }
-    } else {
-        if (st.rows.alloc(std::max<size_t>(n * ld, 4) * 4)) return fail(nullptr);
-        h->g.X = reinterpret_cast<const float *>(st.rows.p);
-        if (n) {
-            if (ld == dims) { if (hipMemcpy(st.rows, vectors, n * dims * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("upload of the rows"); }
-            else if (hipMemset(st.rows, 0, n * ld * 4) != hipSuccess ||
-                     hipMemcpy2D(st.rows, ld * 4, vectors, dims * 4, dims * 4, n, hipMemcpyHostToDevice) != hipSuccess) return fail("upload of the rows");
-        }
-    }
-    if (st.adj0.alloc(nn * M0) || st.adjU.alloc(nu * M) || st.upper_off.alloc(nn) || st.levels.alloc(nn)) return fail(nullptr);
-    h->g.adj0 = st.adj0; h->g.adjU = st.adjU; h->g.upper_off = st.upper_off;
-    if (hipMemset(st.adjU, 0xFF, nu * M * 4) != hipSuccess) return fail("hipMemset");
-    if (n) {
-        if (hipMemcpy(st.adj0, adj0, n * M0 * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(st.upper_off, upper_off, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            (levels ? hipMemcpy(st.levels, levels, n, hipMemcpyHostToDevice) : hipMemset(st.levels, 0, n)) != hipSuccess ||
-            (n_upper_lists && hipMemcpy(st.adjU, adjU, n_upper_lists * M * 4, hipMemcpyHostToDevice) != hipSuccess))
-            return fail("upload of the graph arrays");
-    }
-    if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize"); // the fills above are null-stream work; searches run on non-blocking streams
-    leann_internal_sync_planes(h);
-    *out = h;
-    return LEANN_OK;
 }
 
 extern "C" int leann_backend_from_arrays(int backend, const float *vectors, size_t n, size_t dims, uint32_t M,

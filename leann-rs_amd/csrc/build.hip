@@ -688,25 +688,13 @@ static int build_on_device(leann_backend *h, size_t n_existing, size_t bmax_hint
 // them is the caller's: the levels of an existing graph), upper_off is the exclusive prefix sum of the whole table
 static int alloc_graph_arrays(leann_backend *h, uint64_t level_seed, std::vector<uint8_t> &levels, size_t hash_from) {
     const size_t n = h->g.n, nn = std::max<size_t>(n, 1);
+    if (h->kind == LEANN_BACKEND_HNSW || h->nav_levels)
+        for (size_t i = hash_from; i < n; i++) levels[i] = (uint8_t)node_level(level_seed, i, h->g.M);
     std::vector<uint32_t> uo(nn, 0);
-    uint64_t nu = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (i >= hash_from) levels[i] = (h->kind == LEANN_BACKEND_HNSW || h->nav_levels) ? (uint8_t)node_level(level_seed, i, h->g.M) : 0;
-        uo[i] = (uint32_t)nu;
-        nu += levels[i];
-    }
-    h->n_upper_lists = nu;
-    DeviceBuf<uint32_t> adj0, adjU, duo; // this call's own until the last lines: an earlier return frees them
-    DeviceBuf<uint8_t> dlv;
-    if (adj0.alloc(nn * h->g.M0) || adjU.alloc(std::max<uint64_t>(nu, 1) * h->g.M) || duo.alloc(nn) || dlv.alloc(nn)) return LEANN_ERR_DEVICE;
-    BCHECK(hipMemset(adj0, 0xFF, nn * h->g.M0 * 4));
-    BCHECK(hipMemset(adjU, 0xFF, std::max<uint64_t>(nu, 1) * h->g.M * 4));
-    BCHECK(hipMemcpy(duo, uo.data(), nn * 4, hipMemcpyHostToDevice));
-    BCHECK(hipMemcpy(dlv, levels.data(), nn, hipMemcpyHostToDevice));
-    h->g.adj0 = h->store.adj0 = std::move(adj0);
-    h->g.adjU = h->store.adjU = std::move(adjU);
-    h->g.upper_off = h->store.upper_off = std::move(duo);
-    h->store.levels = std::move(dlv);
+    if (int rc = leann_internal_alloc_graph_lists(h, leann_internal_upper_offsets(levels.data(), n, uo.data()))) return rc;
+    BCHECK(hipMemset(h->store.adj0, 0xFF, nn * h->g.M0 * 4)); // the builder's lists start empty
+    BCHECK(hipMemcpy(h->store.upper_off, uo.data(), nn * 4, hipMemcpyHostToDevice));
+    BCHECK(hipMemcpy(h->store.levels, levels.data(), nn, hipMemcpyHostToDevice));
     return LEANN_OK;
 }
 static int alloc_graph_arrays(leann_backend *h, uint64_t level_seed) { // a fresh build: every level is the hash
@@ -718,8 +706,13 @@ static constexpr uint64_t LEVEL_SEED = 0x5EED0003ull;
 
 static int build_device_impl(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld, size_t graph_degree, size_t complexity,
                              int device, uint64_t key_offset, int take_copy, leann_backend **out, bool planes);
-// Lists hold at most 128 ids: HNSW graph_degree M in [2, 64] (level 0 keeps 2 M), DiskANN R in [2, 128].  Checked before any device work.
-static int check_degree(int backend, size_t graph_degree, size_t complexity) {
+// The backend, and its list lengths: lists hold at most 128 ids, HNSW graph_degree M in [2, 64] (level 0 keeps 2 M), DiskANN R in
+// [2, 128].  Every build entry point checks them here, before any device work.
+int leann_internal_check_build_args(int backend, size_t graph_degree, size_t complexity) {
+    if (backend != LEANN_BACKEND_HNSW && backend != LEANN_BACKEND_DISKANN) {
+        leann_set_error("Unknown backend: %d", backend);
+        return LEANN_ERR_INVALID;
+    }
     const size_t maxdeg = backend == LEANN_BACKEND_HNSW ? 64 : 128;
     if (graph_degree < 2 || graph_degree > maxdeg || complexity < 1) {
         leann_set_error("build: graph_degree must be in [2, %zu] (%s) and complexity >= 1 (got %zu, %zu)", maxdeg,
@@ -727,13 +720,6 @@ static int check_degree(int backend, size_t graph_degree, size_t complexity) {
         return LEANN_ERR_INVALID;
     }
     return LEANN_OK;
-}
-int leann_internal_check_build_args(int backend, size_t graph_degree, size_t complexity) { // for rows_bf16.hip: before any device work
-    if (backend != LEANN_BACKEND_HNSW && backend != LEANN_BACKEND_DISKANN) {
-        leann_set_error("Unknown backend: %d", backend);
-        return LEANN_ERR_INVALID;
-    }
-    return check_degree(backend, graph_degree, complexity);
 }
 // `planes`: cut the row screen's split planes (planes.hip) for the new handle — not for one that is only saved and closed again
 static int build_device_guarded(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld, size_t graph_degree, size_t complexity,
@@ -762,11 +748,7 @@ static int build_device_impl(int backend, const float *d_vectors, size_t n, size
         leann_set_error("leann_backend_build_device: invalid arguments (n=%zu dims=%zu ld=%zu)", n, dims, ld);
         return LEANN_ERR_INVALID;
     }
-    if (backend != LEANN_BACKEND_HNSW && backend != LEANN_BACKEND_DISKANN) {
-        leann_set_error("Unknown backend: %d", backend);
-        return LEANN_ERR_INVALID;
-    }
-    if (int rc = check_degree(backend, graph_degree, complexity)) return rc;
+    if (int rc = leann_internal_check_build_args(backend, graph_degree, complexity)) return rc;
     if (int rc = leann_internal_check_device(device)) return rc;
     BCHECK(hipSetDevice(device));
     leann_backend *h = new leann_backend();
@@ -788,8 +770,7 @@ static int build_device_impl(int backend, const float *d_vectors, size_t n, size
             leann_backend_close(h);
             return LEANN_ERR_DEVICE;
         }
-        h->g.X = cp;
-        h->store.rows = DeviceBuf<unsigned char>(std::move(cp));
+        leann_internal_own_rows(h, std::move(cp));
     } else {
         h->g.X = d_vectors; // borrowed: store.rows stays empty
     }
@@ -808,28 +789,12 @@ extern "C" int leann_backend_build(int backend, const float *vectors, size_t n, 
         leann_set_error("leann_backend_build: invalid arguments");
         return LEANN_ERR_INVALID;
     }
-    if (backend != LEANN_BACKEND_HNSW && backend != LEANN_BACKEND_DISKANN) {
-        leann_set_error("Unknown backend: %d", backend);
-        return LEANN_ERR_INVALID;
-    }
-    if (int rc = check_degree(backend, graph_degree, complexity)) return rc;
-    int ndev = 0;
-    leann_device_count(&ndev);
-    if (ndev < 1) {
-        leann_set_error("no HIP device visible. This library has no CPU fallback.");
-        return LEANN_ERR_DEVICE;
-    }
-    BCHECK(hipSetDevice(0));
+    if (int rc = leann_internal_check_build_args(backend, graph_degree, complexity)) return rc;
+    if (int rc = leann_internal_use_device0()) return rc;
     const size_t ld = (dims + 3) & ~(size_t)3;
     DeviceBuf<float> dX; // this call's own copy: the handle below borrows it and is closed before it goes
     if (int rc = dX.alloc(std::max<size_t>(n * ld, 4))) return rc;
-    if (n) {
-        if (ld == dims) BCHECK(hipMemcpy(dX, vectors, n * dims * 4, hipMemcpyHostToDevice));
-        else {
-            BCHECK(hipMemset(dX, 0, n * ld * 4));
-            BCHECK(hipMemcpy2D(dX, ld * 4, vectors, dims * 4, dims * 4, n, hipMemcpyHostToDevice));
-        }
-    }
+    BCHECK(leann_internal_stage_rows(dX, ld, vectors, dims, dims, n, true));
     leann_backend *h = nullptr;
     int rc = build_device_guarded(backend, dX, n, dims, ld, graph_degree, complexity, 0, 0, 0, &h, false);
     if (rc) return rc;
@@ -855,21 +820,20 @@ static int continue_build(const leann_backend *src, const float *rows, size_t nt
     std::vector<uint8_t> levels(std::max<size_t>(nt, 1), 0);
     uint64_t old_lists = 0;
     if (n_old) {
-        std::vector<uint32_t> uo(n_old);
+        std::vector<uint32_t> uo(n_old), want(n_old);
         if (hipMemcpy(levels.data(), src->store.levels, n_old, hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(uo.data(), src->g.upper_off, n_old * 4, hipMemcpyDeviceToHost) != hipSuccess) {
             leann_set_error("%s: reading the level tables failed: %s", who, hipGetErrorString(hipGetLastError()));
             return LEANN_ERR_DEVICE;
         }
-        for (size_t i = 0; i < n_old; i++) {
-            if (uo[i] != old_lists) {
+        old_lists = leann_internal_upper_offsets(levels.data(), n_old, want.data());
+        for (size_t i = 0; i < n_old; i++)
+            if (uo[i] != want[i]) {
                 leann_set_error("%s: upper_off[%zu] is %u where the prefix sum of the levels is %llu; an append keeps the old upper lists in "
                                 "place, which needs upper_off to be that prefix sum (re-make the handle with such a table)",
-                                who, i, uo[i], (unsigned long long)old_lists);
+                                who, i, uo[i], (unsigned long long)want[i]);
                 return LEANN_ERR_INVALID;
             }
-            old_lists += levels[i];
-        }
         if (old_lists > src->n_upper_lists) {
             leann_set_error("%s: inconsistent level table: the levels name %llu upper lists, the index holds %llu", who,
                             (unsigned long long)old_lists, (unsigned long long)src->n_upper_lists);
@@ -877,19 +841,9 @@ static int continue_build(const leann_backend *src, const float *rows, size_t nt
         }
     }
     // every allocation of the result is a member of the handle: one leann_backend_close frees whatever a failure leaves behind
-    std::unique_ptr<leann_backend, void (*)(leann_backend *)> h(new leann_backend(), leann_backend_close);
-    h->kind = src->kind;
-    h->device = src->device;
-    h->key_offset = src->key_offset;
-    h->efc = src->efc;
-    h->alpha = src->alpha;
-    h->two_stage = src->two_stage;
-    h->nav_levels = src->nav_levels;
-    h->fixed_ef = src->fixed_ef;
-    h->g = src->g; // d, ld, M, M0, entry, max_level
+    HandlePtr h = leann_internal_new_like(src); // d, ld, M, M0, entry, max_level and the build parameters are src's
     h->g.X = rows; // borrowed
     h->g.n = nt;
-    h->g.adj0 = nullptr; h->g.adjU = nullptr; h->g.upper_off = nullptr; h->g.norms = nullptr;
     if (int rc = alloc_graph_arrays(h.get(), LEVEL_SEED, levels, n_old)) return rc;
     if (n_old) {
         if (hipMemcpy(h->store.adj0, src->g.adj0, n_old * h->g.M0 * 4, hipMemcpyDeviceToDevice) != hipSuccess ||
@@ -919,9 +873,6 @@ extern "C" int leann_backend_add(int backend, const float *vectors, size_t n, si
     int rc = leann_backend_open(index_path_stem, backend, dims, "0", &old);
     if (rc) return rc;
     const size_t n_old = old->g.n;
-    std::vector<uint8_t> tomb = old->removed; // removals made so far stay; the appended rows are live (zero bits)
-    const size_t tomb_n = old->n_removed;
-    if (tomb_n) tomb.resize((n_old + n + 7) / 8, 0);
     if (old->g.feat_h) { // a recompute-on index holds encoder inputs, not vectors: appending needs the passages' features, not their embeddings
         leann_set_error("add_to_index: this index stores no vectors (recompute-on); rebuild it from the encoder inputs (leann_recompute_build_index)");
         leann_backend_close(old);
@@ -945,8 +896,7 @@ extern "C" int leann_backend_add(int backend, const float *vectors, size_t n, si
     DeviceBuf<float> dX; // this call's own: every handle below borrows the rows and is closed before they go
     if (dX.alloc(std::max<size_t>(nt * ld, 4)) ||
         (n_old && hipMemcpy(dX, old->g.X, n_old * ld * 4, hipMemcpyDeviceToDevice) != hipSuccess) ||
-        (n && (hipMemset(dX + n_old * ld, 0, n * ld * 4) != hipSuccess ||
-               hipMemcpy2D(dX + n_old * ld, ld * 4, vectors, dims * 4, dims * 4, n, hipMemcpyHostToDevice) != hipSuccess))) {
+        leann_internal_stage_rows(dX + n_old * ld, ld, vectors, dims, dims, n, true) != hipSuccess) {
         leann_set_error("add_to_index: staging %zu rows on the device failed: %s", nt, hipGetErrorString(hipGetLastError()));
         leann_backend_close(old);
         return LEANN_ERR_DEVICE;
@@ -962,26 +912,19 @@ extern "C" int leann_backend_add(int backend, const float *vectors, size_t n, si
         }
         for (size_t i = 0; i < n_old && same_levels; i++) same_levels = la[i] == (uint8_t)node_level(LEVEL_SEED, i, old->g.M);
     }
-    leann_backend *h = nullptr;
+    leann_backend *h = nullptr; // borrows dX
     if (!same_levels) { // foreign level table: rebuild over the concatenation (the pre-append behaviour; leann_backend_append continues)
-        const size_t M = old->g.M, efc = old->efc;
-        leann_backend_close(old);
-        rc = build_device_guarded(backend, dX, nt, dims, ld, M, efc, 0, 0, 0, &h, false);
-        if (rc) return rc;
-        if (tomb_n) rc = leann_internal_set_removed(h, tomb.data(), tomb_n);
-        if (rc == LEANN_OK) rc = leann_backend_save(h, index_path_stem);
-        leann_backend_close(h);
-        return rc;
+        rc = build_device_guarded(backend, dX, nt, dims, ld, old->g.M, old->efc, 0, 0, 0, &h, false);
+    } else {
+        try {
+            rc = continue_build(old, dX, nt, "add_to_index", &h);
+        } catch (const std::exception &e) {
+            leann_set_error("add_to_index: %s", e.what());
+            rc = LEANN_ERR_DEVICE;
+        }
     }
-    try {
-        rc = continue_build(old, dX, nt, "add_to_index", &h); // h borrows dX
-    } catch (const std::exception &e) {
-        leann_set_error("add_to_index: %s", e.what());
-        rc = LEANN_ERR_DEVICE;
-    }
+    if (rc == LEANN_OK) rc = leann_internal_carry_removals(old, h, nt); // removals made so far stay; the appended rows are live
     leann_backend_close(old);
-    if (rc) return rc;
-    if (tomb_n) rc = leann_internal_set_removed(h, tomb.data(), tomb_n);
     if (rc == LEANN_OK) rc = leann_backend_save(h, index_path_stem);
     leann_backend_close(h);
     return rc;
@@ -1032,32 +975,17 @@ int append_impl(const char *who, const leann_backend *hc, const float *vectors, 
     if (int rc = leann_internal_check_device(hc->device)) return rc;
     BCHECK(hipSetDevice(hc->device));
     BCHECK(hipDeviceSynchronize());
-    leann_backend *src = const_cast<leann_backend *>(hc);
     const size_t n_old = hc->g.n, nt = n_old + n, gld = hc->g.ld, d = hc->g.d;
-    std::vector<uint8_t> removed; // the source's removal state, snapshot under its lock (leann_backend_remove takes it)
-    size_t n_removed = 0;
-    {
-        std::lock_guard<std::mutex> lk(src->mu);
-        removed = src->removed;
-        n_removed = src->n_removed;
-    }
     // rows: h's, byte for byte, then the new ones at h's pitch, zero padded
     DeviceBuf<float> rows;
     if (int rc = rows.alloc(std::max<size_t>(nt * gld, 4))) return rc;
     if (n_old) BCHECK(hipMemcpy(rows, hc->g.X, n_old * gld * 4, hipMemcpyDeviceToDevice));
-    if (n) {
-        BCHECK(hipMemset(rows + n_old * gld, 0, n * gld * 4));
-        BCHECK(hipMemcpy2D(rows + n_old * gld, gld * 4, vectors, (on_host ? d : ld) * 4, d * 4, n, // (host rows are [n x dims], unpadded)
-                           on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice));
-    }
+    BCHECK(leann_internal_stage_rows(rows + n_old * gld, gld, vectors, on_host ? d : ld, d, n, on_host)); // (host rows are [n x dims], unpadded)
     leann_backend *raw = nullptr;
     if (int rc = continue_build(hc, rows, nt, who, &raw)) return rc;
-    std::unique_ptr<leann_backend, void (*)(leann_backend *)> h(raw, leann_backend_close);
-    h->store.rows = DeviceBuf<unsigned char>(std::move(rows)); // the result always owns its rows (g.X names this block already)
-    if (n_removed) { // removals are carried over: zero bits for the new rows, the live mask uploaded, n_pending counted on the device
-        removed.resize((nt + 7) / 8, 0);
-        if (int rc = leann_internal_set_removed(h.get(), removed.data(), n_removed)) return rc;
-    }
+    HandlePtr h(raw);
+    leann_internal_own_rows(h.get(), std::move(rows)); // the result always owns its rows
+    if (int rc = leann_internal_carry_removals(hc, h.get(), nt)) return rc;
     if (int rc = leann_internal_copy_coalescing(hc, h.get())) return rc;
     leann_internal_sync_planes(h.get());
     *out = h.release();

@@ -179,51 +179,34 @@ int compact_checked(const leann_backend *src, const CompactChecked &c, uint64_t 
     HIP_CHECK_RET(hipMemset(d_bad, 0, 4));
 
     // every allocation of the result is a member of the handle: one leann_backend_close frees whatever a failure leaves behind
-    std::unique_ptr<leann_backend, void (*)(leann_backend *)> h(new leann_backend(), leann_backend_close);
-    h->kind = src->kind;
-    h->device = src->device;
-    h->key_offset = key_offset == LEANN_KEY_OFFSET_KEEP ? src->key_offset : key_offset;
-    h->efc = src->efc;
-    h->alpha = src->alpha;
-    h->two_stage = src->two_stage;
-    h->nav_levels = src->nav_levels;
-    h->fixed_ef = src->fixed_ef;
-    h->row_type = src->row_type;
-    h->g = g;
+    HandlePtr h = leann_internal_new_like(src);
+    if (key_offset != LEANN_KEY_OFFSET_KEEP) h->key_offset = key_offset;
     h->g.n = live;
     h->g.entry = o2n[g.entry];
-    h->g.X = nullptr; h->g.adj0 = nullptr; h->g.adjU = nullptr; h->g.upper_off = nullptr; h->g.norms = nullptr;
     GraphStore &st = h->store;
 
-    // levels, then upper_off on the host
-    if (st.levels.alloc(live) || st.upper_off.alloc(live)) return LEANN_ERR_DEVICE;
+    // levels first: they say how many upper lists there are; then upper_off on the host
+    if (st.levels.alloc(live)) return LEANN_ERR_DEVICE;
     hipLaunchKernelGGL(gather_levels_kernel, dim3((unsigned)((live + 255) / 256)), dim3(256), 0, nullptr, (const uint8_t *)src->store.levels,
                        (const uint32_t *)d_n2o, (uint32_t)live, st.levels.p);
     HIP_CHECK_RET(hipGetLastError());
     std::vector<uint8_t> lv(live);
     HIP_CHECK_RET(hipMemcpy(lv.data(), st.levels, live, hipMemcpyDeviceToHost));
     std::vector<uint32_t> uo(live);
-    uint64_t n_upper = 0;
-    for (size_t j = 0; j < live; j++) { uo[j] = (uint32_t)n_upper; n_upper += lv[j]; }
+    const uint64_t n_upper = leann_internal_upper_offsets(lv.data(), live, uo.data());
     if (n_upper > src->n_upper_lists || lv[h->g.entry] < g.max_level) {
         leann_set_error("leann_backend_compact: inconsistent graph: %s", n_upper > src->n_upper_lists ? "the levels name more upper lists than the index holds"
                                                                                                       : "the entry point does not reach max_level");
         return LEANN_ERR_INVALID;
     }
+    if (int rc = leann_internal_alloc_graph_lists(h.get(), n_upper)) return rc;
     HIP_CHECK_RET(hipMemcpy(st.upper_off, uo.data(), live * 4, hipMemcpyHostToDevice));
-    h->n_upper_lists = n_upper;
-    h->g.upper_off = st.upper_off;
-
-    // lists
-    const size_t nu = std::max<size_t>(n_upper, 1);
-    if (st.adj0.alloc(live * g.M0) || st.adjU.alloc(nu * g.M)) return LEANN_ERR_DEVICE;
-    h->g.adj0 = st.adj0; h->g.adjU = st.adjU;
-    HIP_CHECK_RET(hipMemset(st.adjU, 0xFF, nu * g.M * 4));
     // rows: the result always owns them, at the source's pitch (allocated here: no allocation between the timed launches)
     const size_t pitch = leann_internal_bf16(src) ? (size_t)g.row_bytes : (size_t)g.ld * 4;
     if (pitch == 0 || (pitch & 15) || !g.X) { leann_set_error("leann_backend_compact: rows of %zu bytes cannot be gathered in 16-byte pieces", pitch); return LEANN_ERR_INVALID; }
-    if (st.rows.alloc(std::max<size_t>(live * pitch, 128))) return LEANN_ERR_DEVICE;
-    h->g.X = reinterpret_cast<const float *>(st.rows.p);
+    DeviceBuf<unsigned char> rows;
+    if (rows.alloc(std::max<size_t>(live * pitch, 128))) return LEANN_ERR_DEVICE;
+    leann_internal_own_rows(h.get(), std::move(rows));
     const unsigned list_grid = (unsigned)std::min<size_t>((live + 3) / 4, (size_t)1 << 16); // four waves = four nodes per block
     PhaseClock phases;
     phases.mark(0);

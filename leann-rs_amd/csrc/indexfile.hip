@@ -9,7 +9,7 @@
 //              weights as f32 [feat_h x d] — what `is_pruned` (src/index/meta.rs:38-42, src/cli/prune.rs:17-79) means for a graph index.
 //   version 3: bf16 rows (rows_bf16.hip): header and graph arrays as version 1, rows = unpadded bf16 [n x d] in element order.
 // The header is checked against the file length BEFORE anything is allocated, every array is validated against n before it is
-// uploaded (api.hip:validate_graph), and no exception crosses the C boundary.
+// uploaded (handle.hip:validate_graph), and no exception crosses the C boundary.
 //
 // Index directories written by stock leann-rs hold a usearch / diskann-rs file this library cannot read (their format sources are
 // not available offline).  When the reference builder also left `<stem>.embeddings` (raw LE f32 [n x dims],
@@ -238,37 +238,14 @@ static int rebuild_from_embeddings(const std::string &emb_path, const std::strin
         leann_set_error("%s: %lld bytes is not a whole number of %zu-dimensional f32 embeddings", emb_path.c_str(), (long long)st.st_size, dims);
         return LEANN_ERR_FORMAT;
     }
-    const size_t n = (size_t)st.st_size / (dims * 4), ld = (dims + 3) & ~(size_t)3;
+    const size_t n = (size_t)st.st_size / (dims * 4);
     if (n >= (1ull << 31)) { leann_set_error("%s: too many embeddings (%zu)", emb_path.c_str(), n); return LEANN_ERR_FORMAT; }
-    FILE *f = fopen(emb_path.c_str(), "rb");
-    if (!f) { leann_set_error("cannot open %s", emb_path.c_str()); return LEANN_ERR_IO; }
-    if (int rc = leann_internal_check_device(device)) { fclose(f); return rc; }
-    if (hipSetDevice(device) != hipSuccess) { fclose(f); leann_set_error("hipSetDevice(%d) failed", device); return LEANN_ERR_DEVICE; }
     DeviceBuf<float> dX;
-    if (int rc = dX.alloc(n * ld)) { fclose(f); return rc; }
-    const size_t slab_rows = std::max<size_t>(1, ((size_t)256 << 20) / (dims * 4));
-    std::vector<float> slab(std::min(slab_rows, n) * dims);
-    bool ok = ld == dims || hipMemset(dX, 0, n * ld * 4) == hipSuccess;
-    for (size_t r0 = 0; ok && r0 < n; r0 += slab_rows) {
-        const size_t rows = std::min(slab_rows, n - r0);
-        ok = fread(slab.data(), dims * 4, rows, f) == rows &&
-             hipMemcpy2D(dX + r0 * ld, ld * 4, slab.data(), dims * 4, dims * 4, rows, hipMemcpyHostToDevice) == hipSuccess;
-    }
-    fclose(f);
-    if (!ok) { leann_set_error("reading %s into device memory failed", emb_path.c_str()); return LEANN_ERR_IO; }
-    // the reference's own build defaults are graph_degree 32, complexity 64 (src/cli/build.rs:78-83); a wider construction beam costs
-    // seconds here.  Vamana needs R = 64 beyond ~1M rows.
-    size_t degree = backend == LEANN_BACKEND_HNSW ? 32 : 64, complexity = 128;
-    if (const char *e = getenv("LEANN_REBUILD_DEGREE")) degree = (size_t)atoi(e);
-    if (const char *e = getenv("LEANN_REBUILD_COMPLEXITY")) complexity = (size_t)atoi(e);
-    leann_backend *h = nullptr;
-    int rc = leann_backend_build_device(backend, dX, n, dims, ld, degree, complexity, device, 0, 0, &h);
+    const int rc = leann_internal_rows_from_file(emb_path, 0, n, dims, device, &dX);
+    if (rc == LEANN_ERR_NOT_FOUND) { leann_set_error("cannot open %s", emb_path.c_str()); return LEANN_ERR_IO; }
+    if (rc == LEANN_ERR_IO) leann_set_error("reading %s into device memory failed", emb_path.c_str());
     if (rc) return rc;
-    h->store.rows = DeviceBuf<unsigned char>(std::move(dX)); // the handle borrowed dX until here
-    if (leann_internal_save_to(h, sidecar) != LEANN_OK) // read-only directory: serve from memory, rebuild again next time
-        leann_log(LEANN_LOG_WARN, "could not cache the rebuilt graph as %s (%s); it will be rebuilt on the next open", sidecar.c_str(), leann_last_error());
-    *out = h;
-    return LEANN_OK;
+    return leann_internal_rebuild_from_rows(backend, std::move(dX), n, dims, device, 0, sidecar, out);
 }
 
 int leann_internal_load_own_file(const std::string &path, int backend, size_t dims, int device, leann_backend **out, std::string *why) {

@@ -173,6 +173,44 @@ int leann_internal_tombstones_load(leann_backend *h, const std::string &index_fi
 enum { LEANN_LOG_ERROR = 0, LEANN_LOG_WARN = 1, LEANN_LOG_INFO = 2, LEANN_LOG_DEBUG = 3 };
 void leann_log(int level, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 bool leann_log_enabled(int level); // for callers whose message costs something to gather
+// ---- making a handle (handle.hip): what every way in shares ------------------------------------------------------------------------
+// src rows [rows x src_ld] (`dims` floats of each are data), on the host (`from_host`) or on the current device, into dst, f32
+// [rows x dst_ld] on the current device, padding columns zero.  A plain copy when both pitches equal dims, else one hipMemcpy2D,
+// behind a zero fill of dst only when dst_ld != dims.  The caller words the message.
+hipError_t leann_internal_stage_rows(float *dst, size_t dst_ld, const float *src, size_t src_ld, size_t dims, size_t rows, bool from_host);
+// `rows` unpadded f32 rows of `dims` floats from `byte_offset` of a file -> *out (empty), [rows x dims rounded up to 4] on `device`,
+// which is checked and selected once the file is open; in slabs of 256 MiB of file rows.  LEANN_ERR_NOT_FOUND: the file cannot be
+// opened or positioned; LEANN_ERR_IO: reading or uploading failed, *out is empty again — for these two the caller words the message.
+int leann_internal_rows_from_file(const std::string &path, uint64_t byte_offset, size_t rows, size_t dims, int device, DeviceBuf<float> *out);
+// The graph of an index that came without one this library can read: built on `rows` (f32 [n x dims rounded up to 4] on `device`)
+// with degree 32 (HNSW) / 64 (DiskANN) and complexity 128, or LEANN_REBUILD_DEGREE / LEANN_REBUILD_COMPLEXITY.  *out owns the rows
+// (on failure they stay the caller's) and is saved as `cache_path`; a cache that cannot be written is a warning.
+int leann_internal_rebuild_from_rows(int backend, DeviceBuf<float> &&rows, size_t n, size_t dims, int device, uint64_t key_offset,
+                                     const std::string &cache_path, leann_backend **out);
+int leann_internal_use_device0(); // the file builders' device: selects device 0, or LEANN_ERR_DEVICE and "no HIP device visible ..."
+// The owning pointer of a handle under construction: an early return closes it (leann_backend_close frees whatever it holds by then).
+struct HandleClose { void operator()(leann_backend *h) const { leann_backend_close(h); } };
+using HandlePtr = std::unique_ptr<leann_backend, HandleClose>;
+// A new handle with src's kind, device, key_offset, build parameters (below), row_type and g — every device pointer of g null, and
+// nothing else of src's (no memory, removals, planes or coalescing).  The caller changes only what it means to change.
+HandlePtr leann_internal_new_like(const leann_backend *src);
+void leann_internal_take_build_params(leann_backend *dst, const leann_backend *src); // efc, alpha, two_stage, nav_levels, fixed_ef
+// dst, over n_new >= src->g.n positions of which the first src->g.n are src's, takes src's removals (snapshot under src->mu): the
+// further positions are live, the live mask is uploaded and n_pending counted on the device.  Nothing to do for a src without removals.
+int leann_internal_carry_removals(const leann_backend *src, leann_backend *dst, size_t n_new);
+// uo[i] = number of upper lists in front of node i (the exclusive prefix sum of the level table); returns their total
+uint64_t leann_internal_upper_offsets(const uint8_t *levels, size_t n, uint32_t *uo);
+// adj0 [max(n, 1) x M0], adjU [max(n_upper_lists, 1) x M] filled with LEANN_EMPTY, upper_off and levels [max(n, 1)] into h->store
+// (g.n, M, M0 set; h's device current); binds the view and sets h->n_upper_lists.  A level array that is there already is kept
+// (compact.hip gathers the levels first: they say how many upper lists there are).
+int leann_internal_alloc_graph_lists(leann_backend *h, uint64_t n_upper_lists);
+// h owns `rows` from here on and g.X names them: the one place store.rows and g.X are set together.  A handle that was built on
+// borrowed rows (leann_backend_build_device with take_copy = 0) borrows them until this call.
+template <typename T>
+inline void leann_internal_own_rows(leann_backend *h, DeviceBuf<T> &&rows) {
+    h->store.rows = DeviceBuf<unsigned char>(std::move(rows));
+    h->g.X = reinterpret_cast<const float *>(h->store.rows.p);
+}
 // host-side graph arrays -> device index; exactly one of `vectors` (f32 rows [n x dims]) and `feat_rows` (recompute-on rows
 // [n x row_bytes] + Wf32 [feat_h x dims]) is given.  Validates every array against n before anything is uploaded.
 int leann_internal_from_host(int backend, size_t n, size_t dims, uint32_t M, uint32_t M0, uint32_t max_level, uint32_t entry,

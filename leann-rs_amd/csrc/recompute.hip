@@ -780,7 +780,7 @@ extern "C" int leann_recompute_build_index(const leann_recompute *r, int backend
     leann_backend *built = nullptr;
     if (rc == LEANN_OK) rc = leann_backend_build_device(backend, E, n, r->d, ld, graph_degree, complexity, r->device, r->key_offset, 0, &built);
     if (rc != LEANN_OK) return rc;
-    std::unique_ptr<leann_backend, void (*)(leann_backend *)> h(built, leann_backend_close); // borrows E until the swap below
+    HandlePtr h(built); // borrows E until the swap below
     // swap the rows: features + inline norm replace the embeddings
     const uint32_t hp4 = (uint32_t)((r->h + 3) & ~(size_t)3);
     const bool split = hp4 == 256; // 512-B rows of whole lines + the norms in an array of their own (GraphView::norms)
@@ -798,8 +798,7 @@ extern "C" int leann_recompute_build_index(const leann_recompute *r, int backend
     HIP_CHECK_RET(hipDeviceSynchronize());
     E.reset();
     if (split) h->g.norms = h->store.norms = std::move(norms);
-    h->g.X = reinterpret_cast<const float *>(rows_b.p);
-    h->store.rows = std::move(rows_b); // (the handle borrowed E until here)
+    leann_internal_own_rows(h.get(), std::move(rows_b));
     h->g.feat_h = hp4;
     h->g.row_bytes = row_bytes;
     *out = h.release();

@@ -60,8 +60,9 @@ static int launch_round(const float *d_src, size_t n, uint32_t d, size_t ld, uin
 static int alloc_store(leann_backend *h) {
     const uint32_t ldb = store_ld(h->g.d);
     const size_t bytes = std::max<size_t>((size_t)h->g.n * ldb * 2, 128);
-    if (int rc = h->store.rows.alloc(bytes)) return rc; // (empty until here: the handle is new, or borrowed the f32 rows it was built on)
-    h->g.X = reinterpret_cast<const float *>(h->store.rows.p);
+    DeviceBuf<unsigned char> store;
+    if (int rc = store.alloc(bytes)) return rc;
+    leann_internal_own_rows(h, std::move(store)); // (the handle is new, or borrowed the f32 rows it was built on until here)
     h->g.row_bytes = ldb * 2;
     h->g.feat_h = 0;
     h->row_type = LEANN_ROWS_BF16;
@@ -95,13 +96,10 @@ int leann_internal_bf16_adopt_host(leann_backend *h, const float *f32_rows, cons
     // f32 host rows: through a transient device slab, rounded by the same kernel as every other way in
     const size_t ld = (d + 3) & ~(size_t)3, slab = std::max<size_t>(1, ((size_t)256 << 20) / (ld * 4));
     DeviceBuf<float> stage;
-    const size_t srows = std::min(slab, n);
-    int rc = stage.alloc(srows * ld);
-    if (rc) return rc;
-    if (ld != d && hipMemset(stage, 0, srows * ld * 4) != hipSuccess) rc = LEANN_ERR_DEVICE;
+    int rc = stage.alloc(std::min(slab, n) * ld);
     for (size_t r0 = 0; rc == LEANN_OK && r0 < n; r0 += slab) {
         const size_t m = std::min(slab, n - r0);
-        if (hipMemcpy2D(stage, ld * 4, f32_rows + r0 * d, d * 4, d * 4, m, hipMemcpyHostToDevice) != hipSuccess) {
+        if (leann_internal_stage_rows(stage, ld, f32_rows + r0 * d, d, d, m, true) != hipSuccess) {
             leann_set_error("bf16 rows: upload of the rows failed: %s", hipGetErrorString(hipGetLastError()));
             rc = LEANN_ERR_DEVICE;
             break;
@@ -217,18 +215,10 @@ extern "C" int leann_backend_build_rows(int backend, const float *vectors, size_
         return LEANN_ERR_INVALID;
     }
     if (int rc = leann_internal_check_build_args(backend, graph_degree, complexity)) return rc;
-    int ndev = 0;
-    leann_device_count(&ndev);
-    if (ndev < 1) {
-        leann_set_error("no HIP device visible. This library has no CPU fallback.");
-        return LEANN_ERR_DEVICE;
-    }
-    HIP_CHECK_RET(hipSetDevice(0));
+    if (int rc = leann_internal_use_device0()) return rc;
     const size_t ld = (dims + 3) & ~(size_t)3;
     DeviceBuf<float> dX;
-    if (dX.alloc(std::max<size_t>(n * ld, 4)) ||
-        (n && ld != dims && hipMemset(dX, 0, n * ld * 4) != hipSuccess) ||
-        (n && hipMemcpy2D(dX, ld * 4, vectors, dims * 4, dims * 4, n, hipMemcpyHostToDevice) != hipSuccess)) {
+    if (dX.alloc(std::max<size_t>(n * ld, 4)) || leann_internal_stage_rows(dX, ld, vectors, dims, dims, n, true) != hipSuccess) {
         leann_set_error("leann_backend_build_rows: upload of %zu rows failed: %s", n, hipGetErrorString(hipGetLastError()));
         return LEANN_ERR_DEVICE;
     }
@@ -259,7 +249,6 @@ extern "C" int leann_backend_to_rows(const leann_backend *hc, int row_type, lean
         return LEANN_ERR_UNSUPPORTED;
     }
     try {
-        leann_backend *src = const_cast<leann_backend *>(hc);
         const size_t n = hc->g.n;
         std::vector<uint8_t> levels(std::max<size_t>(n, 1));
         std::vector<uint32_t> uo(std::max<size_t>(n, 1)), a0(std::max<size_t>(n * hc->g.M0, 1)), aU(std::max<size_t>(hc->n_upper_lists * hc->g.M, 1));
@@ -269,19 +258,8 @@ extern "C" int leann_backend_to_rows(const leann_backend *hc, int row_type, lean
                                           aU.data(), hc->n_upper_lists, nullptr, nullptr, 0, 0, nullptr, hc->device, hc->key_offset, &h, LEANN_ROWS_BF16,
                                           nullptr, n ? hc->g.X : nullptr, hc->g.ld);
         if (rc) return rc;
-        std::vector<uint8_t> removed; // the source's parameters and removal state, snapshot under its lock (leann_backend_remove takes it)
-        size_t n_removed = 0;
-        {
-            std::lock_guard<std::mutex> lk(src->mu);
-            h->efc = src->efc;
-            h->alpha = src->alpha;
-            h->fixed_ef = src->fixed_ef;
-            h->nav_levels = src->nav_levels;
-            h->two_stage = src->two_stage;
-            removed = src->removed;
-            n_removed = src->n_removed;
-        }
-        if (n_removed) rc = leann_internal_set_removed(h, removed.data(), n_removed);
+        leann_internal_take_build_params(h, hc); // (the arrays went through from_host, which knows no source handle)
+        rc = leann_internal_carry_removals(hc, h, n);
         if (rc) { leann_backend_close(h); return rc; }
         *out = h;
         return LEANN_OK;

@@ -340,32 +340,12 @@ static int open_one_shard(const std::string &src, uint64_t src_off, const std::s
         if (rc == LEANN_OK) { leann_backend_close(*out); *out = nullptr; }
         leann_log(LEANN_LOG_WARN, "ignoring stale or unreadable shard cache %s", cache.c_str());
     }
-    if (int rc = leann_internal_check_device(device)) return rc;
-    HIP_CHECK_RET(hipSetDevice(device));
-    const size_t ld = (dims + 3) & ~(size_t)3;
-    FILE *f = fopen(src.c_str(), "rb");
-    if (!f || fseeko(f, (off_t)(src_off + lo * dims * 4), SEEK_SET) != 0) { if (f) fclose(f); leann_set_error("cannot read %s", src.c_str()); return LEANN_ERR_IO; }
     DeviceBuf<float> dX;
-    if (int rc = dX.alloc(std::max<size_t>(rows * ld, 4))) { fclose(f); return rc; }
-    const size_t slab_rows = std::max<size_t>(1, ((size_t)256 << 20) / (dims * 4));
-    std::vector<float> slab(std::min(slab_rows, std::max<size_t>(rows, 1)) * dims);
-    bool ok = ld == dims || hipMemset(dX, 0, rows * ld * 4) == hipSuccess;
-    for (size_t r0 = 0; ok && r0 < rows; r0 += slab_rows) {
-        const size_t nr = std::min(slab_rows, rows - r0);
-        ok = fread(slab.data(), dims * 4, nr, f) == nr &&
-             hipMemcpy2D(dX + r0 * ld, ld * 4, slab.data(), dims * 4, dims * 4, nr, hipMemcpyHostToDevice) == hipSuccess;
-    }
-    fclose(f);
-    if (!ok) { leann_set_error("reading rows [%llu, +%zu) of %s failed", (unsigned long long)lo, rows, src.c_str()); return LEANN_ERR_IO; }
-    size_t degree = backend == LEANN_BACKEND_HNSW ? 32 : 64, complexity = 128;
-    if (const char *e = getenv("LEANN_REBUILD_DEGREE")) degree = (size_t)atoi(e);
-    if (const char *e = getenv("LEANN_REBUILD_COMPLEXITY")) complexity = (size_t)atoi(e);
-    int rc = leann_backend_build_device(backend, dX, rows, dims, ld, degree, complexity, device, lo, 0, out);
+    const int rc = leann_internal_rows_from_file(src, src_off + lo * dims * 4, rows, dims, device, &dX);
+    if (rc == LEANN_ERR_NOT_FOUND) { leann_set_error("cannot read %s", src.c_str()); return LEANN_ERR_IO; }
+    if (rc == LEANN_ERR_IO) leann_set_error("reading rows [%llu, +%zu) of %s failed", (unsigned long long)lo, rows, src.c_str());
     if (rc) return rc;
-    (*out)->store.rows = DeviceBuf<unsigned char>(std::move(dX)); // the handle borrowed dX until here
-    if (leann_internal_save_to(*out, cache) != LEANN_OK)
-        leann_log(LEANN_LOG_WARN, "could not cache shard graph %s (%s)", cache.c_str(), leann_last_error());
-    return LEANN_OK;
+    return leann_internal_rebuild_from_rows(backend, std::move(dX), rows, dims, device, lo, cache, out);
 }
 
 extern "C" int leann_sharded_open(const char *index_path_stem, int backend, size_t dims, const char *device_spec, leann_sharded **out) {
@@ -422,31 +402,28 @@ extern "C" int leann_sharded_open(const char *index_path_stem, int backend, size
     }
 }
 
-// The same thing as ONE leann_backend handle (leann_backend_open with a list / range of devices): what a Rust IndexSearcher holds.
-int leann_internal_open_sharded_backend(const char *stem, int backend, size_t dims, const char *spec, leann_backend **out) {
-    leann_sharded *s = nullptr;
-    int rc = leann_sharded_open(stem, backend, dims, spec, &s);
-    if (rc) return rc;
+// The composite handle over s: searches fan out to the sub-indexes; its own g holds only n and d (and the pitch d implies).
+static leann_backend *composite_shell(leann_sharded *s, int backend) {
     leann_backend *h = new leann_backend();
     h->kind = backend;
-    h->device = s->primary;
-    h->g.n = s->total_rows;
-    h->g.d = (uint32_t)dims;
-    h->g.ld = (uint32_t)((dims + 3) & ~(size_t)3);
-    h->sharded = s;
-    *out = h;
-    return LEANN_OK;
-}
-extern "C" int leann_sharded_as_backend(leann_sharded *s, leann_backend **out) {
-    if (!s || !out || s->rccl) { leann_set_error("leann_sharded_as_backend: null argument, or a one-process-per-GPU (RCCL) group"); return LEANN_ERR_INVALID; }
-    leann_backend *h = new leann_backend();
-    h->kind = s->shards[0].h->kind;
     h->device = s->primary;
     h->g.n = s->total_rows;
     h->g.d = (uint32_t)s->dims;
     h->g.ld = (uint32_t)((s->dims + 3) & ~(size_t)3);
     h->sharded = s;
-    *out = h;
+    return h;
+}
+// The same thing as ONE leann_backend handle (leann_backend_open with a list / range of devices): what a Rust IndexSearcher holds.
+int leann_internal_open_sharded_backend(const char *stem, int backend, size_t dims, const char *spec, leann_backend **out) {
+    leann_sharded *s = nullptr;
+    int rc = leann_sharded_open(stem, backend, dims, spec, &s);
+    if (rc) return rc;
+    *out = composite_shell(s, backend);
+    return LEANN_OK;
+}
+extern "C" int leann_sharded_as_backend(leann_sharded *s, leann_backend **out) {
+    if (!s || !out || s->rccl) { leann_set_error("leann_sharded_as_backend: null argument, or a one-process-per-GPU (RCCL) group"); return LEANN_ERR_INVALID; }
+    *out = composite_shell(s, s->shards[0].h->kind);
     return LEANN_OK;
 }
 
