@@ -319,10 +319,10 @@ int leann_backend_search_filtered_exact_batch_device(const leann_backend *h, con
                                                      size_t nq, size_t top_k, const uint8_t *d_allow,
                                                      size_t allow_stride, uint64_t *d_keys, float *d_dists,
                                                      uint32_t *d_counts, void *stream);
-/* device pointer of the rows (for ground-truth scans); NULL for a composite handle and for a handle without f32 rows (bf16 rows) */
+/* device pointer of the rows (for ground-truth scans); NULL for a composite handle and for a handle without f32 rows (bf16 or int8 rows) */
 const float *leann_backend_device_rows(const leann_backend *h);
 
-/* ---- row types (additive; DESIGN.md "bf16 rows") ----------------------------------------------------------------------------------
+/* ---- row types (additive; DESIGN.md "bf16 rows", "int8 rows") ----------------------------------------------------------------------------------
  * The rows of a stored-vector index are f32 (the default everywhere, and exactly the code paths of before) or bf16, chosen when the
  * index is made.  With r(x) = f32 -> bf16, round to nearest even (a NaN stays a NaN), and w(b) = b << 16 the exact widening:
  *     a bf16 index over rows X IS the f32 index over w(r(X)) with the same graph —
@@ -336,15 +336,37 @@ const float *leann_backend_device_rows(const leann_backend *h);
  * consolidate (removals stay tombstones), leann_backend_add, leann_backend_append and leann_backend_remove_from_index (rebuild; or remove + save),
  * leann_backend_set_row_screen (no f32 planes exist), leann_backend_open with a device list on a version-3 file (build the shards
  * and use leann_sharded_from_handles: bf16 shards work, mixing row types -> LEANN_ERR_INVALID).
+ *
+ * int8 rows (LEANN_ROWS_I8): one power-of-two scale per COLUMN and 8-bit codes.  For rows X [n x dims], all finite:
+ *     amax_j = max_i |x_ij|;   e_j = the largest integer in [-32, 32] with amax_j * 2^e_j <= 127 (0 when amax_j == 0);
+ *     c_ij = clamp(rne(x_ij * 2^e_j), -127, 127)   (the product taken in f32, rne = round to nearest, ties to even; -128 never occurs);
+ *     Xq_ij = (float)c_ij * 2^-e_j                  (exact);
+ *     an int8 index over rows X IS the f32 index over Xq with the same graph —
+ * bit for bit as above (keys, distance bits, counts, the four stats; algorithmic_bytes counts dims * 1).  A quarter of the device
+ * memory and of the row traffic; LEANNGX1 version 4: the header and graph arrays of version 1, then int8 exps [dims], then the codes
+ * [n x dims] in element order (validated on open: file length, |e_j| <= 32, no code -128, every id and offset against n).
+ * A non-finite element -> LEANN_ERR_INVALID naming the row and column, before any graph work.  The kernels apply the scales to the
+ * query (q_j * 2^-e_j, exact); a query element with 0 < |q_j| < 2^-90 may underflow there and is out of scope.
+ * On an int8 handle everything said of a bf16 handle above holds with "int8" for "bf16" and version 4 for version 3: what works
+ * (every search entry point that walks, filter modes 0 and 2, removal and its sidecar, save / open, leann_backend_compact with
+ * nothing pending — codes byte for byte, exponents carried —, leann_sharded_from_handles over int8 shards, each with its own
+ * exponents) and what is refused with LEANN_ERR_UNSUPPORTED (exact filtered search and mode 1, consolidate, add, append,
+ * remove_from_index, set_row_screen, open of a version-4 file with a device list, leann_backend_to_rows from int8 or bf16 -> int8).
+ * Measured at 10M x 768 (profiles/i8_rows.md): 1.09 x the bf16 index's queries/s, recall@10 0.0104 below the f32 index's at the same
+ * complexity and regained with a beam of 68 for 56; other widths, filtered, wide-list and small-batch throughput: not measured.
  * An unknown row_type -> LEANN_ERR_INVALID before any device work. */
-enum { LEANN_ROWS_F32 = 0, LEANN_ROWS_BF16 = 1, LEANN_ROWS_FEATURES = 2 /* recompute-on: no vectors */ };
+enum { LEANN_ROWS_F32 = 0, LEANN_ROWS_BF16 = 1, LEANN_ROWS_FEATURES = 2 /* recompute-on: no vectors */,
+       LEANN_ROWS_I8 = 4 /* 3 stays unassigned: it has always been refused as an unknown row type, and callers may rely on that */ };
 /* the handle's row type (a composite handle: its shards' common type); -1 for NULL */
 int leann_backend_row_type(const leann_backend *h);
 /* host helper, no device: out[i] = r(in[i]) */
 int leann_round_bf16(const float *in, size_t n, uint16_t *out);
+/* host helper, no device: the int8 definition above on rows in [n x d] -> exps [d], codes [n x d]: the reference quantiser the device
+ * kernels are held to.  A non-finite element -> LEANN_ERR_INVALID naming the first one in row-major order. */
+int leann_quantize_i8(const float *in, size_t n, size_t d, int8_t *exps, int8_t *codes);
 /* leann_backend_build / _build_device / _from_arrays with a row type; LEANN_ROWS_F32 is the existing call, bit for bit.
- * LEANN_ROWS_BF16: the rows are rounded first and the graph is built by the same builder on w(r(X)), so the index is reproducible
- * from its file alone.  build_device_rows: may_overwrite != 0 lets the library overwrite d_vectors with w(r(X)) and build on them
+ * LEANN_ROWS_BF16 (LEANN_ROWS_I8): the rows are rounded (quantised) first and the graph is built by the same builder on w(r(X))
+ * (on Xq), so the index is reproducible from its file alone; what follows holds for int8 with Xq for w(r(X)).  build_device_rows: may_overwrite != 0 lets the library overwrite d_vectors with w(r(X)) and build on them
  * in place; 0 takes a transient f32 copy, freed after the build, and the caller's rows come back untouched.  Either way the handle
  * owns its bf16 rows and keeps no f32 rows (d_vectors need not outlive the call); peak device memory is f32 + bf16 rows
  * (the f32 rows being the caller's with may_overwrite, else the library's transient copy beside them; the build cuts no row-screen
@@ -359,13 +381,15 @@ int leann_backend_from_arrays_rows(int backend, const float *vectors, size_t n, 
                                    const uint8_t *levels, const uint32_t *upper_off,
                                    const uint32_t *adj0, const uint32_t *adjU, size_t n_upper_lists,
                                    int device, uint64_t key_offset, int row_type, leann_backend **out);
-/* A new handle with the SAME graph (copied) and the rows of `h` in another type: today F32 -> BF16 only — the migration path of an
+/* A new handle with the SAME graph (copied) and the rows of `h` in another type: today F32 -> BF16 and F32 -> I8 only — the migration path of an
  * existing f32 index (the graph stays the one built on the exact rows; the definition above holds for the result).  `h` is left as
  * it is.  LEANN_ERR_UNSUPPORTED for a composite handle (convert the shards, then leann_sharded_from_handles), a recompute-on handle
- * and BF16 -> F32.  Removals of `h` are carried over. */
+ * and from a bf16 or int8 handle to anything.  Removals of `h` are carried over. */
 int leann_backend_to_rows(const leann_backend *h, int row_type, leann_backend **out);
 /* the rows of a bf16 handle as stored, in element order; LEANN_ERR_UNSUPPORTED for any other handle */
 int leann_backend_rows_export_bf16(const leann_backend *h, uint16_t *out /* [n x dims] */);
+/* the column exponents and the codes of an int8 handle as stored, in element order; LEANN_ERR_UNSUPPORTED for any other handle */
+int leann_backend_rows_export_i8(const leann_backend *h, int8_t *exps /* [dims] */, int8_t *rows /* [n x dims] */);
 
 /* Deterministic synthetic rows written straight into HBM; bit-identical to
  * oracle/oracle.c:orc_gen_rows. */

@@ -129,6 +129,8 @@ extern "C" {
                                    n_live: *mut usize) -> c_int;
     // row types (additive): 0 = f32 (the default: the calls above), 1 = bf16 rows — half the device memory and index file; a bf16
     // index answers bit for bit like the f32 index over the rounded rows.  leann_backend_open detects the type from the file.
+    // 4 = int8 rows — one power-of-two scale per column and 8-bit codes, a quarter of the device memory; the index answers bit for
+    // bit like the f32 index over the dequantised rows.  (2 names a recompute-on handle and cannot be asked for; 3 is unassigned.)
     #[allow(dead_code)]
     fn leann_backend_row_type(h: *const LeannBackend) -> c_int;
     #[allow(dead_code)]
@@ -149,6 +151,10 @@ extern "C" {
     fn leann_backend_to_rows(h: *const LeannBackend, row_type: c_int, out: *mut *mut LeannBackend) -> c_int;
     #[allow(dead_code)]
     fn leann_backend_rows_export_bf16(h: *const LeannBackend, out: *mut u16) -> c_int;
+    #[allow(dead_code)]
+    fn leann_quantize_i8(input: *const f32, n: usize, d: usize, exps: *mut i8, codes: *mut i8) -> c_int;
+    #[allow(dead_code)]
+    fn leann_backend_rows_export_i8(h: *const LeannBackend, exps: *mut i8, rows: *mut i8) -> c_int;
 }
 
 fn last_error() -> anyhow::Error {

@@ -5,7 +5,7 @@ reference's index layer + `leann search` CLI), and this thin ctypes mirror used 
 """
 from ._native import LeannError, lib, device_count, LIB_PATH  # noqa: F401
 from .backend import (BackendBuilder, BackendSearcher, BackendType, DiskAnnSearcher,  # noqa: F401
-                      HnswSearcher, RowType, ShardedIndex, round_bf16)
+                      HnswSearcher, RowType, ShardedIndex, quantize_i8, round_bf16)
 from .bm25 import Bm25Index  # noqa: F401
 from .device import DeviceArray, sync  # noqa: F401
 from .metadata import MetaColumns, parse_filter  # noqa: F401

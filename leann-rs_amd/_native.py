@@ -89,6 +89,8 @@ SIGNATURES = {
                                                 C.c_int, C.c_uint64, C.c_int, C.POINTER(vp)]),
     "leann_backend_to_rows": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
     "leann_backend_rows_export_bf16": (C.c_int, [vp, C.POINTER(C.c_uint16)]),
+    "leann_quantize_i8": (C.c_int, [f32p, C.c_size_t, C.c_size_t, C.POINTER(C.c_int8), C.POINTER(C.c_int8)]),
+    "leann_backend_rows_export_i8": (C.c_int, [vp, C.POINTER(C.c_int8), C.POINTER(C.c_int8)]),
     "leann_backend_graph_info": (C.c_int, [vp, u64p]),
     "leann_backend_graph_export": (C.c_int, [vp, u8p, u32p, u32p, u32p, f32p]),
     "leann_backend_save": (C.c_int, [vp, C.c_char_p]),

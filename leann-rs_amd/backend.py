@@ -34,6 +34,7 @@ class RowType(enum.IntEnum):
     F32 = 0
     BF16 = 1
     Features = 2
+    I8 = 4
 
 
 def round_bf16(x):
@@ -42,6 +43,18 @@ def round_bf16(x):
     out = np.zeros(x.shape, np.uint16)
     N.check(N.lib().leann_round_bf16(_p(x, f32p), x.size, out.ctypes.data_as(C.POINTER(C.c_uint16))))
     return out
+
+
+def quantize_i8(x):
+    """f32 rows [n x d] -> (exps int8 [d], codes int8 [n x d]): one power-of-two scale per column, codes round to nearest even and
+    clamp to +-127 (include/leann_backend.h "row types"): the library's own reference quantiser, on the host"""
+    x = np.ascontiguousarray(x, np.float32)
+    if x.ndim != 2:
+        raise LeannError(1, "quantize_i8: rows must be [n x d]")
+    exps, codes = np.zeros(x.shape[1], np.int8), np.zeros(x.shape, np.int8)
+    i8p = C.POINTER(C.c_int8)
+    N.check(N.lib().leann_quantize_i8(_p(x, f32p), x.shape[0], x.shape[1], exps.ctypes.data_as(i8p), codes.ctypes.data_as(i8p)))
+    return exps, codes
 
 
 def _p(a, t):
@@ -346,7 +359,7 @@ class BackendSearcher:
         return RowType(N.lib().leann_backend_row_type(self._h))
 
     def to_rows(self, row_type):
-        """a new searcher with the same graph and this one's rows in another type (f32 -> bf16)"""
+        """a new searcher with the same graph and this one's rows in another type (f32 -> bf16, f32 -> int8)"""
         h = C.c_void_p()
         N.check(N.lib().leann_backend_to_rows(self._h, int(row_type), C.byref(h)))
         return BackendSearcher(h, self.backend_type)
@@ -356,6 +369,13 @@ class BackendSearcher:
         out = np.zeros((self.len(), self.dims()), np.uint16)
         N.check(N.lib().leann_backend_rows_export_bf16(self._h, out.ctypes.data_as(C.POINTER(C.c_uint16))))
         return out
+
+    def rows_export_i8(self):
+        """the rows of an int8 index as stored: (exps int8 [dims], codes int8 [n x dims])"""
+        exps, codes = np.zeros(self.dims(), np.int8), np.zeros((self.len(), self.dims()), np.int8)
+        i8p = C.POINTER(C.c_int8)
+        N.check(N.lib().leann_backend_rows_export_i8(self._h, exps.ctypes.data_as(i8p), codes.ctypes.data_as(i8p)))
+        return exps, codes
 
     def device_rows_ptr(self):
         return N.lib().leann_backend_device_rows(self._h)

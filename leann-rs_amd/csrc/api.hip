@@ -215,7 +215,7 @@ extern "C" void leann_backend_close(leann_backend *h) {
 }
 extern "C" size_t leann_backend_len(const leann_backend *h) { return h ? (size_t)h->g.n : 0; }
 extern "C" size_t leann_backend_dims(const leann_backend *h) { return h ? (size_t)h->g.d : 0; }
-extern "C" const float *leann_backend_device_rows(const leann_backend *h) { return h && !h->sharded && !leann_internal_bf16(h) ? h->g.X : nullptr; }
+extern "C" const float *leann_backend_device_rows(const leann_backend *h) { return h && !h->sharded && !leann_internal_narrow_rows(h) ? h->g.X : nullptr; }
 #define NOT_ON_SHARDED(h, what)                                                                                                    \
     do {                                                                                                                           \
         if ((h) && (h)->sharded) {                                                                                                 \
@@ -303,7 +303,8 @@ int leann_internal_launch_search(leann_backend *h, SearchArgs a, hipStream_t st)
     if (a.ef < a.k) a.ef = a.k; // diskann.rs:54
     SearchShape shape{};
     shape.ld = g.ld; shape.d = g.d; shape.feat_h = g.feat_h; shape.bf16 = leann_internal_bf16(h); shape.maxdeg = std::max(g.M0, g.M);
-    shape.screen_ready = !g.feat_h && !shape.bf16 && h->row_screen.load(std::memory_order_relaxed) != 0 && leann_internal_planes_ready(h) &&
+    shape.i8 = leann_internal_i8(h);
+    shape.screen_ready = !g.feat_h && !shape.bf16 && !shape.i8 && h->row_screen.load(std::memory_order_relaxed) != 0 && leann_internal_planes_ready(h) &&
                          leann_internal_screen_shape(g);
     const SearchCall call{a.nq, a.k, a.ef, a.allow != nullptr, a.q_rows != nullptr};
     const SearchKnobs knobs{leann_knobs().hash_bits, leann_knobs().nw, leann_knobs().no_feat256};
@@ -320,7 +321,9 @@ int leann_internal_launch_search(leann_backend *h, SearchArgs a, hipStream_t st)
     }
     if (p.family == SEARCH_SCREEN) { a.x_hi = h->x_hi; a.x_lo = h->x_lo; a.ldp = h->ldp; a.screen_ctr = h->screen_ctr; }
     SearchKernel kernel = nullptr;
-    if (int rc = p.family == SEARCH_BF16 ? leann_internal_bf16_kernel(g, p, &kernel) : search_kernel(p, &kernel)) return rc;
+    if (int rc = p.family == SEARCH_BF16 ? leann_internal_bf16_kernel(g, p, &kernel)
+                 : p.family == SEARCH_I8 ? leann_internal_i8_kernel(g, p, &kernel) : search_kernel(p, &kernel))
+        return rc;
     if (leann_log_enabled(LEANN_LOG_DEBUG)) {
         char name[96];
         search_plan_name(p, name, sizeof name);
@@ -348,6 +351,10 @@ int leann_internal_search_plain(leann_backend *h, const float *d_queries, size_t
     }
     if (f.exact && leann_internal_bf16(h)) {
         leann_set_error("exact filtered search scans f32 rows; this index stores bf16 rows (use the filtered walk: mode 0, or mode 2 which picks it)");
+        return LEANN_ERR_UNSUPPORTED;
+    }
+    if (f.exact && leann_internal_i8(h)) {
+        leann_set_error("exact filtered search scans f32 rows; this index stores int8 rows (use the filtered walk: mode 0, or mode 2 which picks it)");
         return LEANN_ERR_UNSUPPORTED;
     }
     if (h->g.n == 0) {
@@ -572,7 +579,7 @@ static int search_filtered_batch_host_impl(const leann_backend *hc, const float 
     // exact up to 5 % of the rows / 64k rows for small batches, 1.5 % for large ones, when the index stores vectors
     bool exact = mode == FILTER_EXACT;
     const leann_backend *first = hc && hc->sharded ? leann_internal_sharded_shard(hc->sharded, 0) : hc;
-    const bool stored_vectors = first && !first->g.feat_h && !leann_internal_bf16(first); // f32 rows an exact scan can read
+    const bool stored_vectors = first && !first->g.feat_h && !leann_internal_narrow_rows(first); // f32 rows an exact scan can read
     if (mode == FILTER_AUTO && flt && hc && stored_vectors && top_k <= 1024) {
         const double frac = nq <= 64 ? 0.05 : 0.015;
         exact = flt->n_allowed <= std::max<size_t>((size_t)(frac * (double)hc->g.n), nq <= 64 ? 65536 : 0);
@@ -670,7 +677,8 @@ static int search_filtered_batch_host_impl(const leann_backend *hc, const float 
     {
         std::lock_guard<std::mutex> lk(h->mu);
         const GraphView &gv = h->sharded ? leann_internal_sharded_shard(h->sharded, 0)->g : h->g; // (shards share one configuration)
-        const size_t elem_bytes = leann_internal_bf16(h->sharded ? leann_internal_sharded_shard(h->sharded, 0) : h) ? 2 : 4;
+        const leann_backend *const h0 = h->sharded ? leann_internal_sharded_shard(h->sharded, 0) : h;
+        const size_t elem_bytes = leann_internal_i8(h0) ? 1 : leann_internal_bf16(h0) ? 2 : 4;
         for (size_t i = 0; i < ns * nq; i++) {
             h->stats.n_dist_evals += hstats[i * 4 + 0];
             h->stats.n_hops_base += hstats[i * 4 + 1];
@@ -969,6 +977,24 @@ extern "C" int leann_backend_graph_export(const leann_backend *h, uint8_t *level
             memcpy(&b, base + 2 * nd + 2 * i, 2);
             const uint32_t w = (uint32_t)b << 16;
             memcpy(base + 4 * i, &w, 4);
+        }
+        return LEANN_OK;
+    }
+    if (vectors && leann_internal_i8(h)) {
+        // Xq = code x 2^-e: exact.  The codes land in the LAST quarter of the caller's own buffer (n d bytes of 4 n d) and are dequantised
+        // in place, front to back: element i is written at bytes 4 i .. 4 i + 3 and read from byte 3 n d + i, which no earlier write
+        // has reached (4 i + 4 <= 3 n d + i + 1 for every i < n d).
+        const size_t d = h->g.d, nd = n * d;
+        unsigned char *base = reinterpret_cast<unsigned char *>(vectors);
+        try {
+            if (int rc = leann_internal_i8_to_host(h, 0, n, reinterpret_cast<int8_t *>(base + 3 * nd))) return rc;
+        } catch (const std::exception &e) {
+            leann_set_error("leann_backend_graph_export: %s", e.what());
+            return LEANN_ERR_IO;
+        }
+        for (size_t i = 0; i < nd; i++) {
+            const float x = (float)(int8_t)base[3 * nd + i] * ldexpf(1.0f, -h->i8_exps[i % d]);
+            memcpy(base + 4 * i, &x, 4);
         }
         return LEANN_OK;
     }

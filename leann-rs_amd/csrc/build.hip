@@ -878,8 +878,9 @@ extern "C" int leann_backend_add(int backend, const float *vectors, size_t n, si
         leann_backend_close(old);
         return LEANN_ERR_UNSUPPORTED;
     }
-    if (leann_internal_bf16(old)) { // the builder reads f32 rows, and appending f32 rows to rounded ones would break the file's reproducibility
-        leann_set_error("add_to_index: this index stores bf16 rows; appending is not supported, rebuild it (leann_backend_build_rows) from all the rows");
+    if (leann_internal_narrow_rows(old)) { // the builder reads f32 rows, and appending f32 rows to rounded ones would break the file's reproducibility
+        leann_set_error("add_to_index: this index stores %s rows; appending is not supported, rebuild it (leann_backend_build_rows) from all the rows",
+                        leann_internal_row_name(old));
         leann_backend_close(old);
         return LEANN_ERR_UNSUPPORTED;
     }
@@ -947,8 +948,9 @@ int append_check(const char *who, const leann_backend *h, const float *vectors, 
         leann_set_error("%s: this index stores no vectors (recompute-on); rebuild it from the encoder inputs (leann_recompute_build_index)", who);
         return LEANN_ERR_UNSUPPORTED;
     }
-    if (leann_internal_bf16(h)) {
-        leann_set_error("%s: this index stores bf16 rows and the builder reads f32 rows; rebuild it from all the rows (leann_backend_build_rows)", who);
+    if (leann_internal_narrow_rows(h)) {
+        leann_set_error("%s: this index stores %s rows and the builder reads f32 rows; rebuild it from all the rows (leann_backend_build_rows)", who,
+                        leann_internal_row_name(h));
         return LEANN_ERR_UNSUPPORTED;
     }
     if (h->nav_levels) {

@@ -7,7 +7,7 @@
 //   position map   old_to_new u32 [n] (LEANN_EMPTY for removed positions) and new_to_old u32 [live], written on the host from the
 //                  handle's removal bitmap (n / 8 bytes in, 8 n bytes out — not the hot part) and uploaded;
 //   rows           gather_rows_kernel: row_bytes-pitched rows by new_to_old in 16-byte pieces.  One kernel for both row types: an f32
-//                  pitch is ld * 4 with ld % 4 == 0, a bf16 pitch is a multiple of 128 B in rs_plane_pos order, which a byte copy keeps;
+//                  pitch is ld * 4 with ld % 4 == 0, a bf16 or int8 pitch is a multiple of 128 B in its own element order, which a byte copy keeps;
 //   levels         gather_levels_kernel; upper_off = their exclusive prefix sum, on the host as the builder's alloc_graph_arrays does;
 //   lists          remap_lists_kernel, once for level 0 and once for the upper array: the lists of a node are one contiguous run of
 //                  slots in either array (level 0: one list at the node's position; upper: `level` lists from upper_off), so both
@@ -202,11 +202,13 @@ int compact_checked(const leann_backend *src, const CompactChecked &c, uint64_t 
     if (int rc = leann_internal_alloc_graph_lists(h.get(), n_upper)) return rc;
     HIP_CHECK_RET(hipMemcpy(st.upper_off, uo.data(), live * 4, hipMemcpyHostToDevice));
     // rows: the result always owns them, at the source's pitch (allocated here: no allocation between the timed launches)
-    const size_t pitch = leann_internal_bf16(src) ? (size_t)g.row_bytes : (size_t)g.ld * 4;
+    const size_t pitch = leann_internal_narrow_rows(src) ? (size_t)g.row_bytes : (size_t)g.ld * 4;
     if (pitch == 0 || (pitch & 15) || !g.X) { leann_set_error("leann_backend_compact: rows of %zu bytes cannot be gathered in 16-byte pieces", pitch); return LEANN_ERR_INVALID; }
     DeviceBuf<unsigned char> rows;
     if (rows.alloc(std::max<size_t>(live * pitch, 128))) return LEANN_ERR_DEVICE;
     leann_internal_own_rows(h.get(), std::move(rows));
+    if (leann_internal_i8(src)) // the codes move byte for byte: the columns keep their exponents
+        if (int rc = leann_internal_i8_carry_exponents(src, h.get())) return rc;
     const unsigned list_grid = (unsigned)std::min<size_t>((live + 3) / 4, (size_t)1 << 16); // four waves = four nodes per block
     PhaseClock phases;
     phases.mark(0);

@@ -400,8 +400,9 @@ static int consolidate_plain(leann_backend *h) {
         leann_set_error("leann_backend_consolidate: a recompute-on index holds no f32 rows to prune on; its removals stay tombstones");
         return LEANN_ERR_UNSUPPORTED;
     }
-    if (leann_internal_bf16(h)) {
-        leann_set_error("leann_backend_consolidate: the repair prunes on f32 rows; this index stores bf16 rows, its removals stay tombstones answered by the filtered walk");
+    if (leann_internal_narrow_rows(h)) {
+        leann_set_error("leann_backend_consolidate: the repair prunes on f32 rows; this index stores %s rows, its removals stay tombstones answered by the filtered walk",
+                        leann_internal_row_name(h));
         return LEANN_ERR_UNSUPPORTED;
     }
     if (!h->n_removed || !h->d_live || !h->g.n) return LEANN_OK;
@@ -555,8 +556,9 @@ extern "C" int leann_backend_remove_from_index(int backend, const uint64_t *keys
     leann_backend *h = nullptr;
     int rc = leann_backend_open(index_path_stem, backend, dims, "0", &h);
     if (rc) return rc;
-    if (leann_internal_bf16(h)) { // its consolidate step needs f32 rows: refused before anything changes
-        leann_set_error("leann_backend_remove_from_index: not available on an index of bf16 rows (no graph repair); open it, leann_backend_remove, leann_backend_save: the removals stay tombstones");
+    if (leann_internal_narrow_rows(h)) { // its consolidate step needs f32 rows: refused before anything changes
+        leann_set_error("leann_backend_remove_from_index: not available on an index of %s rows (no graph repair); open it, leann_backend_remove, leann_backend_save: the removals stay tombstones",
+                        leann_internal_row_name(h));
         leann_backend_close(h);
         return LEANN_ERR_UNSUPPORTED;
     }

@@ -143,18 +143,19 @@ int leann_internal_from_host(int backend, size_t n, size_t dims, uint32_t M, uin
                              const uint8_t *levels, const uint32_t *upper_off, const uint32_t *adj0, const uint32_t *adjU,
                              size_t n_upper_lists, const float *vectors, const unsigned char *feat_rows, uint32_t feat_h, uint32_t row_bytes,
                              const float *Wf32, int device, uint64_t key_offset, leann_backend **out, int row_type, const uint16_t *bf16_rows,
-                             const float *d_f32_rows, size_t d_f32_ld) {
-    const bool feat = feat_rows != nullptr, bf16 = row_type == LEANN_ROWS_BF16;
-    if (row_type != LEANN_ROWS_F32 && row_type != LEANN_ROWS_BF16) {
-        leann_set_error("leann_backend_from_arrays: unknown row type %d (LEANN_ROWS_F32 or LEANN_ROWS_BF16)", row_type);
+                             const float *d_f32_rows, size_t d_f32_ld, const int8_t *i8_codes, const int8_t *i8_exps) {
+    const bool feat = feat_rows != nullptr, bf16 = row_type == LEANN_ROWS_BF16, i8 = row_type == LEANN_ROWS_I8;
+    if (row_type != LEANN_ROWS_F32 && row_type != LEANN_ROWS_BF16 && row_type != LEANN_ROWS_I8) {
+        leann_set_error("leann_backend_from_arrays: unknown row type %d (LEANN_ROWS_F32, LEANN_ROWS_BF16 or LEANN_ROWS_I8)", row_type);
         return LEANN_ERR_INVALID;
     }
-    if ((bf16 && (feat || (vectors != nullptr) + (bf16_rows != nullptr) + (d_f32_rows != nullptr) > 1 || (d_f32_rows && d_f32_ld < dims))) ||
-        (!bf16 && (bf16_rows || d_f32_rows))) {
+    const void *const narrow_rows = bf16 ? (const void *)bf16_rows : (const void *)i8_codes; // an index file's rows in the handle's own type
+    if (((bf16 || i8) && (feat || (vectors != nullptr) + (narrow_rows != nullptr) + (d_f32_rows != nullptr) > 1 || (d_f32_rows && d_f32_ld < dims))) ||
+        (!bf16 && !i8 && d_f32_rows) || (!bf16 && bf16_rows) || (!i8 && (i8_codes || i8_exps)) || (i8_codes && !i8_exps)) {
         leann_set_error("leann_backend_from_arrays: invalid arguments");
         return LEANN_ERR_INVALID;
     }
-    if (!out || dims == 0 || dims > 4096 || n >= (1ull << 31) || (n && ((!vectors && !feat && !bf16_rows && !d_f32_rows) || !adj0 || !upper_off)) ||
+    if (!out || dims == 0 || dims > 4096 || n >= (1ull << 31) || (n && ((!vectors && !feat && !narrow_rows && !d_f32_rows) || !adj0 || !upper_off)) ||
         (backend != LEANN_BACKEND_HNSW && backend != LEANN_BACKEND_DISKANN) ||
         (feat && (!Wf32 || feat_h == 0 || (feat_h & 3) || feat_h > 1024 || row_bytes < 2 * feat_h + 4 || (row_bytes & 7)))) {
         leann_set_error("leann_backend_from_arrays: invalid arguments");
@@ -216,6 +217,10 @@ int leann_internal_from_host(int backend, size_t n, size_t dims, uint32_t M, uin
         if (hipMemcpy(h->Wf32, Wf32, (size_t)feat_h * dims * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("upload of the weights");
     } else if (bf16) {
         const int rc = d_f32_rows ? leann_internal_bf16_adopt_device(h, d_f32_rows, d_f32_ld) : leann_internal_bf16_adopt_host(h, vectors, bf16_rows);
+        if (rc) { leann_backend_close(h); return rc; }
+    } else if (i8) {
+        const int rc = d_f32_rows ? leann_internal_i8_adopt_device(h, d_f32_rows, d_f32_ld, "leann_backend_to_rows")
+                                  : leann_internal_i8_adopt_host(h, vectors, i8_codes, i8_exps);
         if (rc) { leann_backend_close(h); return rc; }
     } else {
         DeviceBuf<float> rows;

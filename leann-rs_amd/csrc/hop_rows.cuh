@@ -70,6 +70,7 @@ for (uint32_t j0 = wave; j0 < n_new; j0 += NW * R) {
 #endif
     if (FEAT) wave_dist_rows_feat<T, R>(q, reinterpret_cast<const char *>(g.X), g.row_bytes, g.feat_h, ids, nrows, lane, dd, g.norms);
     else if constexpr (BF16) wave_dist_rows_bf16<T, R>(q, reinterpret_cast<const uint16_t *>(g.X), g.row_bytes >> 1, ids, nrows, lane, dd);
+    else if constexpr (I8) wave_dist_rows_i8<T, R>(q, reinterpret_cast<const int8_t *>(g.X), g.row_bytes, ids, nrows, lane, dd);
     else wave_dist_rows<T, R>(q, g.X, g.ld, ids, nrows, lane, dd);
 #ifndef LEANN_NO_ADJ_TOUCH
     if constexpr (EARLY_B) asm volatile("" ::"v"(touch));

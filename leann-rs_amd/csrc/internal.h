@@ -116,9 +116,29 @@ struct leann_backend {
     // u16 in rs_plane_pos order (g.row_bytes: a multiple of 128, zero padded), g.feat_h stays 0, no f32 rows exist and no planes are
     // ever cut.  Every path that reads g.X as f32 checks this first.  (A recompute-on handle reports LEANN_ROWS_FEATURES through
     // leann_backend_row_type; here it is g.feat_h != 0 as before.)
+    // LEANN_ROWS_I8 (rows_i8.hip): g.X names the handle's own store of int8 codes, [n x g.row_bytes] bytes in i8_row_pos order, g.norms
+    // (store.norms) the column scales 2^-e_j, f32 [g.ld]; i8_exps holds the exponents e_j [g.d] on the host.  Otherwise as bf16.
     int row_type = LEANN_ROWS_F32;
+    std::vector<int8_t> i8_exps;
 };
 inline bool leann_internal_bf16(const leann_backend *h) { return h->row_type == LEANN_ROWS_BF16; }
+inline bool leann_internal_i8(const leann_backend *h) { return h->row_type == LEANN_ROWS_I8; }
+// the handle stores its vectors in a narrow type: no f32 rows exist for a scan, the builder or the graph repair to read
+inline bool leann_internal_narrow_rows(const leann_backend *h) { return leann_internal_bf16(h) || leann_internal_i8(h); }
+inline const char *leann_internal_row_name(const leann_backend *h) { return leann_internal_i8(h) ? "int8" : leann_internal_bf16(h) ? "bf16" : "f32"; }
+// int8 row store (rows_i8.hip).  _quantize_device: the column pass (when *exps is empty; LEANN_ERR_INVALID naming the first non-finite
+// element) and the quantising kernel over f32 device rows [n x ld_src]: codes into `store` (may be null), Xq back over the rows when
+// `write_back`.  _adopt_device: allocate h's store and scales and fill them from f32 device rows (h->g.n / d / ld set; h's device
+// current; exponents h already has are kept).  _adopt_host: the same from host rows, f32 [n x d] or an index file's codes [n x d] and
+// exponents [d].  _to_host: rows [r0, r0 + rows) as codes [rows x d] in element order.  _carry_exponents: dst takes src's exponents
+// and scales (compact.hip).  _check_file_rows: null, or what is wrong with an index file's exponents and codes.
+int leann_internal_i8_quantize_device(const char *who, float *d_rows, size_t n, uint32_t d, size_t ld_src, std::vector<int8_t> *exps, int8_t *store,
+                                      bool write_back);
+int leann_internal_i8_adopt_device(leann_backend *h, const float *d_src, size_t ld_src, const char *who);
+int leann_internal_i8_adopt_host(leann_backend *h, const float *f32_rows, const int8_t *codes, const int8_t *exps);
+int leann_internal_i8_to_host(const leann_backend *h, size_t r0, size_t rows, int8_t *out);
+int leann_internal_i8_carry_exponents(const leann_backend *src, leann_backend *dst);
+const char *leann_internal_i8_check_file_rows(const int8_t *exps, const int8_t *codes, size_t n, size_t d);
 // bf16 row store (rows_bf16.hip).  _adopt_device: allocate h's store and fill it with r(rows) of f32 device rows [n x ld_src] (h->g.n /
 // d / ld set; h's device current); afterwards h owns the store and names no f32 rows.  _adopt_host: the same from host rows, f32
 // [n x d] (rounded on the device, slab by slab) or bf16 [n x d] in element order (an index file's).  _to_host: rows [r0, r0 + rows)
@@ -153,6 +173,7 @@ inline int leann_internal_find_kernel(const SearchKernelRow (&rows)[N], const Se
     return LEANN_ERR_INVALID;
 }
 int leann_internal_bf16_kernel(const GraphView &g, const SearchPlan &p, SearchKernel *out); // search_bf16.hip: checks the row store too
+int leann_internal_i8_kernel(const GraphView &g, const SearchPlan &p, SearchKernel *out);   // search_i8.hip: the same for int8 rows
 // the one launch of a traversal kernel (api.hip): > 64 KiB of LDS is asked for first; grid = a.nq workgroups of p.NW waves
 int launch_plan(SearchKernel kernel, const SearchPlan &p, const GraphView &g, const SearchArgs &a, hipStream_t st);
 bool leann_internal_screen_shape(const GraphView &g);      // the row widths and list lengths the screen kernel is compiled for
@@ -217,9 +238,11 @@ int leann_internal_from_host(int backend, size_t n, size_t dims, uint32_t M, uin
                              const uint8_t *levels, const uint32_t *upper_off, const uint32_t *adj0, const uint32_t *adjU,
                              size_t n_upper_lists, const float *vectors, const unsigned char *feat_rows, uint32_t feat_h, uint32_t row_bytes,
                              const float *Wf32, int device, uint64_t key_offset, leann_backend **out, int row_type = LEANN_ROWS_F32,
-                             const uint16_t *bf16_rows = nullptr, const float *d_f32_rows = nullptr, size_t d_f32_ld = 0);
+                             const uint16_t *bf16_rows = nullptr, const float *d_f32_rows = nullptr, size_t d_f32_ld = 0,
+                             const int8_t *i8_codes = nullptr, const int8_t *i8_exps = nullptr);
 // ^ row_type LEANN_ROWS_BF16: the rows come as host f32 `vectors` (rounded), host `bf16_rows` [n x dims] (an index file's) or device
-//   f32 rows `d_f32_rows` [n x d_f32_ld] (rounded; leann_backend_to_rows) — exactly one of the three.
+//   f32 rows `d_f32_rows` [n x d_f32_ld] (rounded; leann_backend_to_rows) — exactly one of the three.  LEANN_ROWS_I8: the same three
+//   ways, the file's rows being `i8_codes` [n x dims] with `i8_exps` [dims] in place of `bf16_rows`.
 int leann_internal_save_to(const leann_backend *h, const std::string &path);
 int leann_internal_parse_device(const char *spec, int *device);
 int leann_internal_check_device(int device); // api.hip: LEANN_ERR_DEVICE and the "no CPU fallback" message unless `device` is a visible one

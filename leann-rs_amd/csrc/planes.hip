@@ -81,7 +81,7 @@ bool leann_internal_planes_ready(const leann_backend *h) {
 // Never fails the caller: without planes the searches run the whole-row kernels.
 void leann_internal_sync_planes(leann_backend *h) {
     const int mode = h->row_screen.load();
-    if (h->sharded || mode == 0 || !h->g.X || leann_internal_bf16(h) || h->g.n == 0 || !leann_internal_screen_shape(h->g)) return;
+    if (h->sharded || mode == 0 || !h->g.X || leann_internal_narrow_rows(h) || h->g.n == 0 || !leann_internal_screen_shape(h->g)) return;
     if (mode == 1 && (size_t)h->g.n * h->g.ld * 4 < LEANN_SCREEN_AUTO_MIN_BYTES) return;
     if (leann_internal_planes_ready(h)) return;
     leann_internal_free_planes(h);
@@ -121,6 +121,10 @@ extern "C" int leann_backend_set_row_screen(leann_backend *h, int enable) {
     if (!h) { leann_set_error("leann_backend_set_row_screen: null handle"); return LEANN_ERR_INVALID; }
     if (leann_backend_row_type(h) == LEANN_ROWS_BF16) { // nothing changes: no planes are ever cut for such a handle
         leann_set_error("leann_backend_set_row_screen: the row screen splits f32 rows; this index stores bf16 rows, which are read whole");
+        return LEANN_ERR_UNSUPPORTED;
+    }
+    if (leann_backend_row_type(h) == LEANN_ROWS_I8) {
+        leann_set_error("leann_backend_set_row_screen: the row screen splits f32 rows; this index stores int8 rows, which are read whole");
         return LEANN_ERR_UNSUPPORTED;
     }
     for_each_plain(h, [](leann_backend *s, void *ctx) {

@@ -3,7 +3,8 @@
 // Definition: with r = f32 -> bf16 round to nearest even (bf16.h) and w = the exact widening b << 16, a bf16 index over rows X is
 // the f32 index over w(r(X)) with the same graph, bit for bit.  The search kernels are search_bf16.hip's; this file holds the row
 // store — rounding on the device, the way in from host rows and index files, the way out — and the entry points that make such a
-// handle: from arrays, by a device build on the rounded rows, and from an f32 handle (leann_backend_to_rows).
+// handle: from arrays, by a device build on the rounded rows, and from an f32 handle (leann_backend_to_rows).  The same entry points
+// make int8 handles (LEANN_ROWS_I8): their row store is rows_i8.hip's.
 //
 // Device layout: [n x ldb] u16, ldb = dims rounded up to 64 elements, zero padded — a row is whole, aligned 128-B lines (768-d: 12) —
 // with the elements in rs_plane_pos order (row_screen.h): lane l of a wave finds its eight halves of a 512-element block in one
@@ -127,8 +128,8 @@ int leann_internal_bf16_to_host(const leann_backend *h, size_t r0, size_t rows, 
 
 // ---- C ABI ---------------------------------------------------------------------------------------------------------------------------
 static int check_row_type(const char *who, int row_type) {
-    if (row_type == LEANN_ROWS_F32 || row_type == LEANN_ROWS_BF16) return LEANN_OK;
-    leann_set_error("%s: unknown row type %d (LEANN_ROWS_F32 = 0 or LEANN_ROWS_BF16 = 1)", who, row_type);
+    if (row_type == LEANN_ROWS_F32 || row_type == LEANN_ROWS_BF16 || row_type == LEANN_ROWS_I8) return LEANN_OK;
+    leann_set_error("%s: unknown row type %d (LEANN_ROWS_F32 = 0, LEANN_ROWS_BF16 = 1 or LEANN_ROWS_I8 = 4)", who, row_type);
     return LEANN_ERR_INVALID;
 }
 
@@ -157,7 +158,7 @@ extern "C" int leann_backend_from_arrays_rows(int backend, const float *vectors,
                                          key_offset, out);
     try {
         return leann_internal_from_host(backend, n, dims, M, M0, max_level, entry, levels, upper_off, adj0, adjU, n_upper_lists, vectors, nullptr,
-                                        0, 0, nullptr, device, key_offset, out, LEANN_ROWS_BF16);
+                                        0, 0, nullptr, device, key_offset, out, row_type);
     } catch (const std::exception &e) {
         leann_set_error("leann_backend_from_arrays_rows: %s", e.what());
         return LEANN_ERR_IO;
@@ -189,7 +190,12 @@ extern "C" int leann_backend_build_device_rows(int backend, float *d_vectors, si
         rows = copy;
     }
     // X <- w(r(X)) in place; the existing builder, unchanged, on those rows (borrowed); then the store — r(w(r(x))) = r(x) — replaces them
-    int rc = launch_round(rows, n, (uint32_t)dims, ld, store_ld((uint32_t)dims), nullptr, rows);
+    // (int8: X <- Xq behind the column pass, which refuses a non-finite element before any graph work; the exponents are kept for the
+    // store, and quantising Xq with them gives the codes again)
+    const bool i8 = row_type == LEANN_ROWS_I8;
+    std::vector<int8_t> exps;
+    int rc = i8 ? leann_internal_i8_quantize_device("leann_backend_build_device_rows", rows, n, (uint32_t)dims, ld, &exps, nullptr, true)
+                : launch_round(rows, n, (uint32_t)dims, ld, store_ld((uint32_t)dims), nullptr, rows);
     leann_backend *h = nullptr;
     // (no split planes are cut for the transient f32 rows: device memory peaks at these rows + the store, as the header promises)
     if (rc == LEANN_OK) rc = leann_internal_build_device_no_planes(backend, rows, n, dims, ld, graph_degree, complexity, device, key_offset, &h);
@@ -198,7 +204,8 @@ extern "C" int leann_backend_build_device_rows(int backend, float *d_vectors, si
         h->row_screen.store(0);
         h->g.X = nullptr;
         h->g.ld = (uint32_t)((dims + 3) & ~(size_t)3); // the store's own geometry: the kernel choice must not depend on the caller's pitch
-        rc = leann_internal_bf16_adopt_device(h, rows, ld);
+        if (i8) h->i8_exps = exps;
+        rc = i8 ? leann_internal_i8_adopt_device(h, rows, ld, "leann_backend_build_device_rows") : leann_internal_bf16_adopt_device(h, rows, ld);
     }
     copy.reset();
     if (rc) { if (h) leann_backend_close(h); return rc; }
@@ -223,7 +230,7 @@ extern "C" int leann_backend_build_rows(int backend, const float *vectors, size_
         return LEANN_ERR_DEVICE;
     }
     leann_backend *h = nullptr;
-    int rc = leann_backend_build_device_rows(backend, dX, n, dims, ld, graph_degree, complexity, 0, 0, LEANN_ROWS_BF16, 1, &h);
+    int rc = leann_backend_build_device_rows(backend, dX, n, dims, ld, graph_degree, complexity, 0, 0, row_type, 1, &h);
     dX.reset(); // the upload was this call's own copy: built on in place, not kept
     if (rc) return rc;
     rc = leann_backend_save(h, index_path_stem);
@@ -243,9 +250,9 @@ extern "C" int leann_backend_to_rows(const leann_backend *hc, int row_type, lean
         leann_set_error("leann_backend_to_rows: a recompute-on index holds no vectors to convert");
         return LEANN_ERR_UNSUPPORTED;
     }
-    if (leann_internal_bf16(hc) || row_type != LEANN_ROWS_BF16) {
-        leann_set_error("leann_backend_to_rows: only f32 -> bf16 is supported (%s -> %s asked for); rebuild from the f32 rows for anything else",
-                        leann_internal_bf16(hc) ? "bf16" : "f32", row_type == LEANN_ROWS_BF16 ? "bf16" : "f32");
+    if (leann_internal_narrow_rows(hc) || row_type == LEANN_ROWS_F32) {
+        leann_set_error("leann_backend_to_rows: only f32 -> bf16 and f32 -> int8 are supported (%s -> %s asked for); rebuild from the f32 rows for anything else",
+                        leann_internal_row_name(hc), row_type == LEANN_ROWS_BF16 ? "bf16" : row_type == LEANN_ROWS_I8 ? "int8" : "f32");
         return LEANN_ERR_UNSUPPORTED;
     }
     try {
@@ -255,7 +262,7 @@ extern "C" int leann_backend_to_rows(const leann_backend *hc, int row_type, lean
         if (int rc = leann_backend_graph_export(hc, levels.data(), uo.data(), a0.data(), aU.data(), nullptr)) return rc; // (selects h's device)
         leann_backend *h = nullptr;
         int rc = leann_internal_from_host(hc->kind, n, hc->g.d, hc->g.M, hc->g.M0, hc->g.max_level, hc->g.entry, levels.data(), uo.data(), a0.data(),
-                                          aU.data(), hc->n_upper_lists, nullptr, nullptr, 0, 0, nullptr, hc->device, hc->key_offset, &h, LEANN_ROWS_BF16,
+                                          aU.data(), hc->n_upper_lists, nullptr, nullptr, 0, 0, nullptr, hc->device, hc->key_offset, &h, row_type,
                                           nullptr, n ? hc->g.X : nullptr, hc->g.ld);
         if (rc) return rc;
         leann_internal_take_build_params(h, hc); // (the arrays went through from_host, which knows no source handle)

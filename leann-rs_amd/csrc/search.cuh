@@ -389,6 +389,62 @@ __device__ __forceinline__ void wave_dist_rows_bf16(const float4 (&q)[T], const 
     }
 }
 
+// int8 rows (LEANN_ROWS_I8, rows_i8.hip): the stored row is int8 codes, [n x ldb] bytes in i8_row_pos order (i8_rows.h; ldb: dims rounded
+// up to 128 — whole 128-B lines, zero padded), so a lane's sixteen codes of a 1 024-element block (four chunks) come in ONE 16-byte load,
+// those of a 512-element tail in one 8-byte load, and the rest in 4 bytes per chunk.  The column scales 2^-e_j are applied to the QUERY
+// once (beam_search_one stages q'_j = q_j 2^-e_j, exact), so a row costs one conversion and one fmaf per element: q'_j c_ij is the
+// real number q_j Xq_ij, and the canonical order — lane l owns elements 256t+4l..+3, fma4 over t ascending, lane4_sum, wave_tree_sum,
+// 1 - sum — rounds it exactly as the f32 kernels do on the dequantised rows Xq.
+__device__ __forceinline__ uint32_t i8_tail_load(const int8_t *__restrict__ row, uint32_t ldb, int c, int lane) {
+    const uint32_t j = 256u * c + 4u * lane;
+    return j < ldb ? *reinterpret_cast<const uint32_t *>(row + j) : 0u;
+}
+template <int T>
+__device__ __forceinline__ void i8_row_load(const int8_t *__restrict__ row, uint32_t ldb, int lane, uint32_t (&v)[T]) {
+#pragma unroll
+    for (int b = 0; b < (T + 3) / 4; b++) {
+        const int c = 4 * b;
+        if (c + 4 <= T && 1024u * (uint32_t)(b + 1) <= ldb) {
+            const uint4 w = *reinterpret_cast<const uint4 *>(row + 1024 * b + 16 * lane);
+            v[c] = w.x; v[c + 1] = w.y; v[c + 2] = w.z; v[c + 3] = w.w;
+        } else { // the tail (< 1 024 elements): a 512-element pair where it fits, then element order
+            if (c + 2 <= T && 1024u * (uint32_t)b + 512u <= ldb) {
+                const uint2 w = *reinterpret_cast<const uint2 *>(row + 1024 * b + 8 * lane);
+                v[c] = w.x; v[c + 1] = w.y;
+            } else {
+                v[c] = i8_tail_load(row, ldb, c, lane);
+                if (c + 1 < T) v[c + 1] = i8_tail_load(row, ldb, c + 1, lane);
+            }
+            if (c + 2 < T) v[c + 2] = i8_tail_load(row, ldb, c + 2, lane);
+            if (c + 3 < T) v[c + 3] = i8_tail_load(row, ldb, c + 3, lane);
+        }
+    }
+}
+template <int T, int R>
+__device__ __forceinline__ void wave_dist_rows_i8(const float4 (&q)[T], const int8_t *__restrict__ Xb, uint32_t ldb,
+                                                  const uint32_t (&ids)[R], int nrows, int lane, float (&out)[R]) {
+    uint32_t v[R][T];
+#pragma unroll
+    for (int r = 0; r < R; r++)
+        if (r < nrows) i8_row_load<T>(Xb + (size_t)ids[r] * ldb, ldb, lane, v[r]);
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        if (r < nrows) {
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int t = 0; t < T; t++) {
+                float4 x;
+                x.x = (float)(int8_t)v[r][t];
+                x.y = (float)(int8_t)(v[r][t] >> 8);
+                x.z = (float)(int8_t)(v[r][t] >> 16);
+                x.w = (float)((int32_t)v[r][t] >> 24);
+                fma4(acc, q[t], x);
+            }
+            out[r] = 1.0f - wave_tree_sum(lane4_sum(acc));
+        }
+    }
+}
+
 // Recompute-on rows of exactly 256 bf16 features (+ inline norm), FOUR passages per wave instruction: the 16 lanes of a DPP row share a
 // passage, lane m of them owns elements 8m..8m+7 and 128+8m..128+8m+7 (two 16-byte loads; each instruction reads a contiguous 256-B
 // half of four rows), and one pass of the DPP ladder reduces four rows at once — against one row per 8-byte wave load and one
@@ -468,7 +524,9 @@ struct SearchLds {
 // keys of a lane and adds a second rank count; phases C and D already loop over n_new.  LW = 1 compiles to the narrow code unchanged.
 // SCREEN (throughput form of the plain f32 search only): phase C goes through the split planes (wave_dist_rows_screen; T = 3: its wide form).
 // BF16 (search_bf16.hip): the rows are bf16 (g.X names them, g.row_bytes apart); phase C and the entry go through wave_dist_rows_bf16.
-template <int T, int R, int NW, bool FEAT, bool FILT = false, bool G16 = false, int LW = 1, bool SCREEN = false, bool BF16 = false>
+// I8 (search_i8.hip): the rows are int8 codes (g.X, g.row_bytes apart) and g.norms names the column scales 2^-e_j [g.ld], which the
+// query staging multiplies into the query; phase C and the entry go through wave_dist_rows_i8.
+template <int T, int R, int NW, bool FEAT, bool FILT = false, bool G16 = false, int LW = 1, bool SCREEN = false, bool BF16 = false, bool I8 = false>
 __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_t qi, unsigned char *smem) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const auto *const za = lazy_search_args(); // arguments of the rare paths and of the epilogue: read where they are used
@@ -476,6 +534,7 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
     static_assert(LW == 1 || LW == 2, "lists of at most 128 ids");
     static_assert(!SCREEN || (NW == 4 && !FEAT && !FILT && !G16 && LW == 1), "the row screen exists in the plain throughput form only");
     static_assert(!BF16 || (!FEAT && !G16 && !SCREEN), "bf16 rows: stored vectors, whole rows");
+    static_assert(!I8 || (!FEAT && !G16 && !SCREEN && !BF16), "int8 rows: stored vectors, whole rows");
     const uint32_t maxdeg = g.M0 > g.M ? g.M0 : g.M;
     const uint32_t efp = (ef + 1) & ~1u;
     SearchLds s;
@@ -513,6 +572,16 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
 #pragma unroll
         for (int t = 0; t < T; t++)
             if (!G16) q[t] = vec_load4_guard(qv, dq, t, lane);
+        if constexpr (I8) { // q'_j = q_j 2^-e_j: exact (a query element below 2^-90 in magnitude: out of scope, leann_backend.h)
+#pragma unroll
+            for (int t = 0; t < T; t++) {
+                const uint32_t j = 256u * t + 4u * lane;
+                if (j < g.ld) { // g.ld is a multiple of 4; the scales of padding columns are 1
+                    const float4 sc = *reinterpret_cast<const float4 *>(g.norms + j);
+                    q[t].x *= sc.x; q[t].y *= sc.y; q[t].z *= sc.z; q[t].w *= sc.w;
+                }
+            }
+        }
         if (G16) {
 #pragma unroll
             for (int i = 0; i < 8; i++) {
@@ -544,6 +613,7 @@ __device__ void beam_search_one(const GraphView &g, const SearchArgs &a, uint32_
             dd[0] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dd[0]), 15));
         } else if (FEAT) wave_dist_rows_feat<T, 1>(q, reinterpret_cast<const char *>(g.X), g.row_bytes, g.feat_h, ids, 1, lane, dd, g.norms);
         else if constexpr (BF16) wave_dist_rows_bf16<T, 1>(q, reinterpret_cast<const uint16_t *>(g.X), g.row_bytes >> 1, ids, 1, lane, dd);
+        else if constexpr (I8) wave_dist_rows_i8<T, 1>(q, reinterpret_cast<const int8_t *>(g.X), g.row_bytes, ids, 1, lane, dd);
         else wave_dist_rows<T, 1>(q, g.X, g.ld, ids, 1, lane, dd);
         best = make_key(dd[0], g.entry); // every wave computes the same value
     }

@@ -1,6 +1,6 @@
 // search_plan.h — which beam-search kernel a call runs, with how many waves, which visited table and how much LDS: a pure function of
 // the index shape, the call and the debug knobs.  Plain C++ on purpose: leann_internal_launch_search (api.hip), the kernel tables of
-// api.hip and search_bf16.hip and the stand-alone host test (host/search_plan_selftest.cpp, tests/test_cpu_search_plan.py) compile the
+// api.hip, search_bf16.hip and search_i8.hip and the stand-alone host test (host/search_plan_selftest.cpp, tests/test_cpu_search_plan.py) compile the
 // same functions; nothing here needs a GPU.
 //
 //   family    taken when                 kernel<..>                       width -> T, R                    waves per query (NW)               visited table (hash_bits)
@@ -14,6 +14,8 @@
 //   BF16      bf16 rows                  [wide_]bf16_beam_search          T as F32, R = search_bf16_R4(T)  16: nq <= 512 and the width has a  as F32
 //                                        [_filtered]_kernel<T, R, NW>     / search_bf16_R16(T)             16-wave form (T < 16), else 4;
 //                                                                                                          LEANN_DEBUG_NW is IGNORED
+//   I8        int8 rows                  [wide_]i8_beam_search            T as F32, R = search_i8_R4(T)    as BF16 (its threshold: int8       as F32
+//                                        [_filtered]_kernel<T, R, NW>     / search_i8_R16(T)               batches were not swept)
 //   FEAT      recompute-on graph         [wide_]beam_search_feat          c = ceil(feat_h / 256): <1,      16: nq <= 512, else 4;             knob set: pick(ef); else 12 for
 //             (feat_h != 0)              [_filtered]_kernel<T, R, NW>     LEANN_FEAT_R1>, <2, 6>, c = 3    LEANN_DEBUG_NW is IGNORED          ef <= 64, else pick(ef) (at any
 //                                                                         and 4: <4, 4>                                                       width, construction refused)
@@ -67,13 +69,14 @@ LEANN_SP_HD inline size_t search_lds_bytes(uint32_t ef, uint32_t maxdeg, uint32_
     return b + ((size_t)1 << hash_bits) * 4;
 }
 
-enum SearchFamily { SEARCH_F32 = 0, SEARCH_SCREEN, SEARCH_BF16, SEARCH_FEAT, SEARCH_FEAT256 };
+enum SearchFamily { SEARCH_F32 = 0, SEARCH_SCREEN, SEARCH_BF16, SEARCH_FEAT, SEARCH_FEAT256, SEARCH_I8 };
 
 struct SearchShape {
     uint32_t ld, d, feat_h;
     bool bf16;
     uint32_t maxdeg;   // max(M0, M)
     bool screen_ready; // planes in place, the handle's row screen on, and leann_internal_screen_shape
+    bool i8 = false;   // int8 rows (rows_i8.hip); never together with bf16 or feat_h
 };
 struct SearchCall {
     uint32_t nq, k, ef; // ef: already max(ef, k)
@@ -100,6 +103,9 @@ constexpr int search_f32_R(int T) { return T <= 3 ? 4 : T == 4 ? 3 : T <= 8 ? 2 
 // bf16 rows, 4 / 16 waves per query (how they were chosen: search_bf16.hip); 0: no 16-wave form at this width
 constexpr int search_bf16_R4(int T) { return T <= 3 ? 8 : T == 4 ? 6 : T <= 8 ? 4 : 2; }
 constexpr int search_bf16_R16(int T) { return T <= 4 ? 4 : T == 6 ? 3 : T == 8 ? 2 : T == 12 ? 1 : 0; }
+// int8 rows, 4 / 16 waves per query (how they were chosen: search_i8.hip); 0: no 16-wave form at this width
+constexpr int search_i8_R4(int T) { return T == 1 ? 16 : T <= 4 ? 12 : T == 6 ? 8 : T == 8 ? 6 : 4; }
+constexpr int search_i8_R16(int T) { return T <= 6 ? 4 : T == 8 ? 3 : T == 12 ? 1 : 0; }
 // recompute-on rows: c = chunks of 256 features -> T (0: none), and R by T
 constexpr int search_feat_T(uint32_t c) { return c <= 2 ? (int)c : c <= 4 ? 4 : 0; }
 constexpr int search_feat_R(int T) { return T == 1 ? LEANN_FEAT_R1 : T == 2 ? 6 : 4; }
@@ -144,8 +150,8 @@ static inline SearchPlan search_plan(const SearchShape &s, const SearchCall &c, 
             p.R = search_feat_R(p.T);
         }
     } else {
-        if (s.bf16 && c.build) {
-            snprintf(p.msg, sizeof p.msg, "bf16 rows: construction searches are not supported");
+        if ((s.bf16 || s.i8) && c.build) {
+            snprintf(p.msg, sizeof p.msg, "%s rows: construction searches are not supported", s.i8 ? "int8" : "bf16");
             p.err = SEARCH_PLAN_UNSUPPORTED;
             return p;
         }
@@ -164,6 +170,10 @@ static inline SearchPlan search_plan(const SearchShape &s, const SearchCall &c, 
             p.family = SEARCH_BF16;
             p.NW = search_bf16_R16(p.T) && c.nq <= 512 ? 16 : 4;
             p.R = p.NW == 16 ? search_bf16_R16(p.T) : search_bf16_R4(p.T);
+        } else if (s.i8) { // the BF16 batch threshold: int8 batches were not swept on their own
+            p.family = SEARCH_I8;
+            p.NW = search_i8_R16(p.T) && c.nq <= 512 ? 16 : 4;
+            p.R = p.NW == 16 ? search_i8_R16(p.T) : search_i8_R4(p.T);
         } else {
             // Waves per query: 4 for throughput batches (4 workgroups per CU hide each other's dependent hops); 16 for small batches,
             // where the chip is mostly idle and the per-hop row fetch is the critical path — all ~40 new rows of a hop are then in
@@ -203,6 +213,7 @@ static inline int search_plan_name(const SearchPlan &p, char *buf, size_t cap) {
             return snprintf(buf, cap, "%sbeam_search_kernel<%d, %d, %d, %s>", w, p.T, p.R, p.NW, p.build ? "true" : "false");
         case SEARCH_SCREEN: return snprintf(buf, cap, "beam_search_screen_kernel<%d, %d>", p.T, p.R);
         case SEARCH_BF16: return snprintf(buf, cap, "%sbf16_beam_search%s_kernel<%d, %d, %d>", w, f, p.T, p.R, p.NW);
+        case SEARCH_I8: return snprintf(buf, cap, "%si8_beam_search%s_kernel<%d, %d, %d>", w, f, p.T, p.R, p.NW);
         case SEARCH_FEAT: return snprintf(buf, cap, "%sbeam_search_feat%s_kernel<%d, %d, %d>", w, f, p.T, p.R, p.NW);
         case SEARCH_FEAT256: return snprintf(buf, cap, "%sbeam_search_feat256%s_kernel<%d, %d>", w, f, p.R, p.NW);
         default: return snprintf(buf, cap, "(no kernel family %d)", p.family);

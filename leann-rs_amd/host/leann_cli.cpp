@@ -247,17 +247,20 @@ static int run_search(int argc, char **argv) {
 
 // leann build --index-dir DIR --passages-jsonl FILE [--backend-name hnsw|diskann] [--graph-degree 32]
 //             [--complexity 64] [--dimensions 128] [--embedding-mode synthetic|synthetic-linear] [--recompute] [--pruned]
-//             [--recompute-graph] [--row-type f32|bf16]
+//             [--recompute-graph] [--row-type f32|bf16|int8]
 // --recompute       also write documents.embeddings (only in recompute mode, src/index/builder.rs:105-113), so that the index can be
 //                   pruned later; off by default like the reference (meta.is_recompute = args.recompute)
 // --pruned          no ANN file and no embeddings: the reference's pruned state (brute-force recompute at query time)
 // --recompute-graph (needs --embedding-mode synthetic-linear) graph + compact encoder inputs, no vectors
 // --row-type        what the ANN file stores per element: f32 (default) or bf16 (half the file and device memory; the rows are rounded
-//                   first and the graph is built on the rounded rows, DESIGN.md "bf16 rows")
+//                   first and the graph is built on the rounded rows, DESIGN.md "bf16 rows") or int8 (a quarter: one power-of-two
+//                   scale per column and 8-bit codes, the graph built on the dequantised rows, DESIGN.md "int8 rows")
+static const char *row_type_name(int row_type) { return row_type == LEANN_ROWS_BF16 ? "bf16" : row_type == LEANN_ROWS_I8 ? "int8" : "f32"; }
 static int parse_row_type(const std::string &v) {
     if (v == "f32") return LEANN_ROWS_F32;
     if (v == "bf16") return LEANN_ROWS_BF16;
-    throw Error("invalid value '" + v + "' for '--row-type': expected f32 or bf16");
+    if (v == "int8") return LEANN_ROWS_I8;
+    throw Error("invalid value '" + v + "' for '--row-type': expected f32 or bf16, or int8");
 }
 static int run_build(int argc, char **argv) {
     std::string dir, jsonl, backend_name = "hnsw", mode = "synthetic";
@@ -348,7 +351,7 @@ static int run_build(int argc, char **argv) {
     }
     m.save(dir + "/documents.leann.meta.json");
     printf("Indexed %zu passages (%zu dims, backend %s%s) into %s\n", n, dims, backend_name.c_str(),
-           rgraph ? ", recompute-on graph (no vectors)" : pruned ? ", pruned" : row_type == LEANN_ROWS_BF16 ? ", bf16 rows" : "", dir.c_str());
+           rgraph ? ", recompute-on graph (no vectors)" : pruned ? ", pruned" : row_type == LEANN_ROWS_BF16 ? ", bf16 rows" : row_type == LEANN_ROWS_I8 ? ", int8 rows" : "", dir.c_str());
     return 0;
 }
 
@@ -404,8 +407,8 @@ static int run_delete(int argc, char **argv) {
     return 0;
 }
 
-// leann convert <index> --row-type bf16   (additive)
-// Rewrites the ANN file of an existing f32 index with bf16 rows: open -> leann_backend_to_rows -> save.  The graph stays the one that
+// leann convert <index> --row-type bf16|int8   (additive)
+// Rewrites the ANN file of an existing f32 index with bf16 or int8 rows: open -> leann_backend_to_rows -> save.  The graph stays the one that
 // was built on the exact rows; removals (the tombstone sidecar) are carried over.  Passages, ids and meta files are not touched: the
 // row type lives in the index file alone.
 static int run_convert(int argc, char **argv) {
@@ -414,7 +417,7 @@ static int run_convert(int argc, char **argv) {
     for (int i = 0; i < argc; i++) {
         std::string s = argv[i];
         auto val = [&]() -> std::string { if (i + 1 >= argc) throw Error("a value is required for '" + s + "' but none was supplied"); return argv[++i]; };
-        if (s == "-h" || s == "--help") { puts("Rewrite an index with another row type\n\nUsage: leann convert <INDEX> --row-type bf16"); return 0; }
+        if (s == "-h" || s == "--help") { puts("Rewrite an index with another row type\n\nUsage: leann convert <INDEX> --row-type bf16|int8"); return 0; }
         else if (s == "--row-type") row_type = parse_row_type(val());
         else if (s == "-i" || s == "--index") index_name = val();
         else if (!s.empty() && s[0] == '-' && s.size() > 1) throw Error("unexpected argument '" + s + "' found");
@@ -422,7 +425,7 @@ static int run_convert(int argc, char **argv) {
         else throw Error("unexpected argument '" + s + "' found");
     }
     if (index_name.empty()) throw Error("the following required arguments were not provided:\n  <INDEX>");
-    if (row_type < 0) throw Error("the following required arguments were not provided:\n  --row-type <f32|bf16>");
+    if (row_type < 0) throw Error("the following required arguments were not provided:\n  --row-type <f32|bf16|int8>");
     std::string index_path = find_index(index_name) + "/documents.leann";
     IndexMeta meta = IndexMeta::load(index_path + ".meta.json");
     int backend = meta.backend_name == "hnsw" ? LEANN_BACKEND_HNSW : meta.backend_name == "diskann" ? LEANN_BACKEND_DISKANN : -1;
@@ -431,7 +434,7 @@ static int run_convert(int argc, char **argv) {
     check(leann_backend_open(index_path.c_str(), backend, meta.dimensions, "0", &h));
     if (leann_backend_row_type(h) == row_type) {
         leann_backend_close(h);
-        printf("Index '%s': rows are %s already\n", index_name.c_str(), row_type == LEANN_ROWS_BF16 ? "bf16" : "f32");
+        printf("Index '%s': rows are %s already\n", index_name.c_str(), row_type_name(row_type));
         return 0;
     }
     int rc = leann_backend_to_rows(h, row_type, &b);
@@ -440,14 +443,14 @@ static int run_convert(int argc, char **argv) {
     if (b) leann_backend_close(b);
     leann_backend_close(h);
     check(rc);
-    printf("Index '%s': %zu rows rewritten as %s\n", index_name.c_str(), n, row_type == LEANN_ROWS_BF16 ? "bf16" : "f32");
+    printf("Index '%s': %zu rows rewritten as %s\n", index_name.c_str(), n, row_type_name(row_type));
     return 0;
 }
 
 int main(int argc, char **argv) {
     try {
         if (argc < 2 || !strcmp(argv[1], "-h") || !strcmp(argv[1], "--help")) {
-            puts("LEANN search path on MI355X\n\nUsage: leann <COMMAND>\n\nCommands:\n  search  Query an index\n  build   Build an index from a passages JSONL (synthetic embeddings)\n  delete  Remove passages from an index\n  convert Rewrite an index with another row type (f32 -> bf16)\n");
+            puts("LEANN search path on MI355X\n\nUsage: leann <COMMAND>\n\nCommands:\n  search  Query an index\n  build   Build an index from a passages JSONL (synthetic embeddings)\n  delete  Remove passages from an index\n  convert Rewrite an index with another row type (f32 -> bf16, f32 -> int8)\n");
             return argc < 2 ? 2 : 0;
         }
         if (!strcmp(argv[1], "--version") || !strcmp(argv[1], "-V")) { printf("leann %s\n", leann_version()); return 0; }

@@ -2,7 +2,8 @@
 //   no argument: plans every point of a grid of shapes, calls and knobs and checks the invariants below; one JSON line, exit status 1
 //                on any violation.
 //   --plans:     reads one case per line from stdin, "ld d feat_h bf16 maxdeg screen_ready nq k ef filtered build hash_bits nw no_feat256",
-//                and prints one JSON line per case: what tests/test_cpu_search_plan.py holds to its hand-written rows.
+//                and prints one JSON line per case: what tests/test_cpu_search_plan.py holds to its hand-written rows.  An optional
+//                fifteenth column "i8" (default 0) plans for int8 rows (tests/test_cpu_i8_rows.py).
 #include "../csrc/search_plan.h"
 #include <cstdlib>
 #include <cstring>
@@ -10,8 +11,8 @@
 #include <string>
 
 static const char *family_name(int f) {
-    static const char *const names[] = {"F32", "SCREEN", "BF16", "FEAT", "FEAT256"};
-    return f >= 0 && f < 5 ? names[f] : "?";
+    static const char *const names[] = {"F32", "SCREEN", "BF16", "FEAT", "FEAT256", "I8"};
+    return f >= 0 && f < 6 ? names[f] : "?";
 }
 
 // "name<a, b, ..>" back into the fields of a plan that name a kernel; false: not a traversal kernel's name
@@ -61,15 +62,16 @@ static bool parse_name(const char *s, SearchPlan *out) {
 static int print_plans() {
     char line[256];
     while (fgets(line, sizeof line, stdin)) {
-        unsigned ld, d, feat_h, bf16, maxdeg, screen, nq, k, ef, filtered, build, no_feat256;
+        unsigned ld, d, feat_h, bf16, maxdeg, screen, nq, k, ef, filtered, build, no_feat256, i8 = 0;
         int hash_bits, nw;
-        if (sscanf(line, "%u %u %u %u %u %u %u %u %u %u %u %d %d %u", &ld, &d, &feat_h, &bf16, &maxdeg, &screen, &nq, &k, &ef, &filtered, &build,
-                   &hash_bits, &nw, &no_feat256) != 14) {
+        if (sscanf(line, "%u %u %u %u %u %u %u %u %u %u %u %d %d %u %u", &ld, &d, &feat_h, &bf16, &maxdeg, &screen, &nq, &k, &ef, &filtered, &build,
+                   &hash_bits, &nw, &no_feat256, &i8) < 14) {
             fprintf(stderr, "search_plan_selftest: bad case line: %s", line);
             return 2;
         }
         SearchShape s = {};
         s.ld = ld; s.d = d; s.feat_h = feat_h; s.bf16 = bf16 != 0; s.maxdeg = maxdeg; s.screen_ready = screen != 0;
+        s.i8 = i8 != 0;
         const SearchCall c = {nq, k, ef, filtered != 0, build != 0};
         const SearchKnobs kn = {hash_bits, nw, no_feat256 != 0};
         const SearchPlan p = search_plan(s, c, kn);
