@@ -349,12 +349,9 @@ int leann_internal_search_plain(leann_backend *h, const float *d_queries, size_t
         leann_set_error("exact filtered search needs stored vectors; this index recomputes them from features (use leann_recompute_search_batch_device with an allow mask)");
         return LEANN_ERR_UNSUPPORTED;
     }
-    if (f.exact && leann_internal_bf16(h)) {
-        leann_set_error("exact filtered search scans f32 rows; this index stores bf16 rows (use the filtered walk: mode 0, or mode 2 which picks it)");
-        return LEANN_ERR_UNSUPPORTED;
-    }
-    if (f.exact && leann_internal_i8(h)) {
-        leann_set_error("exact filtered search scans f32 rows; this index stores int8 rows (use the filtered walk: mode 0, or mode 2 which picks it)");
+    if (f.exact && leann_internal_narrow_rows(h)) {
+        leann_set_error("exact filtered search scans f32 rows; this index stores %s rows (use the filtered walk: mode 0, or mode 2 which picks it)",
+                        leann_internal_row_name(h));
         return LEANN_ERR_UNSUPPORTED;
     }
     if (h->g.n == 0) {
@@ -678,7 +675,8 @@ static int search_filtered_batch_host_impl(const leann_backend *hc, const float 
         std::lock_guard<std::mutex> lk(h->mu);
         const GraphView &gv = h->sharded ? leann_internal_sharded_shard(h->sharded, 0)->g : h->g; // (shards share one configuration)
         const leann_backend *const h0 = h->sharded ? leann_internal_sharded_shard(h->sharded, 0) : h;
-        const size_t elem_bytes = leann_internal_i8(h0) ? 1 : leann_internal_bf16(h0) ? 2 : 4;
+        const NarrowRows *const t = leann_internal_narrow(h0->row_type);
+        const size_t elem_bytes = t ? t->elem_bytes : 4;
         for (size_t i = 0; i < ns * nq; i++) {
             h->stats.n_dist_evals += hstats[i * 4 + 0];
             h->stats.n_hops_base += hstats[i * 4 + 1];
@@ -960,42 +958,20 @@ extern "C" int leann_backend_graph_export(const leann_backend *h, uint8_t *level
     if (adjU && h->n_upper_lists)
         HIP_CHECK_RET(hipMemcpy(adjU, h->g.adjU, h->n_upper_lists * h->g.M * 4, hipMemcpyDeviceToHost));
     if (vectors && h->g.feat_h) { leann_set_error("graph_export: a recompute-on index holds no vectors"); return LEANN_ERR_UNSUPPORTED; }
-    if (vectors && leann_internal_bf16(h)) {
-        // w(rows): exact.  The bf16 rows land in the SECOND half of the caller's own buffer (n d u16 = half of n d f32) and are widened
-        // in place, front to back: element i is written at bytes 4 i .. 4 i + 3 and read from bytes 2 n d + 2 i, which no earlier
-        // write has reached (4 i + 4 <= 2 n d + 2 i + 2 for every i < n d).
-        const size_t nd = n * (size_t)h->g.d;
-        unsigned char *base = reinterpret_cast<unsigned char *>(vectors);
-        try { // (the device-to-host staging slab is a std::vector)
-            if (int rc = leann_internal_bf16_to_host(h, 0, n, reinterpret_cast<uint16_t *>(base + 2 * nd))) return rc;
-        } catch (const std::exception &e) {
-            leann_set_error("leann_backend_graph_export: %s", e.what());
-            return LEANN_ERR_IO;
-        }
-        for (size_t i = 0; i < nd; i++) {
-            uint16_t b;
-            memcpy(&b, base + 2 * nd + 2 * i, 2);
-            const uint32_t w = (uint32_t)b << 16;
-            memcpy(base + 4 * i, &w, 4);
-        }
-        return LEANN_OK;
-    }
-    if (vectors && leann_internal_i8(h)) {
-        // Xq = code x 2^-e: exact.  The codes land in the LAST quarter of the caller's own buffer (n d bytes of 4 n d) and are dequantised
-        // in place, front to back: element i is written at bytes 4 i .. 4 i + 3 and read from byte 3 n d + i, which no earlier write
-        // has reached (4 i + 4 <= 3 n d + i + 1 for every i < n d).
+    if (const NarrowRows *t = vectors ? leann_internal_narrow(h->row_type) : nullptr) {
+        // The widened rows: exact.  The narrow rows, e = elem_bytes each, land at the END of the caller's own buffer — e n d bytes of
+        // 4 n d — and are widened in place, front to back: element i is written at bytes 4 i .. 4 i + 3 and read from bytes
+        // (4 - e) n d + e i onward, which no earlier write has reached: 4 i + 4 <= (4 - e) n d + e i + e  <=>  (4 - e)(i + 1) <=
+        // (4 - e) n d, true for every i < n d.
         const size_t d = h->g.d, nd = n * d;
-        unsigned char *base = reinterpret_cast<unsigned char *>(vectors);
-        try {
-            if (int rc = leann_internal_i8_to_host(h, 0, n, reinterpret_cast<int8_t *>(base + 3 * nd))) return rc;
+        unsigned char *base = reinterpret_cast<unsigned char *>(vectors), *narrow = base + (4 - t->elem_bytes) * nd;
+        try { // (the device-to-host staging slab is a std::vector)
+            if (int rc = leann_internal_narrow_to_host(h, 0, n, narrow)) return rc;
         } catch (const std::exception &e) {
             leann_set_error("leann_backend_graph_export: %s", e.what());
             return LEANN_ERR_IO;
         }
-        for (size_t i = 0; i < nd; i++) {
-            const float x = (float)(int8_t)base[3 * nd + i] * ldexpf(1.0f, -h->i8_exps[i % d]);
-            memcpy(base + 4 * i, &x, 4);
-        }
+        t->widen(narrow, nd, d, h->i8_exps.data(), base);
         return LEANN_OK;
     }
     if (vectors)

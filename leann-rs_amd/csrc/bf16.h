@@ -1,5 +1,5 @@
 // bf16.h — the one f32 -> bf16 rounding of the library, for host and device code alike (recompute.hip's synthetic features, the bf16
-// row store of rows_bf16.hip, leann_round_bf16).  Round to nearest even; a NaN stays a NaN (its quiet bit is set, so that a payload
+// rounding kernel of rows_bf16.hip, leann_round_bf16).  Round to nearest even; a NaN stays a NaN (its quiet bit is set, so that a payload
 // living in the low 16 bits alone cannot round to an infinity).  The widening back is exact: (uint32_t)b << 16.
 #pragma once
 #include <stdint.h>

@@ -736,7 +736,7 @@ extern "C" int leann_backend_build_device(int backend, const float *d_vectors, s
                                           int take_copy, leann_backend **out) {
     return build_device_guarded(backend, d_vectors, n, dims, ld, graph_degree, complexity, device, key_offset, take_copy, out, true);
 }
-// the device build WITHOUT the row screen's split planes: for a caller that replaces the f32 rows afterwards (rows_bf16.hip) — the
+// the device build WITHOUT the row screen's split planes: for a caller that replaces the f32 rows afterwards (narrow_rows.hip) — the
 // planes would be a second full-size copy of rows that are about to go
 int leann_internal_build_device_no_planes(int backend, const float *d_vectors, size_t n, size_t dims, size_t ld, size_t graph_degree,
                                           size_t complexity, int device, uint64_t key_offset, leann_backend **out) {

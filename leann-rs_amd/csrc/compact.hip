@@ -207,8 +207,10 @@ int compact_checked(const leann_backend *src, const CompactChecked &c, uint64_t 
     DeviceBuf<unsigned char> rows;
     if (rows.alloc(std::max<size_t>(live * pitch, 128))) return LEANN_ERR_DEVICE;
     leann_internal_own_rows(h.get(), std::move(rows));
-    if (leann_internal_i8(src)) // the codes move byte for byte: the columns keep their exponents
-        if (int rc = leann_internal_i8_carry_exponents(src, h.get())) return rc;
+    if (leann_internal_i8(src)) { // the codes move byte for byte: the columns keep their exponents
+        h->i8_exps = src->i8_exps;
+        if (int rc = leann_internal_i8_bind_scales(h.get())) return rc;
+    }
     const unsigned list_grid = (unsigned)std::min<size_t>((live + 3) / 4, (size_t)1 << 16); // four waves = four nodes per block
     PhaseClock phases;
     phases.mark(0);

@@ -1,5 +1,5 @@
 // handle.hip — making a leann_backend: the steps every way in shares, stated once (contracts: internal.h).  Host code only, no
-// kernel.  A new way in starts here; build.hip, compact.hip, rows_bf16.hip, indexfile.hip and shard.hip keep only what is their own.
+// kernel.  A new way in starts here; build.hip, compact.hip, narrow_rows.hip, indexfile.hip and shard.hip keep only what is their own.
 #include "common.cuh"
 #include "internal.h"
 
@@ -142,20 +142,26 @@ static const char *validate_graph(size_t n, uint32_t M, uint32_t M0, uint32_t ma
 int leann_internal_from_host(int backend, size_t n, size_t dims, uint32_t M, uint32_t M0, uint32_t max_level, uint32_t entry,
                              const uint8_t *levels, const uint32_t *upper_off, const uint32_t *adj0, const uint32_t *adjU,
                              size_t n_upper_lists, const float *vectors, const unsigned char *feat_rows, uint32_t feat_h, uint32_t row_bytes,
-                             const float *Wf32, int device, uint64_t key_offset, leann_backend **out, int row_type, const uint16_t *bf16_rows,
-                             const float *d_f32_rows, size_t d_f32_ld, const int8_t *i8_codes, const int8_t *i8_exps) {
-    const bool feat = feat_rows != nullptr, bf16 = row_type == LEANN_ROWS_BF16, i8 = row_type == LEANN_ROWS_I8;
-    if (row_type != LEANN_ROWS_F32 && row_type != LEANN_ROWS_BF16 && row_type != LEANN_ROWS_I8) {
+                             const float *Wf32, int device, uint64_t key_offset, leann_backend **out, int row_type, const NarrowSource *narrow) {
+    const bool feat = feat_rows != nullptr;
+    const NarrowRows *const t = leann_internal_narrow(row_type);
+    if (row_type != LEANN_ROWS_F32 && !t) {
         leann_set_error("leann_backend_from_arrays: unknown row type %d (LEANN_ROWS_F32, LEANN_ROWS_BF16 or LEANN_ROWS_I8)", row_type);
         return LEANN_ERR_INVALID;
     }
-    const void *const narrow_rows = bf16 ? (const void *)bf16_rows : (const void *)i8_codes; // an index file's rows in the handle's own type
-    if (((bf16 || i8) && (feat || (vectors != nullptr) + (narrow_rows != nullptr) + (d_f32_rows != nullptr) > 1 || (d_f32_rows && d_f32_ld < dims))) ||
-        (!bf16 && !i8 && d_f32_rows) || (!bf16 && bf16_rows) || (!i8 && (i8_codes || i8_exps)) || (i8_codes && !i8_exps)) {
+    // the rows come ONE way: recompute-on rows, host f32 `vectors`, or — a narrow type only — one of `narrow`'s two sources
+    const NarrowSource src = narrow ? *narrow : NarrowSource{};
+    const int ways = (vectors != nullptr) + (src.file_rows != nullptr) + (src.d_f32 != nullptr);
+    bool bad = false;
+    if (!t) bad = src.file_rows || src.exps || src.d_f32;                  // f32 and recompute-on handles take nothing from `narrow`
+    else if (feat || ways > 1) bad = true;
+    else if (src.d_f32 && src.d_ld < dims) bad = true;
+    else if (t->fit ? (src.file_rows && !src.exps) : src.exps != nullptr) bad = true; // a file's exponents come with its rows, for a type that has any
+    if (bad) {
         leann_set_error("leann_backend_from_arrays: invalid arguments");
         return LEANN_ERR_INVALID;
     }
-    if (!out || dims == 0 || dims > 4096 || n >= (1ull << 31) || (n && ((!vectors && !feat && !narrow_rows && !d_f32_rows) || !adj0 || !upper_off)) ||
+    if (!out || dims == 0 || dims > 4096 || n >= (1ull << 31) || (n && ((!ways && !feat) || !adj0 || !upper_off)) ||
         (backend != LEANN_BACKEND_HNSW && backend != LEANN_BACKEND_DISKANN) ||
         (feat && (!Wf32 || feat_h == 0 || (feat_h & 3) || feat_h > 1024 || row_bytes < 2 * feat_h + 4 || (row_bytes & 7)))) {
         leann_set_error("leann_backend_from_arrays: invalid arguments");
@@ -215,12 +221,8 @@ int leann_internal_from_host(int backend, size_t n, size_t dims, uint32_t M, uin
         leann_internal_own_rows(h, std::move(rows));
         if (h->Wf32.alloc((size_t)feat_h * dims)) return fail(nullptr);
         if (hipMemcpy(h->Wf32, Wf32, (size_t)feat_h * dims * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("upload of the weights");
-    } else if (bf16) {
-        const int rc = d_f32_rows ? leann_internal_bf16_adopt_device(h, d_f32_rows, d_f32_ld) : leann_internal_bf16_adopt_host(h, vectors, bf16_rows);
-        if (rc) { leann_backend_close(h); return rc; }
-    } else if (i8) {
-        const int rc = d_f32_rows ? leann_internal_i8_adopt_device(h, d_f32_rows, d_f32_ld, "leann_backend_to_rows")
-                                  : leann_internal_i8_adopt_host(h, vectors, i8_codes, i8_exps);
+    } else if (t) {
+        const int rc = leann_internal_narrow_adopt(h, t, vectors, src, src.d_f32 ? "leann_backend_to_rows" : "leann_backend_from_arrays_rows");
         if (rc) { leann_backend_close(h); return rc; }
     } else {
         DeviceBuf<float> rows;

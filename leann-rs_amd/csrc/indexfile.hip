@@ -7,9 +7,9 @@
 //   version 1: rows = unpadded f32 vectors [n x d];
 //   version 2: recompute-on index (no vectors): rows = [n x row_bytes] {bf16 features | f32 ||W^T f|| | pad}, followed by the encoder
 //              weights as f32 [feat_h x d] — what `is_pruned` (src/index/meta.rs:38-42, src/cli/prune.rs:17-79) means for a graph index.
-//   version 3: bf16 rows (rows_bf16.hip): header and graph arrays as version 1, rows = unpadded bf16 [n x d] in element order.
-//   version 4: int8 rows (rows_i8.hip): header and graph arrays as version 1, then the column exponents int8 [d] (each in [-32, 32]) and
-//              the codes int8 [n x d] in element order (never -128).
+//   versions 3, 4: narrow rows (narrow_rows.h names the version of each type; 3: bf16, 4: int8): header and graph arrays as version 1,
+//              rows = unpadded [n x d] of the type in element order; int8 rows come behind their column exponents int8 [d] (each in
+//              [-32, 32]), and no code is -128.
 // The header is checked against the file length BEFORE anything is allocated, every array is validated against n before it is
 // uploaded (handle.hip:validate_graph), and no exception crosses the C boundary.
 //
@@ -62,15 +62,16 @@ static_assert(sizeof(FileHeader) == 128, "index file header is 128 bytes");
 static uint64_t payload_bytes(const FileHeader &hd) {
     const uint64_t n = hd.n;
     uint64_t b = n + 4 * n + 4 * n * hd.M0 + 4 * hd.n_upper_lists * hd.M;
+    const NarrowRows *t = leann_internal_narrow_of_version(hd.version);
     if (hd.version == 2) b += n * hd.row_bytes + 4ull * hd.feat_h * hd.d;
-    else if (hd.version == 4) b += hd.d + n * hd.d;
-    else b += (hd.version == 3 ? 2 : 4) * n * hd.d;
+    else b += (t && t->row_type == LEANN_ROWS_I8 ? hd.d : 0) + (t ? t->elem_bytes : 4) * n * hd.d; // (int8: the column exponents in front)
     return b;
 }
 
 int leann_internal_save_to(const leann_backend *h, const std::string &path) {
     const size_t n = h->g.n, d = h->g.d;
-    const bool feat = h->g.feat_h != 0, bf16 = leann_internal_bf16(h), i8 = leann_internal_i8(h);
+    const bool feat = h->g.feat_h != 0, i8 = leann_internal_i8(h);
+    const NarrowRows *const t = leann_internal_narrow(h->row_type);
     std::vector<uint8_t> levels(std::max<size_t>(n, 1));
     std::vector<uint32_t> uo(std::max<size_t>(n, 1)), a0(std::max<size_t>(n * h->g.M0, 1)),
         aU(std::max<size_t>(h->n_upper_lists * h->g.M, 1));
@@ -83,12 +84,12 @@ int leann_internal_save_to(const leann_backend *h, const std::string &path) {
     if (!f) { leann_set_error("cannot create %s", tmp.c_str()); return LEANN_ERR_IO; }
     FileHeader hd{};
     memcpy(hd.magic, "LEANNGX1", 8);
-    hd.version = feat ? 2 : bf16 ? 3 : i8 ? 4 : 1; hd.kind = (uint32_t)h->kind; hd.n = n; hd.d = (uint32_t)d; hd.M = h->g.M; hd.M0 = h->g.M0;
+    hd.version = feat ? 2 : t ? t->file_version : 1; hd.kind = (uint32_t)h->kind; hd.n = n; hd.d = (uint32_t)d; hd.M = h->g.M; hd.M0 = h->g.M0;
     hd.max_level = h->g.max_level; hd.entry = h->g.entry; hd.efc = h->efc; hd.alpha = h->alpha;
     hd.n_upper_lists = h->n_upper_lists;
     hd.one_stage = (h->kind == LEANN_BACKEND_DISKANN && !h->two_stage) ? 1 : 0;
     hd.feat_h = h->g.feat_h;
-    hd.row_bytes = feat ? (uint32_t)leann_internal_feat_file_row_bytes(h->g) : bf16 || i8 ? 0u : h->g.row_bytes; // (the store's pitch is not the file's business)
+    hd.row_bytes = feat ? (uint32_t)leann_internal_feat_file_row_bytes(h->g) : t ? 0u : h->g.row_bytes; // (the store's pitch is not the file's business)
     bool ok = fwrite(&hd, sizeof(hd), 1, f) == 1;
     ok = ok && (n == 0 || fwrite(levels.data(), 1, n, f) == n);
     ok = ok && (n == 0 || fwrite(uo.data(), 4, n, f) == n);
@@ -96,16 +97,15 @@ int leann_internal_save_to(const leann_backend *h, const std::string &path) {
     ok = ok && (h->n_upper_lists == 0 || fwrite(aU.data(), 4, h->n_upper_lists * h->g.M, f) == h->n_upper_lists * h->g.M);
     ok = ok && (!i8 || (h->i8_exps.size() == d && fwrite(h->i8_exps.data(), 1, d, f) == d));
     // rows in slabs of <= 256 MiB: a 10M x 768 index is 30 GB, more than some hosts want to hold twice
-    const size_t row_b = feat ? leann_internal_feat_file_row_bytes(h->g) : bf16 ? d * 2 : i8 ? d : d * 4, dev_pitch = feat ? h->g.row_bytes : (size_t)h->g.ld * 4;
+    const size_t row_b = feat ? leann_internal_feat_file_row_bytes(h->g) : d * (t ? t->elem_bytes : 4), dev_pitch = feat ? h->g.row_bytes : (size_t)h->g.ld * 4;
     const size_t slab_rows = std::max<size_t>(1, ((size_t)256 << 20) / std::max<size_t>(row_b, 1));
     std::vector<unsigned char> slab(std::min(slab_rows, std::max<size_t>(n, 1)) * row_b);
     for (size_t r0 = 0; ok && r0 < n; r0 += slab_rows) {
         const size_t rows = std::min(slab_rows, n - r0);
         if (feat ? leann_internal_feat_rows_to_host(h, r0, rows, slab.data()) != LEANN_OK
-            : bf16 ? leann_internal_bf16_to_host(h, r0, rows, reinterpret_cast<uint16_t *>(slab.data())) != LEANN_OK
-            : i8 ? leann_internal_i8_to_host(h, r0, rows, reinterpret_cast<int8_t *>(slab.data())) != LEANN_OK
-                 : hipMemcpy2D(slab.data(), row_b, reinterpret_cast<const unsigned char *>(h->g.X) + r0 * dev_pitch, dev_pitch, row_b, rows,
-                               hipMemcpyDeviceToHost) != hipSuccess) {
+            : t ? leann_internal_narrow_to_host(h, r0, rows, slab.data()) != LEANN_OK
+                : hipMemcpy2D(slab.data(), row_b, reinterpret_cast<const unsigned char *>(h->g.X) + r0 * dev_pitch, dev_pitch, row_b, rows,
+                              hipMemcpyDeviceToHost) != hipSuccess) {
             fclose(f);
             (void)remove(tmp.c_str());
             leann_set_error("leann_backend_save: device read failed: %s", hipGetErrorString(hipGetLastError()));
@@ -189,7 +189,7 @@ static int load_own_file(const std::string &path, int backend, size_t dims, int 
         leann_set_error("Failed to load index: %s in %s", msg, path.c_str());
         return (int)LEANN_ERR_FORMAT;
     };
-    if (hd.version < 1 || hd.version > 4) return bad("unsupported version");
+    if (hd.version != 1 && hd.version != 2 && !leann_internal_narrow_of_version(hd.version)) return bad("unsupported version");
     if (hd.kind != (uint32_t)backend) return bad(backend == LEANN_BACKEND_HNSW ? "the file holds a DiskANN graph, an HNSW index was asked for"
                                                                                  : "the file holds an HNSW graph, a DiskANN index was asked for");
     if (hd.d == 0 || hd.d > 4096 || hd.M == 0 || hd.M > 128 || hd.M0 == 0 || hd.M0 > 128 || hd.n >= (1ull << 31) || hd.max_level > 15 ||
@@ -205,10 +205,11 @@ static int load_own_file(const std::string &path, int backend, size_t dims, int 
         return LEANN_ERR_FORMAT;
     }
     const size_t n = hd.n, d = hd.d;
-    const bool feat = hd.version == 2, bf16 = hd.version == 3, i8 = hd.version == 4;
+    const NarrowRows *const t = leann_internal_narrow_of_version(hd.version);
+    const bool feat = hd.version == 2, i8 = t && t->row_type == LEANN_ROWS_I8;
     std::vector<uint8_t> levels(std::max<size_t>(n, 1));
     std::vector<uint32_t> uo(std::max<size_t>(n, 1)), a0(std::max<size_t>(n * hd.M0, 1)), aU(std::max<size_t>(hd.n_upper_lists * hd.M, 1));
-    const size_t file_row_b = feat ? (size_t)hd.row_bytes : bf16 ? d * 2 : i8 ? d : d * 4;
+    const size_t file_row_b = feat ? (size_t)hd.row_bytes : d * (t ? t->elem_bytes : 4);
     std::vector<unsigned char> rows(std::max<size_t>(n * file_row_b, 4));
     std::vector<int8_t> exps(i8 ? d : 0);
     std::vector<float> W(feat ? (size_t)hd.feat_h * d : 0);
@@ -227,12 +228,11 @@ static int load_own_file(const std::string &path, int backend, size_t dims, int 
             leann_set_error("Failed to load index: %s in %s", msg, path.c_str());
             return LEANN_ERR_FORMAT;
         }
+    const NarrowSource src{rows.data(), i8 ? exps.data() : nullptr, nullptr, 0};
     int rc = leann_internal_from_host(backend, n, d, hd.M, hd.M0, hd.max_level, hd.entry, levels.data(), uo.data(), a0.data(), aU.data(),
-                                      hd.n_upper_lists, feat || bf16 || i8 ? nullptr : reinterpret_cast<const float *>(rows.data()), feat ? rows.data() : nullptr,
-                                      hd.feat_h, hd.row_bytes, feat ? W.data() : nullptr, device, 0, out,
-                                      bf16 ? LEANN_ROWS_BF16 : i8 ? LEANN_ROWS_I8 : LEANN_ROWS_F32,
-                                      bf16 ? reinterpret_cast<const uint16_t *>(rows.data()) : nullptr, nullptr, 0,
-                                      i8 ? reinterpret_cast<const int8_t *>(rows.data()) : nullptr, i8 ? exps.data() : nullptr);
+                                      hd.n_upper_lists, feat || t ? nullptr : reinterpret_cast<const float *>(rows.data()), feat ? rows.data() : nullptr,
+                                      hd.feat_h, hd.row_bytes, feat ? W.data() : nullptr, device, 0, out, t ? t->row_type : (int)LEANN_ROWS_F32,
+                                      t ? &src : nullptr);
     if (rc == LEANN_ERR_FORMAT) { // validate_graph: keep the reason, name the file
         std::string msg = leann_last_error();
         leann_set_error("Failed to load index: %s (%s)", msg.c_str(), path.c_str());
@@ -337,10 +337,10 @@ extern "C" int leann_backend_open(const char *index_path_stem, int backend, size
         return LEANN_ERR_INVALID;
     }
     if (leann_internal_spec_is_sharded(device_spec)) { // "0-7", "0,1,2,3": one handle over per-device shards (shard.hip)
-        const uint32_t version = index_file_version(leann_internal_index_file(index_path_stem, backend));
-        if (version == 3 || version == 4) { // (partitioning rebuilds per-shard graphs from f32 rows)
+        if (const NarrowRows *t = leann_internal_narrow_of_version(index_file_version(leann_internal_index_file(index_path_stem, backend)))) {
+            // (partitioning rebuilds per-shard graphs from f32 rows)
             leann_set_error("leann_backend_open: sharded open of an index of %s rows is not supported; build each shard with "
-                            "leann_backend_build_device_rows and join them with leann_sharded_from_handles", version == 3 ? "bf16" : "int8");
+                            "leann_backend_build_device_rows and join them with leann_sharded_from_handles", t->name);
             return LEANN_ERR_UNSUPPORTED;
         }
         return leann_internal_open_sharded_backend(index_path_stem, backend, dims, device_spec, out);

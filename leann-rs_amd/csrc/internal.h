@@ -1,6 +1,6 @@
 // internal.h — structs and functions shared by the .hip files (not part of the C ABI).  Every leann_internal_* function is declared
-// once, here (the four allocation functions: device_mem.h).  Whatever a handle holds on its device is a DeviceBuf member of
-// leann_backend / GraphStore, or a ScratchLease: `delete` frees it, nothing is freed by hand.
+// once, here (the four allocation functions: device_mem.h; the narrow row store: narrow_rows.h, included below).  Whatever a handle
+// holds on its device is a DeviceBuf member of leann_backend / GraphStore, or a ScratchLease: `delete` frees it, nothing is freed by hand.
 #pragma once
 #include "search.cuh"
 #include "device_mem.h"
@@ -54,8 +54,8 @@ extern std::atomic<uint64_t> leann_internal_device_blocks; // api.hip: blocks ow
 // What a plain handle's graph owns on its device.  GraphView (search.cuh) is the kernels' read-only view of it: its pointers are set
 // from these members next to the allocation that fills them.  Builder and graph repair write through the members.
 struct GraphStore {
-    DeviceBuf<unsigned char> rows; // f32 rows, the bf16 store or feature rows; EMPTY = g.X names the caller's rows (borrowed)
-    DeviceBuf<float> norms;        // split feat_h == 256 layout only
+    DeviceBuf<unsigned char> rows; // f32 rows, a narrow type's store or feature rows; EMPTY = g.X names the caller's rows (borrowed)
+    DeviceBuf<float> norms;        // the split feat_h == 256 layout's norms, or int8 rows' column scales
     DeviceBuf<uint32_t> adj0, adjU, upper_off;
     DeviceBuf<uint8_t> levels;
 };
@@ -112,40 +112,22 @@ struct leann_backend {
     uint64_t planes_n = 0;
     DeviceBuf<unsigned long long> screen_ctr;
     std::atomic<int> row_screen{leann_knobs().row_screen};
-    // Row type (rows_bf16.hip): LEANN_ROWS_F32, or LEANN_ROWS_BF16 — then g.X names the handle's own bf16 store, [n x g.row_bytes / 2]
-    // u16 in rs_plane_pos order (g.row_bytes: a multiple of 128, zero padded), g.feat_h stays 0, no f32 rows exist and no planes are
-    // ever cut.  Every path that reads g.X as f32 checks this first.  (A recompute-on handle reports LEANN_ROWS_FEATURES through
-    // leann_backend_row_type; here it is g.feat_h != 0 as before.)
-    // LEANN_ROWS_I8 (rows_i8.hip): g.X names the handle's own store of int8 codes, [n x g.row_bytes] bytes in i8_row_pos order, g.norms
-    // (store.norms) the column scales 2^-e_j, f32 [g.ld]; i8_exps holds the exponents e_j [g.d] on the host.  Otherwise as bf16.
+    // Row type: LEANN_ROWS_F32, or a narrow type (narrow_rows.h: LEANN_ROWS_BF16, LEANN_ROWS_I8) — then g.X names the handle's own store in
+    // that type's layout and no f32 rows exist: every path that reads g.X as f32 checks this first.  (A recompute-on handle reports
+    // LEANN_ROWS_FEATURES through leann_backend_row_type; here it is g.feat_h != 0 as before.)  i8_exps: int8 rows' column exponents e_j
+    // [g.d], on the host; their scales 2^-e_j are g.norms (store.norms), f32 [g.ld].
     int row_type = LEANN_ROWS_F32;
     std::vector<int8_t> i8_exps;
 };
+#include "narrow_rows.h"
 inline bool leann_internal_bf16(const leann_backend *h) { return h->row_type == LEANN_ROWS_BF16; }
 inline bool leann_internal_i8(const leann_backend *h) { return h->row_type == LEANN_ROWS_I8; }
 // the handle stores its vectors in a narrow type: no f32 rows exist for a scan, the builder or the graph repair to read
-inline bool leann_internal_narrow_rows(const leann_backend *h) { return leann_internal_bf16(h) || leann_internal_i8(h); }
-inline const char *leann_internal_row_name(const leann_backend *h) { return leann_internal_i8(h) ? "int8" : leann_internal_bf16(h) ? "bf16" : "f32"; }
-// int8 row store (rows_i8.hip).  _quantize_device: the column pass (when *exps is empty; LEANN_ERR_INVALID naming the first non-finite
-// element) and the quantising kernel over f32 device rows [n x ld_src]: codes into `store` (may be null), Xq back over the rows when
-// `write_back`.  _adopt_device: allocate h's store and scales and fill them from f32 device rows (h->g.n / d / ld set; h's device
-// current; exponents h already has are kept).  _adopt_host: the same from host rows, f32 [n x d] or an index file's codes [n x d] and
-// exponents [d].  _to_host: rows [r0, r0 + rows) as codes [rows x d] in element order.  _carry_exponents: dst takes src's exponents
-// and scales (compact.hip).  _check_file_rows: null, or what is wrong with an index file's exponents and codes.
-int leann_internal_i8_quantize_device(const char *who, float *d_rows, size_t n, uint32_t d, size_t ld_src, std::vector<int8_t> *exps, int8_t *store,
-                                      bool write_back);
-int leann_internal_i8_adopt_device(leann_backend *h, const float *d_src, size_t ld_src, const char *who);
-int leann_internal_i8_adopt_host(leann_backend *h, const float *f32_rows, const int8_t *codes, const int8_t *exps);
-int leann_internal_i8_to_host(const leann_backend *h, size_t r0, size_t rows, int8_t *out);
-int leann_internal_i8_carry_exponents(const leann_backend *src, leann_backend *dst);
-const char *leann_internal_i8_check_file_rows(const int8_t *exps, const int8_t *codes, size_t n, size_t d);
-// bf16 row store (rows_bf16.hip).  _adopt_device: allocate h's store and fill it with r(rows) of f32 device rows [n x ld_src] (h->g.n /
-// d / ld set; h's device current); afterwards h owns the store and names no f32 rows.  _adopt_host: the same from host rows, f32
-// [n x d] (rounded on the device, slab by slab) or bf16 [n x d] in element order (an index file's).  _to_host: rows [r0, r0 + rows)
-// as bf16 [rows x d] in element order.
-int leann_internal_bf16_adopt_device(leann_backend *h, const float *d_src, size_t ld_src);
-int leann_internal_bf16_adopt_host(leann_backend *h, const float *f32_rows, const uint16_t *bf16_rows);
-int leann_internal_bf16_to_host(const leann_backend *h, size_t r0, size_t rows, uint16_t *out);
+inline bool leann_internal_narrow_rows(const leann_backend *h) { return leann_internal_narrow(h->row_type) != nullptr; }
+inline const char *leann_internal_row_name(const leann_backend *h) {
+    const NarrowRows *t = leann_internal_narrow(h->row_type);
+    return t ? t->name : "f32";
+}
 int leann_internal_check_build_args(int backend, size_t graph_degree, size_t complexity); // build.hip: backend and list lengths
 // api.hip: dst takes src's coalescing configuration (automatic, configured with src's window and batch, or switched off)
 int leann_internal_copy_coalescing(const leann_backend *src, leann_backend *dst);
@@ -238,11 +220,9 @@ int leann_internal_from_host(int backend, size_t n, size_t dims, uint32_t M, uin
                              const uint8_t *levels, const uint32_t *upper_off, const uint32_t *adj0, const uint32_t *adjU,
                              size_t n_upper_lists, const float *vectors, const unsigned char *feat_rows, uint32_t feat_h, uint32_t row_bytes,
                              const float *Wf32, int device, uint64_t key_offset, leann_backend **out, int row_type = LEANN_ROWS_F32,
-                             const uint16_t *bf16_rows = nullptr, const float *d_f32_rows = nullptr, size_t d_f32_ld = 0,
-                             const int8_t *i8_codes = nullptr, const int8_t *i8_exps = nullptr);
-// ^ row_type LEANN_ROWS_BF16: the rows come as host f32 `vectors` (rounded), host `bf16_rows` [n x dims] (an index file's) or device
-//   f32 rows `d_f32_rows` [n x d_f32_ld] (rounded; leann_backend_to_rows) — exactly one of the three.  LEANN_ROWS_I8: the same three
-//   ways, the file's rows being `i8_codes` [n x dims] with `i8_exps` [dims] in place of `bf16_rows`.
+                             const NarrowSource *narrow = nullptr);
+// ^ a narrow row_type (narrow_rows.h): the rows come as host f32 `vectors` or from one of `narrow`'s sources — an index file's rows in
+//   the handle's own type, or device f32 rows (leann_backend_to_rows) — exactly one of the three, narrowed by the type's encode kernel.
 int leann_internal_save_to(const leann_backend *h, const std::string &path);
 int leann_internal_parse_device(const char *spec, int *device);
 int leann_internal_check_device(int device); // api.hip: LEANN_ERR_DEVICE and the "no CPU fallback" message unless `device` is a visible one

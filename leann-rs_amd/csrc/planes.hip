@@ -119,12 +119,8 @@ static void for_each_plain(leann_backend *h, void (*fn)(leann_backend *, void *)
 
 extern "C" int leann_backend_set_row_screen(leann_backend *h, int enable) {
     if (!h) { leann_set_error("leann_backend_set_row_screen: null handle"); return LEANN_ERR_INVALID; }
-    if (leann_backend_row_type(h) == LEANN_ROWS_BF16) { // nothing changes: no planes are ever cut for such a handle
-        leann_set_error("leann_backend_set_row_screen: the row screen splits f32 rows; this index stores bf16 rows, which are read whole");
-        return LEANN_ERR_UNSUPPORTED;
-    }
-    if (leann_backend_row_type(h) == LEANN_ROWS_I8) {
-        leann_set_error("leann_backend_set_row_screen: the row screen splits f32 rows; this index stores int8 rows, which are read whole");
+    if (const NarrowRows *t = leann_internal_narrow(leann_backend_row_type(h))) { // nothing changes: no planes are ever cut for such a handle
+        leann_set_error("leann_backend_set_row_screen: the row screen splits f32 rows; this index stores %s rows, which are read whole", t->name);
         return LEANN_ERR_UNSUPPORTED;
     }
     for_each_plain(h, [](leann_backend *s, void *ctx) {

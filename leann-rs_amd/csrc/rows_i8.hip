@@ -3,20 +3,19 @@
 //
 // Definition (i8_rows.h): amax_j = max_i |x_ij|, e_j the largest integer in [-32, 32] with amax_j 2^e_j <= 127 (0 for a zero column),
 // c_ij = clamp(rne(x_ij 2^e_j), -127, 127), Xq_ij = (float)c_ij 2^-e_j.  An int8 index over rows X is the f32 index over Xq with the
-// same graph, bit for bit.  The search kernels are search_i8.hip's; this file holds the row store — the column reduction and the
-// quantising kernel on the device, the way in from host rows, device rows and index files, the way out — and the row-type entry
-// points' int8 branches (rows_bf16.hip owns the entry points themselves).
+// same graph, bit for bit.  The search kernels are search_i8.hip's; the row store and the entry points that make such a handle are
+// narrow_rows.hip's, shared with every narrow type.  This file holds what is int8's alone: the column reduction and the quantising
+// kernel, the exponents and their scales, the type's description for that store (narrow_rows.h), the check of an index file's rows
+// and the host quantiser leann_quantize_i8.
 //
-// Device layout: [n x ldb] bytes, ldb = dims rounded up to 128, zero padded — a row is whole, aligned 128-B lines (768-d: 6) — with
-// the elements in i8_row_pos order (i8_rows.h).  g.X names the store, g.row_bytes = ldb; g.ld keeps the f32 meaning (dims rounded up to
-// 4) and selects the kernel; g.norms names the column scales 2^-e_j, f32 [g.ld], padding 1.0.  The exponents stay on the host
-// (leann_backend::i8_exps).  Files and exports are in plain element order.
+// Store row: ldb = dims rounded up to 128 bytes, zero padded — whole, aligned 128-B lines (768-d: 6) — with the elements in
+// i8_row_pos order (i8_rows.h).  g.norms names the column scales 2^-e_j, f32 [g.ld], padding 1.0.  The exponents stay on the host
+// (leann_backend::i8_exps).
 #include "common.cuh"
 #include "internal.h"
 #include "i8_rows.h"
 
 #include <algorithm>
-#include <new>
 #include <vector>
 
 // Column reduction.  amax_bits[j] = max over the rows of the bits of |x_ij| (non-negative floats order as their bits do; a NaN or an
@@ -117,19 +116,13 @@ struct ColumnPass {
     }
 };
 
-// h's exponents (host) and scales 2^-e_j (device, [g.ld], padding 1.0; g.norms); up: 2^e_j [g.ld] for the quantising kernel (may be null)
-static int set_exponents(leann_backend *h, const int8_t *exps, DeviceBuf<float> *up) {
+int leann_internal_i8_bind_scales(leann_backend *h) {
     const uint32_t d = h->g.d, ld = h->g.ld;
-    std::vector<float> dn(ld, 1.0f), u(ld, 1.0f);
-    for (uint32_t j = 0; j < d; j++) { dn[j] = i8_pow2(-exps[j]); u[j] = i8_pow2(exps[j]); }
-    h->i8_exps.assign(exps, exps + d);
+    std::vector<float> dn(ld, 1.0f);
+    for (uint32_t j = 0; j < d; j++) dn[j] = i8_pow2(-h->i8_exps[j]);
     if (h->store.norms.alloc(ld)) return LEANN_ERR_DEVICE;
     h->g.norms = h->store.norms;
     HIP_CHECK_RET(hipMemcpy(h->store.norms, dn.data(), (size_t)ld * 4, hipMemcpyHostToDevice));
-    if (up) {
-        if (up->alloc(ld)) return LEANN_ERR_DEVICE;
-        HIP_CHECK_RET(hipMemcpy(*up, u.data(), (size_t)ld * 4, hipMemcpyHostToDevice));
-    }
     return LEANN_OK;
 }
 
@@ -144,119 +137,38 @@ static int launch_quantize(const float *d_src, size_t n, uint32_t d, size_t ld, 
     return LEANN_OK;
 }
 
-// the store of h (h->g.n / d set), zero filled; h owns it from here on
-static int alloc_store(leann_backend *h) {
-    const uint32_t ldb = i8_store_ld(h->g.d);
-    const size_t bytes = std::max<size_t>((size_t)h->g.n * ldb, 128);
-    DeviceBuf<unsigned char> store;
-    if (int rc = store.alloc(bytes)) return rc;
-    HIP_CHECK_RET(hipMemset(store, 0, bytes));
-    leann_internal_own_rows(h, std::move(store)); // (the handle is new, or borrowed the f32 rows it was built on until here)
-    h->g.row_bytes = ldb;
-    h->g.feat_h = 0;
-    h->row_type = LEANN_ROWS_I8;
-    return LEANN_OK;
-}
-
-// Quantise f32 device rows [n x ld_src]: *exps empty -> the column pass fills it (LEANN_ERR_INVALID naming the first non-finite
-// element), else the given exponents are used; store: where the codes go (may be null); write_back: Xq over d_rows.  The
-// scale arrays are sized to the source pitch: the kernels read them in groups of four columns up to that pitch.
-int leann_internal_i8_quantize_device(const char *who, float *d_rows, size_t n, uint32_t d, size_t ld_src, std::vector<int8_t> *exps, int8_t *store,
-                                      bool write_back) {
-    if ((ld_src & 3) || ld_src < d || (n && !d_rows)) { leann_set_error("int8 rows: invalid source rows (ld %zu)", ld_src); return LEANN_ERR_INVALID; }
-    if (exps->empty()) {
-        ColumnPass cp;
-        if (int rc = cp.begin(d, (uint32_t)ld_src)) return rc;
-        if (int rc = cp.add(d_rows, n, 0)) return rc;
-        if (int rc = cp.finish(who, exps)) return rc;
-    }
-    if (!store && !write_back) return LEANN_OK;
-    std::vector<float> u(ld_src, 1.0f), v(ld_src, 1.0f);
-    for (uint32_t j = 0; j < d; j++) { u[j] = i8_pow2((*exps)[j]); v[j] = i8_pow2(-(*exps)[j]); }
-    DeviceBuf<float> up, dn;
-    if (up.alloc(ld_src) || dn.alloc(ld_src)) return LEANN_ERR_DEVICE;
-    HIP_CHECK_RET(hipMemcpy(up, u.data(), ld_src * 4, hipMemcpyHostToDevice));
-    HIP_CHECK_RET(hipMemcpy(dn, v.data(), ld_src * 4, hipMemcpyHostToDevice));
-    return launch_quantize(d_rows, n, d, ld_src, i8_store_ld(d), up, dn, store, write_back ? d_rows : nullptr);
-}
-
-int leann_internal_i8_adopt_device(leann_backend *h, const float *d_src, size_t ld_src, const char *who) {
-    std::vector<int8_t> exps = h->i8_exps; // (a device build has run the column pass already: quantising Xq again gives the same codes)
-    if (int rc = leann_internal_i8_quantize_device(who, const_cast<float *>(d_src), h->g.n, h->g.d, ld_src, &exps, nullptr, false)) return rc;
-    if (int rc = set_exponents(h, exps.data(), nullptr)) return rc;
-    if (int rc = alloc_store(h)) return rc;
-    return leann_internal_i8_quantize_device(who, const_cast<float *>(d_src), h->g.n, h->g.d, ld_src, &exps, (int8_t *)h->g.X, false);
-}
-
-int leann_internal_i8_adopt_host(leann_backend *h, const float *f32_rows, const int8_t *codes, const int8_t *exps) {
-    const size_t n = h->g.n, d = h->g.d;
-    if (n && !f32_rows && !codes) { leann_set_error("int8 rows: no rows given"); return LEANN_ERR_INVALID; }
-    if (codes && !exps) { leann_set_error("int8 rows: codes without their column exponents"); return LEANN_ERR_INVALID; }
-    const uint32_t ldb = i8_store_ld((uint32_t)d);
-    if (codes) { // an index file's rows: permuted on the host, slab by slab
-        if (int rc = set_exponents(h, exps, nullptr)) return rc;
-        if (int rc = alloc_store(h)) return rc;
-        int8_t *store = (int8_t *)h->g.X;
-        const size_t slab = std::max<size_t>(1, ((size_t)64 << 20) / ldb);
-        std::vector<int8_t> buf(std::min(slab, std::max<size_t>(n, 1)) * ldb, (int8_t)0);
-        for (size_t r0 = 0; r0 < n; r0 += slab) {
-            const size_t m = std::min(slab, n - r0);
-            for (size_t i = 0; i < m; i++)
-                for (size_t j = 0; j < d; j++) buf[i * ldb + i8_row_pos((uint32_t)j, ldb)] = codes[(r0 + i) * d + j];
-            HIP_CHECK_RET(hipMemcpy(store + r0 * ldb, buf.data(), m * ldb, hipMemcpyHostToDevice));
-        }
-        return LEANN_OK;
-    }
-    // f32 host rows: through a transient device slab, twice when they do not fit one — the column pass over all rows comes before the
-    // first code — and quantised by the same kernel as every other way in
-    const size_t ld = (d + 3) & ~(size_t)3, slab = std::max<size_t>(1, ((size_t)256 << 20) / (ld * 4));
-    DeviceBuf<float> stage;
-    if (int rc = stage.alloc(std::max<size_t>(std::min(slab, n) * ld, 4))) return rc;
-    auto upload = [&](size_t r0, size_t m) {
-        if (leann_internal_stage_rows(stage, ld, f32_rows + r0 * d, d, d, m, true) == hipSuccess) return (int)LEANN_OK;
-        leann_set_error("int8 rows: upload of the rows failed: %s", hipGetErrorString(hipGetLastError()));
-        return (int)LEANN_ERR_DEVICE;
-    };
+// ---- the type's description for the shared store (narrow_rows.h) ---------------------------------------------------------------------
+static uint32_t store_pitch(uint32_t d) { return i8_store_ld(d); }
+static uint32_t store_pos(uint32_t j, uint32_t ldb) { return i8_row_pos(j, ldb); }
+// the column pass over all rows comes before the first code: LEANN_ERR_INVALID naming the first non-finite element
+static int fit(const char *who, uint32_t d, uint32_t ld, const SlabLoop &each_slab, std::vector<int8_t> *exps) {
     ColumnPass cp;
-    std::vector<int8_t> e;
-    if (int rc = cp.begin((uint32_t)d, (uint32_t)ld)) return rc;
-    for (size_t r0 = 0; r0 < n; r0 += slab) {
-        const size_t m = std::min(slab, n - r0);
-        if (int rc = upload(r0, m)) return rc;
-        if (int rc = cp.add(stage, m, r0)) return rc;
-        HIP_CHECK_RET(hipDeviceSynchronize()); // the next upload overwrites the slab
-    }
-    if (int rc = cp.finish("leann_backend_from_arrays_rows", &e)) return rc;
-    DeviceBuf<float> up;
-    if (int rc = set_exponents(h, e.data(), &up)) return rc;
-    if (int rc = alloc_store(h)) return rc;
-    int8_t *store = (int8_t *)h->g.X;
-    for (size_t r0 = 0; r0 < n; r0 += slab) {
-        const size_t m = std::min(slab, n - r0);
-        if (n > slab)
-            if (int rc = upload(r0, m)) return rc; // (one slab: it is still staged)
-        if (int rc = launch_quantize(stage, m, (uint32_t)d, ld, ldb, up, h->g.norms, store + r0 * ldb, nullptr)) return rc;
-    }
-    return LEANN_OK;
+    if (int rc = cp.begin(d, ld)) return rc;
+    if (int rc = each_slab([&](float *d_rows, size_t m, size_t row0) { return cp.add(d_rows, m, row0); })) return rc;
+    return cp.finish(who, exps);
 }
-
-int leann_internal_i8_to_host(const leann_backend *h, size_t r0, size_t rows, int8_t *out) {
-    if (!leann_internal_i8(h) || r0 + rows > h->g.n) { leann_set_error("int8 rows: no such rows"); return LEANN_ERR_INVALID; }
-    if (rows == 0) return LEANN_OK;
-    const size_t d = h->g.d;
-    const uint32_t ldb = h->g.row_bytes;
-    const size_t slab = std::max<size_t>(1, ((size_t)64 << 20) / ldb);
-    std::vector<int8_t> buf(std::min(slab, rows) * ldb);
-    for (size_t s0 = 0; s0 < rows; s0 += slab) {
-        const size_t m = std::min(slab, rows - s0);
-        HIP_CHECK_RET(hipMemcpy(buf.data(), (const int8_t *)h->g.X + (r0 + s0) * ldb, m * ldb, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < m; i++)
-            for (size_t j = 0; j < d; j++) out[(s0 + i) * d + j] = buf[i * ldb + i8_row_pos((uint32_t)j, ldb)];
-    }
-    return LEANN_OK;
+// The scale arrays are sized to the source pitch: the kernel reads them in groups of four columns up to that pitch.
+static int encode(float *d_rows, size_t m, uint32_t d, size_t ld, const int8_t *exps, void *store, bool write_back) {
+    if (m == 0 || (!store && !write_back)) return LEANN_OK;
+    std::vector<float> u(ld, 1.0f), v(ld, 1.0f);
+    for (uint32_t j = 0; j < d; j++) { u[j] = i8_pow2(exps[j]); v[j] = i8_pow2(-exps[j]); }
+    DeviceBuf<float> up, dn;
+    if (up.alloc(ld) || dn.alloc(ld)) return LEANN_ERR_DEVICE;
+    HIP_CHECK_RET(hipMemcpy(up, u.data(), ld * 4, hipMemcpyHostToDevice));
+    HIP_CHECK_RET(hipMemcpy(dn, v.data(), ld * 4, hipMemcpyHostToDevice));
+    return launch_quantize(d_rows, m, d, ld, i8_store_ld(d), up, dn, (int8_t *)store, write_back ? d_rows : nullptr);
 }
-
-int leann_internal_i8_carry_exponents(const leann_backend *src, leann_backend *dst) { return set_exponents(dst, src->i8_exps.data(), nullptr); }
+// Xq = code x 2^-e: exact
+static void widen(const unsigned char *src, size_t count, size_t d, const int8_t *exps, unsigned char *dst) {
+    for (size_t i = 0; i < count; i++) {
+        const float x = (float)(int8_t)src[i] * ldexpf(1.0f, -exps[i % d]);
+        memcpy(dst + 4 * i, &x, 4);
+    }
+}
+const NarrowRows *leann_internal_i8_rows() { // (a function: a const object at namespace scope would be emitted into the device code too)
+    static const NarrowRows t = {LEANN_ROWS_I8, "int8", 1, 4, store_pitch, store_pos, fit, encode, widen};
+    return &t;
+}
 
 const char *leann_internal_i8_check_file_rows(const int8_t *exps, const int8_t *codes, size_t n, size_t d) {
     for (size_t j = 0; j < d; j++)
@@ -287,23 +199,6 @@ extern "C" int leann_quantize_i8(const float *in, size_t n, size_t d, int8_t *ex
         return LEANN_OK;
     } catch (const std::exception &e) {
         leann_set_error("leann_quantize_i8: %s", e.what());
-        return LEANN_ERR_IO;
-    }
-}
-
-extern "C" int leann_backend_rows_export_i8(const leann_backend *h, int8_t *exps, int8_t *rows) {
-    if (!h || !exps || !rows) { leann_set_error("leann_backend_rows_export_i8: null argument"); return LEANN_ERR_INVALID; }
-    if (h->sharded || !leann_internal_i8(h)) {
-        leann_set_error("leann_backend_rows_export_i8: the handle stores no int8 rows (a composite handle: export its shards)");
-        return LEANN_ERR_UNSUPPORTED;
-    }
-    try {
-        HIP_CHECK_RET(hipSetDevice(h->device));
-        HIP_CHECK_RET(hipDeviceSynchronize());
-        memcpy(exps, h->i8_exps.data(), h->g.d);
-        return leann_internal_i8_to_host(h, 0, h->g.n, rows);
-    } catch (const std::exception &e) {
-        leann_set_error("leann_backend_rows_export_i8: %s", e.what());
         return LEANN_ERR_IO;
     }
 }
