@@ -108,6 +108,11 @@ typedef struct leann_filter leann_filter;
 int leann_backend_filter_create(const leann_backend *h, const uint8_t *allow, leann_filter **out);
 size_t leann_backend_filter_count(const leann_filter *f); /* allowed positions */
 void leann_backend_filter_free(leann_filter *f);
+/* The registered bitmap in HBM, on the handle's device: *d_allow [ceil(*n / 8)] over *n positions (n: optional), already "valid AND
+ * match AND live" (leann_backend_filter_create ANDs the live mask; for removals alone register an all-ones bitmap).  Borrowed: valid
+ * until the filter is freed.  It is an ordinary allow-bitmap, e.g. for the leann_bm25_*_filtered calls.  The filter of a composite
+ * handle holds one slice per shard and no whole bitmap: LEANN_ERR_UNSUPPORTED — pass the caller's own bitmap there. */
+int leann_backend_filter_bitmap_device(const leann_filter *f, const uint8_t **d_allow, size_t *n);
 int leann_backend_search_filter_batch(const leann_backend *h, const float *queries, size_t nq, size_t top_k,
                                       size_t complexity, const leann_filter *filter, int mode,
                                       uint64_t *keys, float *dists, uint32_t *counts);
@@ -527,6 +532,33 @@ int leann_bm25_hybrid_rerank_device(const leann_bm25 *b, size_t nq, const uint32
                                     const uint64_t *d_keys, const float *d_dists, const uint32_t *d_counts, size_t fetch_k,
                                     float alpha, int compat_polarity, size_t top_k,
                                     uint64_t *d_out_keys, float *d_out_scores, uint32_t *d_out_counts, void *stream);
+/* The three calls above under an allow-bitmap (DESIGN.md §8c "under a filter"), so that a hybrid query under a metadata filter, or on
+ * an index with removed passages, composes with the filtered graph search.  Let A be the positions whose bit is set: bit i & 7 of byte
+ * i >> 3 stands for position i, ceil(n_docs / 8) bytes, bits at positions >= n_docs ignored.  Scoring is unchanged — idf, doc_len and
+ * avg_doc_len are the corpus's, a filter does not change them — and everything after it sees the score vector restricted to A:
+ *   search   the positives at positions in A, score descending, ties by position ascending; n_positive counts the positives in A;
+ *            min_max is folded over the scores at positions in A.
+ *   hybrid   bm25_top is that search at fetch_k and min_b / max_b are folded over A; the ANN lists enter as given (the caller searched
+ *            under the same bitmap) and the BM25 score of a merged key is scores[key], as in the unfiltered call.
+ *   empty A  count 0 for that query in both calls, whatever its ANN list holds; n_positive 0; min_max (+inf, -inf), the folds' identities.
+ * allow / allow_stride as in leann_backend_search_filtered_batch_device: stride 0 is one bitmap for the batch, otherwise query i uses
+ * allow + i * allow_stride, any value >= ceil(n_docs / 8) (no alignment is needed).  allow == NULL with stride 0 is the unfiltered
+ * call, bit for bit and launch for launch.  A non-zero stride below ceil(n_docs / 8), or a NULL bitmap with a non-zero stride, is
+ * LEANN_ERR_INVALID before any device work, like every other argument.  In the *_device forms the bitmap is in HBM on the handle's
+ * device — e.g. what leann_meta_eval_device wrote on the same stream, or leann_backend_filter_bitmap_device — and the host form
+ * uploads it.  Like their twins, the *_device calls synchronise the stream inside and cannot be captured into a HIP graph. */
+int leann_bm25_search_filtered_batch(const leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint32_t *q_term, const float *q_idf,
+                                     size_t top_k, const uint8_t *allow, size_t allow_stride,
+                                     uint32_t *pos, float *scores, uint32_t *counts, uint32_t *n_positive, float *min_max);
+int leann_bm25_search_filtered_batch_device(const leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint32_t *q_term,
+                                            const float *q_idf, size_t top_k, const uint8_t *d_allow, size_t allow_stride,
+                                            uint32_t *d_pos, float *d_scores, uint32_t *d_counts, uint32_t *d_n_positive,
+                                            float *d_min_max, void *stream);
+int leann_bm25_hybrid_rerank_filtered_device(const leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint32_t *q_term,
+                                             const float *q_idf, const uint64_t *d_keys, const float *d_dists, const uint32_t *d_counts,
+                                             size_t fetch_k, float alpha, int compat_polarity, size_t top_k,
+                                             const uint8_t *d_allow, size_t allow_stride,
+                                             uint64_t *d_out_keys, float *d_out_scores, uint32_t *d_out_counts, void *stream);
 
 /* ---- metadata filters evaluated on the device (src/index/filter.rs:328-418) ---------------------------------------------
  * A leann_meta is a columnar copy of the passages' metadata in HBM: one column per field (a dotted path, get_nested_value,

@@ -47,6 +47,12 @@ SIGNATURES = {
     "leann_bm25_search_batch_device": (C.c_int, [vp, C.c_size_t, u32p, u32p, f32p, C.c_size_t, vp, vp, vp, vp, vp, vp]),
     "leann_bm25_hybrid_rerank_device": (C.c_int, [vp, C.c_size_t, u32p, u32p, f32p, vp, vp, vp, C.c_size_t, C.c_float, C.c_int,
                                                  C.c_size_t, vp, vp, vp, vp]),
+    "leann_bm25_search_filtered_batch": (C.c_int, [vp, C.c_size_t, u32p, u32p, f32p, C.c_size_t, u8p, C.c_size_t, u32p, f32p, u32p, u32p,
+                                                  f32p]),
+    "leann_bm25_search_filtered_batch_device": (C.c_int, [vp, C.c_size_t, u32p, u32p, f32p, C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp, vp,
+                                                         vp]),
+    "leann_bm25_hybrid_rerank_filtered_device": (C.c_int, [vp, C.c_size_t, u32p, u32p, f32p, vp, vp, vp, C.c_size_t, C.c_float, C.c_int,
+                                                          C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp]),
     "leann_backend_open": (C.c_int, [C.c_char_p, C.c_int, C.c_size_t, C.c_char_p, C.POINTER(vp)]),
     "leann_backend_search": (C.c_int, [vp, f32p, C.c_size_t, C.c_size_t, u64p, f32p, C.POINTER(C.c_size_t)]),
     "leann_backend_search_batch": (C.c_int, [vp, f32p, C.c_size_t, C.c_size_t, C.c_size_t, u64p, f32p, u32p]),
@@ -100,6 +106,7 @@ SIGNATURES = {
     "leann_backend_filter_create": (C.c_int, [vp, u8p, C.POINTER(vp)]),
     "leann_backend_filter_count": (C.c_size_t, [vp]),
     "leann_backend_filter_free": (None, [vp]),
+    "leann_backend_filter_bitmap_device": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
     "leann_backend_search_filter_batch": (C.c_int, [vp, f32p, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_int, u64p, f32p, u32p]),
     "leann_meta_create": (C.c_int, [C.c_size_t, u8p, C.c_int, C.POINTER(vp)]),
     "leann_meta_add_column": (C.c_int, [vp, C.c_char_p, u8p, C.POINTER(C.c_double), C.c_char_p, u64p]),

@@ -466,6 +466,13 @@ class Filter:
     def count(self):
         return int(N.lib().leann_backend_filter_count(self._h))
 
+    def device_bitmap(self):
+        """(device pointer, positions) of the registered bitmap — valid AND match AND live — borrowed until close(): an allow-bitmap
+        for Bm25Index.search_batch_device / hybrid_rerank_device.  The filter of a composite handle has none (LeannError 5)."""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        N.check(N.lib().leann_backend_filter_bitmap_device(self._h, C.byref(p), C.byref(n)))
+        return p.value, int(n.value)
+
     def close(self):
         if self._h:
             N.lib().leann_backend_filter_free(self._h)

@@ -128,38 +128,72 @@ class Bm25Index:
     def __len__(self):
         return int(N.lib().leann_bm25_len(self._h))
 
-    def search_batch(self, queries, top_k):
+    def _device_allow(self, allow):
+        """an allow-bitmap for a *_device call: a numpy bitmap is uploaded (the returned DeviceArray keeps it alive for the call), a
+        DeviceArray or a raw device pointer is passed through"""
+        if isinstance(allow, DeviceArray):
+            return allow.ptr, allow
+        if isinstance(allow, np.ndarray):
+            d = DeviceArray.from_host(np.ascontiguousarray(allow, np.uint8))
+            return d.ptr, d
+        return allow, None
+
+    def search_batch(self, queries, top_k, allow=None, allow_stride=0):
         """Bm25Scorer::search per query.  queries: texts, lists of (term id, idf), or packed (q_off, q_term, q_idf).
-        Returns pos [nq x top_k] u32, scores [nq x top_k] f32, counts [nq], n_positive [nq], min_max [nq x 2]."""
+        Returns pos [nq x top_k] u32, scores [nq x top_k] f32, counts [nq], n_positive [nq], min_max [nq x 2].
+        allow: a bitmap over the passages (numpy u8, a DeviceArray or a device pointer; include/leann_backend.h "under an allow-bitmap"),
+        query i's at byte i * allow_stride, stride 0 = one for the batch; None makes exactly the unfiltered call."""
         nq, q_off, q_term, q_idf = self._queries(queries)
+        if allow is not None and not isinstance(allow, np.ndarray):  # already on the device: the device call, results downloaded
+            return tuple(a.to_host() for a in self.search_batch_device((q_off, q_term, q_idf), top_k, allow=allow, allow_stride=allow_stride))
         pos = np.full((nq, top_k), 0xFFFFFFFF, np.uint32)
         sc = np.full((nq, top_k), -np.inf, np.float32)
         cnt, npos, mm = np.zeros(nq, np.uint32), np.zeros(nq, np.uint32), np.zeros((nq, 2), np.float32)
-        N.check(N.lib().leann_bm25_search_batch(self._h, nq, _p(q_off, C.c_uint32), _p(q_term, C.c_uint32), _p(q_idf, C.c_float), top_k,
-                                                _p(pos, C.c_uint32), _p(sc, C.c_float), _p(cnt, C.c_uint32), _p(npos, C.c_uint32),
-                                                _p(mm, C.c_float)))
+        q = (self._h, nq, _p(q_off, C.c_uint32), _p(q_term, C.c_uint32), _p(q_idf, C.c_float), top_k)
+        o = (_p(pos, C.c_uint32), _p(sc, C.c_float), _p(cnt, C.c_uint32), _p(npos, C.c_uint32), _p(mm, C.c_float))
+        if allow is None:
+            N.check(N.lib().leann_bm25_search_batch(*q, *o))
+        else:
+            allow = np.ascontiguousarray(allow, np.uint8)
+            need = (self.n_docs + 7) // 8 + (nq - 1) * allow_stride if allow_stride and nq else (self.n_docs + 7) // 8
+            if allow.size < need:
+                raise N.LeannError(1, f"Bm25Index.search_batch: the allow-bitmap holds {allow.size} bytes, {need} are needed")
+            N.check(N.lib().leann_bm25_search_filtered_batch(*q, _p(allow, C.c_uint8), allow_stride, *o))
         return pos, sc, cnt, npos, mm
 
-    def search_batch_device(self, queries, top_k, stream=None, out=None):
+    def search_batch_device(self, queries, top_k, stream=None, out=None, allow=None, allow_stride=0):
         """search_batch with the results left in HBM: DeviceArrays (pos u32 [nq x top_k], scores f32, counts u32 [nq],
         n_positive u32 [nq], min_max f32 [nq x 2]); `out` reuses the arrays of an earlier call of the same shape."""
         nq, q_off, q_term, q_idf = self._queries(queries)
         if out is None:
             out = (DeviceArray((nq, top_k), np.uint32), DeviceArray((nq, top_k), np.float32), DeviceArray(nq, np.uint32),
                    DeviceArray(nq, np.uint32), DeviceArray((nq, 2), np.float32))
-        N.check(N.lib().leann_bm25_search_batch_device(self._h, nq, _p(q_off, C.c_uint32), _p(q_term, C.c_uint32), _p(q_idf, C.c_float), top_k,
-                                                       out[0].ptr, out[1].ptr, out[2].ptr, out[3].ptr, out[4].ptr, stream))
+        q = (self._h, nq, _p(q_off, C.c_uint32), _p(q_term, C.c_uint32), _p(q_idf, C.c_float), top_k)
+        o = (out[0].ptr, out[1].ptr, out[2].ptr, out[3].ptr, out[4].ptr, stream)
+        if allow is None:
+            N.check(N.lib().leann_bm25_search_batch_device(*q, *o))
+        else:
+            d_allow, keep = self._device_allow(allow)
+            N.check(N.lib().leann_bm25_search_filtered_batch_device(*q, d_allow, allow_stride, *o))  # returns after the stream has finished
+            del keep
         return out
 
-    def hybrid_rerank_device(self, queries, d_keys, d_dists, d_counts, fetch_k, alpha, compat_polarity, top_k, stream=None):
+    def hybrid_rerank_device(self, queries, d_keys, d_dists, d_counts, fetch_k, alpha, compat_polarity, top_k, stream=None, allow=None,
+                             allow_stride=0):
         """The hybrid leg on lists in HBM (DeviceArrays or raw pointers: keys u64 / dists f32 [nq x fetch_k], counts u32 [nq]).
-        Returns DeviceArrays (keys [nq x top_k] u64, scores f32, counts u32)."""
+        Returns DeviceArrays (keys [nq x top_k] u64, scores f32, counts u32).  allow / allow_stride: as in search_batch."""
         nq, q_off, q_term, q_idf = self._queries(queries)
         ptr = lambda a: a.ptr if isinstance(a, DeviceArray) else a  # noqa: E731
         ok, os_, oc = DeviceArray((nq, top_k), np.uint64), DeviceArray((nq, top_k), np.float32), DeviceArray(nq, np.uint32)
-        N.check(N.lib().leann_bm25_hybrid_rerank_device(self._h, nq, _p(q_off, C.c_uint32), _p(q_term, C.c_uint32), _p(q_idf, C.c_float),
-                                                        ptr(d_keys), ptr(d_dists), ptr(d_counts), fetch_k, alpha,
-                                                        1 if compat_polarity else 0, top_k, ok.ptr, os_.ptr, oc.ptr, stream))
+        a = (self._h, nq, _p(q_off, C.c_uint32), _p(q_term, C.c_uint32), _p(q_idf, C.c_float), ptr(d_keys), ptr(d_dists), ptr(d_counts),
+             fetch_k, alpha, 1 if compat_polarity else 0, top_k)
+        o = (ok.ptr, os_.ptr, oc.ptr, stream)
+        if allow is None:
+            N.check(N.lib().leann_bm25_hybrid_rerank_device(*a, *o))
+        else:
+            d_allow, keep = self._device_allow(allow)
+            N.check(N.lib().leann_bm25_hybrid_rerank_filtered_device(*a, d_allow, allow_stride, *o))
+            del keep
         return ok, os_, oc
 
     def close(self):

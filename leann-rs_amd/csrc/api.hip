@@ -507,6 +507,23 @@ extern "C" int leann_backend_filter_create(const leann_backend *hc, const uint8_
     return leann_internal_filter_finish(hc, f, out);
 }
 extern "C" size_t leann_backend_filter_count(const leann_filter *f) { return f ? f->n_allowed : 0; }
+// the registered bitmap (valid AND match AND live) for a caller that filters something else by it: the BM25 *_filtered calls
+extern "C" int leann_backend_filter_bitmap_device(const leann_filter *f, const uint8_t **d_allow, size_t *n) {
+    if (!f || !d_allow) {
+        leann_set_error("leann_backend_filter_bitmap_device: null %s", !f ? "filter" : "d_allow");
+        return LEANN_ERR_INVALID;
+    }
+    *d_allow = nullptr;
+    if (n) *n = 0;
+    if (!f->parts.empty()) {
+        leann_set_error("leann_backend_filter_bitmap_device: the filter of a composite handle holds one bitmap slice per shard, each on "
+                        "its shard's device, and no whole one; pass the caller's own bitmap over global positions instead");
+        return LEANN_ERR_UNSUPPORTED;
+    }
+    *d_allow = f->d_allow;
+    if (n) *n = f->n;
+    return LEANN_OK;
+}
 extern "C" void leann_backend_filter_free(leann_filter *f) {
     if (!f) return;
     if (!f->parts.empty()) {

@@ -25,6 +25,10 @@
 //   consume   search: best-k -> (position, score) lists;  hybrid: the rerank body of hybrid.hip with the BM25 score of a merged key
 //             gathered from the live accumulator.
 //   reset     the chunk's accumulators are cleared (one memset node) for the next chunk.
+// Under an allow-bitmap (the *_filtered entry points; DESIGN.md §8c "under a filter") scoring is unchanged — idf, doc_len and avg_doc_len
+// are the corpus's — and everything after it sees the score vector restricted to the allowed positions: the sweep is
+// bm25_emit_masked_kernel, the segment sorter gets the bitmap, and a query that allows nothing is settled by bm25_empty_allow_kernel.
+// Without a bitmap the launches are the ones above, the same kernels with the same arguments.
 // Selection and reset sweep the dense vector, not the lists: on a Zipf vocabulary a 2-8 term query is positive on nearly every passage,
 // where the dense sweep reads 4 B per passage against 12 B per posting, and it needs no claim marks.  The price is 8 B per passage for a
 // query with few positives (80 MB = ~16 us at 10M passages).
@@ -59,7 +63,7 @@ struct leann_bm25 {
     DeviceBuf<float> d_k1n, d_acc;                               // acc [slots x n_docs], all zero between calls
     DeviceBuf<uint64_t> d_best, d_list;                          // [slots x BM25_MAX_TOPK], [slots x BM25_CAND_CAP]
     DeviceBuf<float> d_thr;                                      // [slots]
-    DeviceBuf<uint32_t> d_cnt, d_stats, d_overflow;              // [slots], [slots x 4] {P, min, max, -}, [1]
+    DeviceBuf<uint32_t> d_cnt, d_stats, d_overflow;              // [slots], [slots x 4] {P, min, max, allowed rows (masked sweep)}, [1]
     uint32_t *h_overflow = nullptr;                              // pinned
     DeviceBuf<Bm25Tok> d_toks;                                   // query tokens / offsets of the running batch; grown, never shrunk
     DeviceBuf<uint32_t> d_qoff;
@@ -147,6 +151,78 @@ __global__ void __launch_bounds__(256) bm25_emit_kernel(const float *__restrict_
     }
 }
 
+// bm25_emit_kernel under an allow-bitmap (bit row & 7 of byte row >> 3): a row whose bit is clear contributes to nothing — not to the
+// positives, not to min / max, not to the candidate list — and stats[slot * 4 + 3] counts the allowed rows, so that the consumers can
+// tell an empty allowed set (whose min / max have no orderable encoding) from any other.  The slot's bitmap is allow + slot *
+// allow_stride (the caller has added the chunk's q0 * allow_stride).  Every launch starts at a multiple of BM25_CAND_CAP rows and a
+// workgroup's 256 rows at a multiple of 256, so each aligned group of 32 lanes covers the rows of one 4-byte group of the bitmap: its
+// first lane reads the bytes (singly: a stride need not be a multiple of 4, and no byte behind ceil(n_docs / 8) is touched) and the
+// other 31 take the word by a shuffle.  4 bitmap bytes per 128 bytes of scores.  Every lane asks for its score before the word is there.
+__global__ void __launch_bounds__(256) bm25_emit_masked_kernel(const float *__restrict__ acc, uint64_t n_docs, uint32_t r0, uint32_t r1,
+                                                               const uint64_t *__restrict__ best, uint32_t k, uint32_t *__restrict__ cnt,
+                                                               uint64_t *__restrict__ list, uint32_t cap, uint32_t *__restrict__ stats,
+                                                               const uint8_t *__restrict__ allow, uint64_t allow_stride) {
+    __shared__ uint32_t s_p, s_min, s_max, s_a;
+    const uint32_t slot = blockIdx.y;
+    const float *__restrict__ a = acc + (size_t)slot * n_docs;
+    const uint8_t *__restrict__ bits = allow + (size_t)slot * allow_stride;
+    const uint32_t nbytes = (uint32_t)((n_docs + 7) >> 3);
+    const uint64_t bound = best[(size_t)slot * k + (k - 1)];
+    if (threadIdx.x == 0) { s_p = 0; s_min = 0xFFFFFFFFu; s_max = 0; s_a = 0; }
+    __syncthreads();
+    uint32_t p = 0, mn = 0xFFFFFFFFu, mx = 0, na = 0;
+    const uint32_t lane = threadIdx.x & 63;
+    for (uint32_t base = r0 + blockIdx.x * 256u; base < r1; base += gridDim.x * 256u) { // uniform over the workgroup: every lane shuffles
+        const uint32_t row = base + threadIdx.x;
+        const bool in = row < r1;
+        const float v = in ? a[row] : 0.0f; // asked for beside the bitmap bytes, not behind them: one memory latency per step, not two
+        uint32_t w = 0;
+        if ((lane & 31) == 0 && in) {
+            const uint32_t b0 = row >> 3; // row is a multiple of 32 here
+            if (b0 + 3 < nbytes) {
+                w = (uint32_t)bits[b0] | ((uint32_t)bits[b0 + 1] << 8) | ((uint32_t)bits[b0 + 2] << 16) | ((uint32_t)bits[b0 + 3] << 24);
+            } else { // the bitmap's last bytes
+                for (uint32_t i = 0; i < 4; i++)
+                    if (b0 + i < nbytes) w |= (uint32_t)bits[b0 + i] << (8 * i);
+            }
+        }
+        w = __shfl(w, (int)(lane & 32));
+        if (in && ((w >> (lane & 31)) & 1)) {
+            na++;
+            const uint32_t o = f32_orderable(v);
+            mn = min(mn, o);
+            mx = max(mx, o);
+            if (v > 0.0f) {
+                p++;
+                const uint64_t key = ((uint64_t)(~o) << 32) | row;
+                if (key < bound) {
+                    const uint32_t at = atomicAdd(&cnt[slot], 1u);
+                    if (at < cap) list[(size_t)slot * cap + at] = key;
+                }
+            }
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        p += __shfl_xor(p, off);
+        na += __shfl_xor(na, off);
+        mn = min(mn, (uint32_t)__shfl_xor(mn, off));
+        mx = max(mx, (uint32_t)__shfl_xor(mx, off));
+    }
+    if (lane == 0) {
+        atomicAdd(&s_p, p);
+        atomicAdd(&s_a, na);
+        atomicMin(&s_min, mn);
+        atomicMax(&s_max, mx);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_p) atomicAdd(&stats[slot * 4 + 0], s_p);
+        if (s_a) atomicAdd(&stats[slot * 4 + 3], s_a);
+        atomicMin(&stats[slot * 4 + 1], s_min);
+        atomicMax(&stats[slot * 4 + 2], s_max);
+    }
+}
+
 // overflow path: (position, score) lists of the segment sorter -> selection keys; rows that are not positive sort last and are cut
 __global__ void bm25_rebuild_best_kernel(const uint64_t *__restrict__ keys, const float *__restrict__ scores, uint32_t k,
                                          uint64_t *__restrict__ best) {
@@ -189,6 +265,26 @@ __global__ void __launch_bounds__(256) bm25_hybrid_rerank_kernel(const uint64_t 
     const uint32_t q = blockIdx.x; // slot == query within the chunk
     const HybDenseBm bm{best + (size_t)q * fetch_k, acc + (size_t)q * n_docs, n_docs, stats[q * 4 + 0], stats[q * 4 + 1], stats[q * 4 + 2]};
     hybrid_rerank_body(bm, keys, dists, counts, fetch_k, alpha, compat, top_k, out_keys, out_scores, out_counts, q);
+}
+
+// After the consumer of a masked chunk: a query whose bitmap allows no position.  Its folds never ran, and their identities (+inf,
+// -inf) are not what the orderable sentinels of d_stats decode to, so they are written here; the rerank of such a query returns
+// nothing whatever its ANN list holds.  (The search consumer has written count 0, n_positive 0 and the tails already: P == 0.)
+__global__ void bm25_empty_allow_kernel(const uint32_t *__restrict__ stats, float *__restrict__ min_max, uint32_t top_k,
+                                        uint64_t *__restrict__ out_keys, float *__restrict__ out_scores, uint32_t *__restrict__ out_counts) {
+    const uint32_t q = blockIdx.x; // pointers are already at the chunk's first query
+    if (stats[q * 4 + 3] != 0) return;
+    if (min_max && threadIdx.x == 0) {
+        min_max[q * 2 + 0] = __uint_as_float(0x7F800000u);
+        min_max[q * 2 + 1] = __uint_as_float(0xFF800000u);
+    }
+    if (out_keys) {
+        for (uint32_t j = threadIdx.x; j < top_k; j += blockDim.x) {
+            out_keys[(size_t)q * top_k + j] = ~0ull;
+            out_scores[(size_t)q * top_k + j] = __uint_as_float(0xFF800000u);
+        }
+        if (threadIdx.x == 0) out_counts[q] = 0;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
@@ -376,10 +472,14 @@ struct Bm25Consumer { // what happens to a chunk's best-k while its accumulators
     uint64_t *d_out_keys = nullptr;
     float *d_out_scores = nullptr;
     uint32_t *d_out_counts = nullptr;
+    // both: an allow-bitmap on the handle's device (null: none), query i's at d_allow + i * allow_stride
+    const uint8_t *d_allow = nullptr;
+    size_t allow_stride = 0;
 };
 
 // best-k of the chunk's nslots accumulators by the segment sorter of the exact scan (no list to overflow)
-static int bm25_select_by_segments(leann_bm25 *b, uint32_t nslots, uint32_t k, hipStream_t st) {
+// `allow`: the bitmap of the chunk's first slot (null: none); with a stride the slots are sorted one by one, each under its own
+static int bm25_select_by_segments(leann_bm25 *b, uint32_t nslots, uint32_t k, const uint8_t *allow, size_t allow_stride, hipStream_t st) {
     const size_t segs = (b->n_docs + SEG - 1) / SEG, cand_len = segs * k;
     DeviceBuf<uint64_t> candA, candB, keys;
     DeviceBuf<float> scores;
@@ -388,7 +488,14 @@ static int bm25_select_by_segments(leann_bm25 *b, uint32_t nslots, uint32_t k, h
         counts.alloc(nslots))
         return LEANN_ERR_DEVICE;
     size_t segs_out = 0;
-    int rc = leann_internal_topk_chunk(b->d_acc, b->n_docs, nslots, k, nullptr, 0, candA, cand_len, 0, st, &segs_out, nullptr);
+    int rc = LEANN_OK;
+    if (allow && allow_stride) {
+        for (uint32_t s = 0; s < nslots && rc == LEANN_OK; s++)
+            rc = leann_internal_topk_chunk(b->d_acc + (size_t)s * b->n_docs, b->n_docs, 1, k, allow + (size_t)s * allow_stride, 0,
+                                           candA + (size_t)s * cand_len, cand_len, 0, st, &segs_out, nullptr);
+    } else {
+        rc = leann_internal_topk_chunk(b->d_acc, b->n_docs, nslots, k, allow, 0, candA, cand_len, 0, st, &segs_out, nullptr);
+    }
     if (rc == LEANN_OK) rc = leann_internal_scan_finish_ex(candA, candB, cand_len, segs_out, nslots, k, 0, keys, scores, counts, st, nullptr, 0);
     if (rc == LEANN_OK) {
         hipLaunchKernelGGL(bm25_rebuild_best_kernel, dim3(nslots), dim3(256), 0, st, keys.p, scores.p, k, b->d_best.p);
@@ -441,13 +548,18 @@ static int bm25_run(leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint3
                                b->d_k1n, b->d_acc, (uint64_t)b->n_docs);
         }
         // select
+        const uint8_t *allow = c.d_allow ? c.d_allow + q0 * c.allow_stride : nullptr; // the bitmap of the chunk's first query
         hipLaunchKernelGGL(bm25_select_init_kernel, dim3(ns), dim3(256), 0, st, b->d_best, k, b->d_thr, b->d_cnt, b->d_stats, b->d_overflow);
         CandEmit em{b->d_thr, b->d_cnt, b->d_list, BM25_CAND_CAP, nullptr, 0};
         for (uint32_t r0 = 0, len = BM25_CAND_CAP; r0 < n_docs32 && rc == LEANN_OK;) {
             const uint32_t r1 = (uint32_t)std::min<uint64_t>((uint64_t)r0 + len, n_docs32);
             const unsigned gx = (unsigned)std::min<size_t>(BM25_MAX_GRID_X, ((size_t)(r1 - r0) + 1023) / 1024);
-            hipLaunchKernelGGL(bm25_emit_kernel, dim3(gx, ns), dim3(256), 0, st, b->d_acc, (uint64_t)b->n_docs, r0, r1, b->d_best, k, b->d_cnt,
-                               b->d_list, (uint32_t)BM25_CAND_CAP, b->d_stats);
+            if (allow)
+                hipLaunchKernelGGL(bm25_emit_masked_kernel, dim3(gx, ns), dim3(256), 0, st, b->d_acc, (uint64_t)b->n_docs, r0, r1, b->d_best, k,
+                                   b->d_cnt, b->d_list, (uint32_t)BM25_CAND_CAP, b->d_stats, allow, (uint64_t)c.allow_stride);
+            else
+                hipLaunchKernelGGL(bm25_emit_kernel, dim3(gx, ns), dim3(256), 0, st, b->d_acc, (uint64_t)b->n_docs, r0, r1, b->d_best, k, b->d_cnt,
+                                   b->d_list, (uint32_t)BM25_CAND_CAP, b->d_stats);
             rc = leann_internal_fold_candidates(em, k, ns, ns, b->d_best, b->d_overflow, st);
             r0 = r1;
             len = r0; // the next range doubles the rows seen: ~k survivors per range whatever its length
@@ -458,7 +570,7 @@ static int bm25_run(leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint3
         if (rc != LEANN_OK) break;
         if (*b->h_overflow) {
             leann_log(LEANN_LOG_DEBUG, "bm25: a candidate list overflowed, chunk at query %zu selects by segments", q0);
-            rc = bm25_select_by_segments(b, ns, k, st);
+            rc = bm25_select_by_segments(b, ns, k, allow, c.allow_stride, st);
             if (rc != LEANN_OK) break;
         }
         // consume
@@ -470,6 +582,10 @@ static int bm25_run(leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint3
             hipLaunchKernelGGL(bm25_finalize_kernel, dim3(ns), dim3(256), 0, st, b->d_best, b->d_stats, k, c.d_pos + q0 * k, c.d_scores + q0 * k,
                                c.d_counts + q0, c.d_npos ? c.d_npos + q0 : nullptr, c.d_minmax ? c.d_minmax + q0 * 2 : nullptr);
         }
+        if (allow)
+            hipLaunchKernelGGL(bm25_empty_allow_kernel, dim3(ns), dim3(256), 0, st, b->d_stats, c.d_minmax ? c.d_minmax + q0 * 2 : nullptr, c.top_k,
+                               c.hybrid ? c.d_out_keys + q0 * c.top_k : nullptr, c.hybrid ? c.d_out_scores + q0 * c.top_k : nullptr,
+                               c.hybrid ? c.d_out_counts + q0 : nullptr);
         // reset
         fail(hipMemsetAsync(b->d_acc, 0, (size_t)ns * b->n_docs * 4, st), "hipMemsetAsync");
         fail(hipGetLastError(), "kernel launch");
@@ -503,41 +619,84 @@ static int bm25_check_search(const char *fn, const leann_bm25 *b, size_t nq, con
     return leann_bm25_check_queries(b->n_terms, nq, q_off, q_term, q_idf);
 }
 
-extern "C" int leann_bm25_search_batch_device(const leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint32_t *q_term, const float *q_idf,
-                                              size_t top_k, uint32_t *d_pos, float *d_scores, uint32_t *d_counts, uint32_t *d_n_positive,
-                                              float *d_min_max, void *stream) {
-    const int rc = bm25_check_search("leann_bm25_search_batch_device", b, nq, q_off, q_term, q_idf, top_k);
+// the bitmap arguments of the *_filtered calls; a null handle is reported by the query checks that follow
+static int bm25_check_allow(const char *fn, const leann_bm25 *b, const void *allow, size_t allow_stride) {
+    if (!allow && allow_stride) {
+        leann_set_error("%s: allow is null but allow_stride is %zu (no bitmap means stride 0)", fn, allow_stride);
+        return LEANN_ERR_INVALID;
+    }
+    if (b && allow && allow_stride && allow_stride < (b->n_docs + 7) / 8) {
+        leann_set_error("%s: allow_stride %zu is smaller than the %zu-byte bitmap of %zu passages", fn, allow_stride, (b->n_docs + 7) / 8,
+                        b->n_docs);
+        return LEANN_ERR_INVALID;
+    }
+    return LEANN_OK;
+}
+
+static int bm25_search_device(const char *fn, const leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint32_t *q_term, const float *q_idf,
+                              size_t top_k, const uint8_t *d_allow, size_t allow_stride, uint32_t *d_pos, float *d_scores, uint32_t *d_counts,
+                              uint32_t *d_n_positive, float *d_min_max, void *stream) {
+    int rc = bm25_check_allow(fn, b, d_allow, allow_stride);
+    if (rc == LEANN_OK) rc = bm25_check_search(fn, b, nq, q_off, q_term, q_idf, top_k);
     if (rc != LEANN_OK) return rc;
     if (nq == 0) return LEANN_OK;
     if (!d_pos || !d_scores || !d_counts) {
-        leann_set_error("leann_bm25_search_batch_device: null output");
+        leann_set_error("%s: null output", fn);
         return LEANN_ERR_INVALID;
     }
     Bm25Consumer c;
     c.d_pos = d_pos; c.d_scores = d_scores; c.d_counts = d_counts; c.d_npos = d_n_positive; c.d_minmax = d_min_max;
+    c.d_allow = d_allow; c.allow_stride = allow_stride;
     return bm25_run(const_cast<leann_bm25 *>(b), nq, q_off, q_term, q_idf, (uint32_t)top_k, c, (hipStream_t)stream);
 }
 
-extern "C" int leann_bm25_search_batch(const leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint32_t *q_term, const float *q_idf,
-                                       size_t top_k, uint32_t *pos, float *scores, uint32_t *counts, uint32_t *n_positive, float *min_max) {
-    int rc = bm25_check_search("leann_bm25_search_batch", b, nq, q_off, q_term, q_idf, top_k);
+extern "C" int leann_bm25_search_batch_device(const leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint32_t *q_term, const float *q_idf,
+                                              size_t top_k, uint32_t *d_pos, float *d_scores, uint32_t *d_counts, uint32_t *d_n_positive,
+                                              float *d_min_max, void *stream) {
+    return bm25_search_device("leann_bm25_search_batch_device", b, nq, q_off, q_term, q_idf, top_k, nullptr, 0, d_pos, d_scores, d_counts,
+                              d_n_positive, d_min_max, stream);
+}
+
+extern "C" int leann_bm25_search_filtered_batch_device(const leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint32_t *q_term,
+                                                       const float *q_idf, size_t top_k, const uint8_t *d_allow, size_t allow_stride,
+                                                       uint32_t *d_pos, float *d_scores, uint32_t *d_counts, uint32_t *d_n_positive,
+                                                       float *d_min_max, void *stream) {
+    return bm25_search_device("leann_bm25_search_filtered_batch_device", b, nq, q_off, q_term, q_idf, top_k, d_allow, allow_stride, d_pos,
+                              d_scores, d_counts, d_n_positive, d_min_max, stream);
+}
+
+static int bm25_search_host(const char *fn, const leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint32_t *q_term, const float *q_idf,
+                            size_t top_k, const uint8_t *allow, size_t allow_stride, uint32_t *pos, float *scores, uint32_t *counts,
+                            uint32_t *n_positive, float *min_max) {
+    int rc = bm25_check_allow(fn, b, allow, allow_stride);
+    if (rc == LEANN_OK) rc = bm25_check_search(fn, b, nq, q_off, q_term, q_idf, top_k);
     if (rc != LEANN_OK) return rc;
     if (nq == 0) return LEANN_OK;
     if (!pos || !scores || !counts) {
-        leann_set_error("leann_bm25_search_batch: null output");
+        leann_set_error("%s: null output", fn);
         return LEANN_ERR_INVALID;
     }
     int prev = 0;
     HIP_CHECK_RET(hipGetDevice(&prev));
     HIP_CHECK_RET(hipSetDevice(b->device));
     DeviceBuf<unsigned char> d;
+    const size_t nbytes = (b->n_docs + 7) / 8; // of one bitmap; the last query's need not be followed by a whole stride
+    const size_t allow_bytes = !allow ? 0 : allow_stride ? (nq - 1) * allow_stride + nbytes : nbytes;
     const size_t o_pos = 0, o_sc = o_pos + nq * top_k * 4, o_cnt = o_sc + nq * top_k * 4, o_np = o_cnt + nq * 4, o_mm = o_np + nq * 4,
-                 total = o_mm + nq * 8;
+                 o_allow = o_mm + nq * 8, total = o_allow + allow_bytes;
     if ((rc = d.alloc(total))) { (void)hipSetDevice(prev); return rc; }
     Bm25Consumer c;
     c.d_pos = (uint32_t *)(d + o_pos); c.d_scores = (float *)(d + o_sc); c.d_counts = (uint32_t *)(d + o_cnt);
     c.d_npos = (uint32_t *)(d + o_np); c.d_minmax = (float *)(d + o_mm);
-    rc = bm25_run(const_cast<leann_bm25 *>(b), nq, q_off, q_term, q_idf, (uint32_t)top_k, c, nullptr);
+    if (allow) {
+        if (hipMemcpy(d + o_allow, allow, allow_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            leann_set_error("%s: the bitmap could not be copied to the device", fn);
+            rc = LEANN_ERR_DEVICE;
+        }
+        c.d_allow = d + o_allow; c.allow_stride = allow_stride;
+    }
+    if (rc == LEANN_OK) rc = bm25_run(const_cast<leann_bm25 *>(b), nq, q_off, q_term, q_idf, (uint32_t)top_k, c, nullptr);
     if (rc == LEANN_OK) {
         hipError_t e = hipMemcpy(pos, d + o_pos, nq * top_k * 4, hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipMemcpy(scores, d + o_sc, nq * top_k * 4, hipMemcpyDeviceToHost);
@@ -546,7 +705,7 @@ extern "C" int leann_bm25_search_batch(const leann_bm25 *b, size_t nq, const uin
         if (e == hipSuccess && min_max) e = hipMemcpy(min_max, d + o_mm, nq * 8, hipMemcpyDeviceToHost);
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            leann_set_error("leann_bm25_search_batch: hipMemcpy failed: %s", hipGetErrorString(e));
+            leann_set_error("%s: hipMemcpy failed: %s", fn, hipGetErrorString(e));
             rc = LEANN_ERR_DEVICE;
         }
     }
@@ -555,24 +714,37 @@ extern "C" int leann_bm25_search_batch(const leann_bm25 *b, size_t nq, const uin
     return rc;
 }
 
-extern "C" int leann_bm25_hybrid_rerank_device(const leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint32_t *q_term, const float *q_idf,
-                                               const uint64_t *d_keys, const float *d_dists, const uint32_t *d_counts, size_t fetch_k, float alpha,
-                                               int compat_polarity, size_t top_k, uint64_t *d_out_keys, float *d_out_scores,
-                                               uint32_t *d_out_counts, void *stream) {
+extern "C" int leann_bm25_search_batch(const leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint32_t *q_term, const float *q_idf,
+                                       size_t top_k, uint32_t *pos, float *scores, uint32_t *counts, uint32_t *n_positive, float *min_max) {
+    return bm25_search_host("leann_bm25_search_batch", b, nq, q_off, q_term, q_idf, top_k, nullptr, 0, pos, scores, counts, n_positive, min_max);
+}
+
+extern "C" int leann_bm25_search_filtered_batch(const leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint32_t *q_term, const float *q_idf,
+                                                size_t top_k, const uint8_t *allow, size_t allow_stride, uint32_t *pos, float *scores,
+                                                uint32_t *counts, uint32_t *n_positive, float *min_max) {
+    return bm25_search_host("leann_bm25_search_filtered_batch", b, nq, q_off, q_term, q_idf, top_k, allow, allow_stride, pos, scores, counts,
+                            n_positive, min_max);
+}
+
+static int bm25_hybrid(const char *fn, const leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint32_t *q_term, const float *q_idf,
+                       const uint64_t *d_keys, const float *d_dists, const uint32_t *d_counts, size_t fetch_k, float alpha, int compat_polarity,
+                       size_t top_k, const uint8_t *d_allow, size_t allow_stride, uint64_t *d_out_keys, float *d_out_scores,
+                       uint32_t *d_out_counts, void *stream) {
     if (fetch_k == 0 || fetch_k > HYB_MAX_FETCH || top_k == 0 || top_k > HYB_MAX_MERGED) {
-        leann_set_error("leann_bm25_hybrid_rerank_device: fetch_k %zu outside [1, %d] or top_k %zu outside [1, %d] (the reference fetches 5 * top_k, "
-                        "searcher.rs:129-133)", fetch_k, HYB_MAX_FETCH, top_k, HYB_MAX_MERGED);
+        leann_set_error("%s: fetch_k %zu outside [1, %d] or top_k %zu outside [1, %d] (the reference fetches 5 * top_k, "
+                        "searcher.rs:129-133)", fn, fetch_k, HYB_MAX_FETCH, top_k, HYB_MAX_MERGED);
         return LEANN_ERR_INVALID;
     }
     if (!(alpha >= 0.0f && alpha <= 1.0f)) {
-        leann_set_error("leann_bm25_hybrid_rerank_device: alpha %g outside [0, 1]", (double)alpha);
+        leann_set_error("%s: alpha %g outside [0, 1]", fn, (double)alpha);
         return LEANN_ERR_INVALID;
     }
-    const int rc = bm25_check_search("leann_bm25_hybrid_rerank_device", b, nq, q_off, q_term, q_idf, fetch_k);
+    int rc = bm25_check_allow(fn, b, d_allow, allow_stride);
+    if (rc == LEANN_OK) rc = bm25_check_search(fn, b, nq, q_off, q_term, q_idf, fetch_k);
     if (rc != LEANN_OK) return rc;
     if (nq == 0) return LEANN_OK;
     if (!d_keys || !d_dists || !d_counts || !d_out_keys || !d_out_scores || !d_out_counts) {
-        leann_set_error("leann_bm25_hybrid_rerank_device: null list / output");
+        leann_set_error("%s: null list / output", fn);
         return LEANN_ERR_INVALID;
     }
     Bm25Consumer c;
@@ -580,5 +752,23 @@ extern "C" int leann_bm25_hybrid_rerank_device(const leann_bm25 *b, size_t nq, c
     c.d_keys = d_keys; c.d_dists = d_dists; c.d_vcounts = d_counts;
     c.alpha = alpha; c.compat = compat_polarity; c.top_k = (uint32_t)top_k;
     c.d_out_keys = d_out_keys; c.d_out_scores = d_out_scores; c.d_out_counts = d_out_counts;
+    c.d_allow = d_allow; c.allow_stride = allow_stride;
     return bm25_run(const_cast<leann_bm25 *>(b), nq, q_off, q_term, q_idf, (uint32_t)fetch_k, c, (hipStream_t)stream);
+}
+
+extern "C" int leann_bm25_hybrid_rerank_device(const leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint32_t *q_term, const float *q_idf,
+                                               const uint64_t *d_keys, const float *d_dists, const uint32_t *d_counts, size_t fetch_k, float alpha,
+                                               int compat_polarity, size_t top_k, uint64_t *d_out_keys, float *d_out_scores,
+                                               uint32_t *d_out_counts, void *stream) {
+    return bm25_hybrid("leann_bm25_hybrid_rerank_device", b, nq, q_off, q_term, q_idf, d_keys, d_dists, d_counts, fetch_k, alpha, compat_polarity,
+                       top_k, nullptr, 0, d_out_keys, d_out_scores, d_out_counts, stream);
+}
+
+extern "C" int leann_bm25_hybrid_rerank_filtered_device(const leann_bm25 *b, size_t nq, const uint32_t *q_off, const uint32_t *q_term,
+                                                        const float *q_idf, const uint64_t *d_keys, const float *d_dists,
+                                                        const uint32_t *d_counts, size_t fetch_k, float alpha, int compat_polarity, size_t top_k,
+                                                        const uint8_t *d_allow, size_t allow_stride, uint64_t *d_out_keys, float *d_out_scores,
+                                                        uint32_t *d_out_counts, void *stream) {
+    return bm25_hybrid("leann_bm25_hybrid_rerank_filtered_device", b, nq, q_off, q_term, q_idf, d_keys, d_dists, d_counts, fetch_k, alpha,
+                       compat_polarity, top_k, d_allow, allow_stride, d_out_keys, d_out_scores, d_out_counts, stream);
 }

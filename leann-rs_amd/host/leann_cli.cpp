@@ -27,6 +27,7 @@ struct SearchArgs {
     std::string device = getenv("LEANN_DEVICES") ? getenv("LEANN_DEVICES") : "0"; // "0", or a list / range = sharded (leann_backend.h)
     bool device_filter = false;
     bool bm25_device = true;
+    bool hybrid_filter_inside = false;
     std::optional<std::string> queries_file;
 };
 
@@ -53,6 +54,7 @@ static void usage_search() {
          "      --queries-file <FILE>          (additive) one query per line instead of <QUERY>: the batch is searched in one backend call and,\n"
          "                                     with --hybrid, one device BM25 + rerank call; prints a JSON array with one result array per query\n"
          "      --bm25 <WHERE>                 (additive) where hybrid mode scores BM25: device (inverted index in HBM) or host; same output [default: device] [possible values: device, host]\n"
+         "      --hybrid-filter <WHEN>         (additive) hybrid mode: inside = BM25 and its rerank see only what --device-filter allows and no removed passage; post = filter after the rerank [default: post] [possible values: inside, post]\n"
          "  -h, --help                         Print help");
 }
 
@@ -94,6 +96,7 @@ static int run_search(int argc, char **argv) {
         else if (name == "--device") a.device = val();
         else if (name == "--queries-file") a.queries_file = val();
         else if (name == "--bm25") { std::string w = val(); if (w != "device" && w != "host") throw Error("invalid value '" + w + "' for '--bm25 <WHERE>' [possible values: device, host]"); a.bm25_device = w == "device"; }
+        else if (name == "--hybrid-filter") { std::string w = val(); if (w != "inside" && w != "post") throw Error("invalid value '" + w + "' for '--hybrid-filter <WHEN>' [possible values: inside, post]"); a.hybrid_filter_inside = w == "inside"; }
         else if (name == "-v" || name == "--verbose" || name == "-q" || name == "--quiet") {}
         else if (!s.empty() && s[0] == '-' && s.size() > 1) throw Error("unexpected argument '" + s + "' found");
         else if (!have_query) { a.query = s; have_query = true; }
@@ -177,7 +180,7 @@ static int run_search(int argc, char **argv) {
         if (filter) opts.with_filter(*filter);
         if (filter && a.device_filter) opts.with_device_filter(*a.filter);
         if (a.hybrid) opts.with_hybrid("", a.hybrid_alpha);
-        opts.with_compat_polarity(a.compat_polarity).with_bm25_device(a.bm25_device);
+        opts.with_compat_polarity(a.compat_polarity).with_bm25_device(a.bm25_device).with_hybrid_filter_inside(a.hybrid_filter_inside);
         lj::Value all = lj::Value::array();
         for (auto &rs : searcher.search_batch_with_options(embeddings, texts, opts)) all.a->push_back(results_json(rs));
         printf("%s\n", lj::to_string_pretty(all).c_str());
@@ -193,7 +196,7 @@ static int run_search(int argc, char **argv) {
         if (filter) opts.with_filter(*filter);
         if (filter && a.device_filter) opts.with_device_filter(*a.filter);
         if (use_hybrid) opts.with_hybrid(a.query, a.hybrid_alpha);
-        opts.with_compat_polarity(a.compat_polarity).with_bm25_device(a.bm25_device);
+        opts.with_compat_polarity(a.compat_polarity).with_bm25_device(a.bm25_device).with_hybrid_filter_inside(a.hybrid_filter_inside);
         results = searcher.search_with_options(q, opts);
     };
     // A pruned index (search.rs:151-167) recomputes embeddings at query time.  The reference scans every passage through the provider

@@ -276,13 +276,20 @@ class Bm25Scorer {
 };
 
 // bm25.rs:135-170 — min-max normalise both lists, alpha blend, stable sort descending
+// `allow` (additive; include/leann_backend.h "under an allow-bitmap"): min_b / max_b are folded over the positions whose bit is set only
 inline std::vector<std::pair<size_t, float>> hybrid_rerank(const std::vector<std::pair<size_t, float>> &vector_results,
-                                                           const std::vector<float> &bm25_scores, float alpha) {
+                                                           const std::vector<float> &bm25_scores, float alpha,
+                                                           const std::vector<uint8_t> *allow = nullptr) {
     float max_v = -INFINITY, min_v = INFINITY;
     for (auto &r : vector_results) { max_v = std::fmax(max_v, r.second); min_v = std::fmin(min_v, r.second); }
     float vrange = std::fmax(max_v - min_v, 1e-6f);
     float max_b = -INFINITY, min_b = INFINITY;
-    for (float b : bm25_scores) { max_b = std::fmax(max_b, b); min_b = std::fmin(min_b, b); }
+    if (!allow) {
+        for (float b : bm25_scores) { max_b = std::fmax(max_b, b); min_b = std::fmin(min_b, b); }
+    } else {
+        for (size_t i = 0; i < bm25_scores.size() && (i >> 3) < allow->size(); i++)
+            if (((*allow)[i >> 3] >> (i & 7)) & 1) { max_b = std::fmax(max_b, bm25_scores[i]); min_b = std::fmin(min_b, bm25_scores[i]); }
+    }
     float brange = std::fmax(max_b - min_b, 1e-6f);
     std::vector<std::pair<size_t, float>> out;
     out.reserve(vector_results.size());
@@ -502,12 +509,18 @@ struct SearchOptions {
     // Additive: the BM25 half of hybrid mode runs on the device (leann_bm25, csrc/bm25.hip) when the searcher has a backend and
     // fetch_k <= 256; false — or no device — scores on the host.  Same bits either way.  `leann search --bm25 device|host`.
     bool bm25_device = true;
+    // Additive (include/leann_backend.h "under an allow-bitmap"): in hybrid mode the BM25 half sees only the passages the vector half
+    // may return — the --device-filter bitmap, or the live positions of an index with removals — so that no BM25-only hit is injected
+    // that the post-filter then drops, and a removed or filtered-out best hit does not set max_bm25.  false (default): the filter and
+    // the removals act after the rerank, as before.  `leann search --hybrid-filter inside|post`.
+    bool hybrid_filter_inside = false;
     SearchOptions(size_t k, size_t c) : top_k(k), complexity(c) {}
     SearchOptions &with_device_filter(std::string key) { device_filter = true; filter_key = std::move(key); return *this; }
     SearchOptions &with_filter(MetadataFilter f) { filter = std::move(f); return *this; }
     SearchOptions &with_hybrid(std::string q, float alpha) { hybrid = true; hybrid_alpha = alpha; query_text = std::move(q); return *this; }
     SearchOptions &with_compat_polarity(bool on) { compat_polarity = on; return *this; }
     SearchOptions &with_bm25_device(bool on) { bm25_device = on; return *this; }
+    SearchOptions &with_hybrid_filter_inside(bool on) { hybrid_filter_inside = on; return *this; }
 };
 
 inline std::vector<std::string> read_id_map(const std::string &index_path, const PassageStore &passages) {
@@ -580,14 +593,7 @@ class IndexSearcher {
             if (!opts.hybrid) { fetch_k = opts.top_k; }
             // The filter lives on the device (bitmap + compacted list of allowed positions), registered once per distinct filter.
             const RegisteredFilter rf = device_filter(*opts.filter, opts.filter_key);
-            // The walk answers from the pool of evaluated nodes (20-33 x complexity for M = 16-32): widen it so that the pool is
-            // expected to hold >= 8 x fetch_k allowed passages (selectivity s: complexity >= 8 fetch_k / (20 s)), capped at 1024.
-            size_t complexity = opts.complexity;
-            const size_t n_rows = std::max<size_t>(leann_backend_len(backend_.get()), 1);
-            if (rf.allowed > 0) {
-                const double s_sel = (double)rf.allowed / (double)n_rows;
-                complexity = std::min<size_t>(1024, std::max<size_t>(complexity, (size_t)std::ceil(8.0 * (double)fetch_k / (20.0 * s_sel))));
-            }
+            const size_t complexity = filter_complexity(rf, opts.complexity, fetch_k);
             // mode 2: the library answers selective filters (<= 5 % of the rows, or <= 64k rows) exactly — the allowed rows are scanned
             // on the device — and walks otherwise.  One query at a time, 10M x 768 rows (scripts/filter_latency.py): 3 % allowed: 0.49 ms
             // exact against 0.80 ms walking at recall 0.92; 1 %: 0.32 ms against 1.8 ms at 0.84; 10 %: 1.1 ms against 0.46 ms at 0.89.
@@ -613,8 +619,28 @@ class IndexSearcher {
             const Bm25Scorer &scorer = bm25();
             leann_bm25 *dev = device_bm25_applies(opts, fetch_k) ? bm25_device(scorer) : nullptr;
             if (host_log_debug()) fprintf(stderr, "DEBUG leann: BM25 scored on the %s\n", dev ? "device" : "host");
+            const std::shared_ptr<const HybridMask> mask = hybrid_mask(opts, scorer);
+            if (host_log_debug() && mask) fprintf(stderr, "DEBUG leann: hybrid rerank under the allow-bitmap (%zu allowed)\n", mask->allowed);
             if (dev) {
-                vector_results = device_hybrid(dev, scorer, {*opts.query_text}, {vector_results}, fetch_k, opts)[0];
+                vector_results = device_hybrid(dev, scorer, {*opts.query_text}, {vector_results}, fetch_k, opts, mask ? mask->d_allow : nullptr)[0];
+            } else if (mask) { // the definition of the leann_bm25_*_filtered calls on the host: same bits
+                if (!opts.compat_polarity)
+                    for (auto &r : vector_results) r.second = 1.0f - r.second;
+                if (mask->allowed == 0) {
+                    vector_results.clear(); // nothing is allowed: nothing comes back, whatever the ANN list holds
+                } else {
+                    auto bm25_scores = scorer.score_query(*opts.query_text);
+                    std::vector<std::pair<size_t, float>> bm25_top;
+                    for (size_t i = 0; i < bm25_scores.size(); i++)
+                        if (bm25_scores[i] > 0.0f && mask->allows(i)) bm25_top.emplace_back(i, bm25_scores[i]);
+                    std::stable_sort(bm25_top.begin(), bm25_top.end(), [](auto &a, auto &b) { return b.second < a.second; });
+                    if (bm25_top.size() > fetch_k) bm25_top.resize(fetch_k);
+                    std::unordered_set<size_t> have;
+                    for (auto &r : vector_results) have.insert(r.first);
+                    for (auto &b : bm25_top)
+                        if (!have.count(b.first)) vector_results.emplace_back(b.first, 0.0f);
+                    vector_results = hybrid_rerank(vector_results, bm25_scores, opts.hybrid_alpha, &mask->host);
+                }
             } else {
                 if (!opts.compat_polarity)
                     for (auto &r : vector_results) r.second = 1.0f - r.second; // corrected polarity (N1): similarity, larger = better
@@ -639,7 +665,8 @@ class IndexSearcher {
         const size_t fetch_k = opts.top_k * 5;
         leann_bm25 *dev = (opts.hybrid && device_bm25_applies(opts, fetch_k)) ? bm25_device(bm25()) : nullptr;
         std::vector<std::vector<SearchResult>> out;
-        if (!opts.hybrid || (opts.filter && opts.device_filter) || !dev) { // nothing to batch: the single-query path, query by query
+        const bool filter_inside = opts.hybrid && opts.hybrid_filter_inside && opts.filter && opts.device_filter && dev;
+        if (!opts.hybrid || (opts.filter && opts.device_filter && !filter_inside) || !dev) { // nothing to batch: the single-query path, query by query
             for (size_t i = 0; i < nq; i++) {
                 SearchOptions o = opts;
                 if (opts.hybrid) o.query_text = query_texts[i];
@@ -656,12 +683,27 @@ class IndexSearcher {
         std::vector<uint64_t> keys(nq * fetch_k);
         std::vector<float> dists(nq * fetch_k);
         std::vector<uint32_t> counts(nq);
-        check(leann_backend_search_batch(backend_.get(), q.data(), nq, fetch_k, opts.complexity, keys.data(), dists.data(), counts.data()));
+        std::shared_ptr<const HybridMask> mask = hybrid_mask(opts, bm25());
+        if (filter_inside) {
+            // the filtered search of search_with_options for the whole batch.  The library chooses between the walk and the exact scan
+            // by the batch size too (64 queries is the line), so the batch goes in groups of at most 64: every query is answered as
+            // it is alone.  One rerank call for all of them follows.
+            const RegisteredFilter rf = device_filter(*opts.filter, opts.filter_key);
+            const size_t complexity = filter_complexity(rf, opts.complexity, fetch_k);
+            for (size_t q0 = 0; q0 < nq; q0 += 64) {
+                const size_t m = std::min<size_t>(64, nq - q0);
+                check(leann_backend_search_filter_batch(backend_.get(), q.data() + q0 * dims, m, fetch_k, complexity, rf.handle.get(), 2,
+                                                        keys.data() + q0 * fetch_k, dists.data() + q0 * fetch_k, counts.data() + q0));
+            }
+        } else {
+            check(leann_backend_search_batch(backend_.get(), q.data(), nq, fetch_k, opts.complexity, keys.data(), dists.data(), counts.data()));
+        }
         std::vector<std::vector<std::pair<size_t, float>>> lists(nq);
         for (size_t i = 0; i < nq; i++)
             for (size_t j = 0; j < counts[i]; j++) lists[i].emplace_back((size_t)keys[i * fetch_k + j], dists[i * fetch_k + j]);
         if (host_log_debug()) fprintf(stderr, "DEBUG leann: BM25 scored on the device (batch of %zu)\n", nq);
-        auto reranked = device_hybrid(dev, bm25(), query_texts, lists, fetch_k, opts);
+        if (host_log_debug() && mask) fprintf(stderr, "DEBUG leann: hybrid rerank under the allow-bitmap (%zu allowed)\n", mask->allowed);
+        auto reranked = device_hybrid(dev, bm25(), query_texts, lists, fetch_k, opts, mask ? mask->d_allow : nullptr);
         for (size_t i = 0; i < nq; i++) out.push_back(finish_results(reranked[i], opts));
         return out;
     }
@@ -749,7 +791,8 @@ class IndexSearcher {
     std::vector<std::vector<std::pair<size_t, float>>> device_hybrid(leann_bm25 *dev, const Bm25Scorer &scorer,
                                                                      const std::vector<std::string> &texts,
                                                                      const std::vector<std::vector<std::pair<size_t, float>>> &lists,
-                                                                     size_t fetch_k, const SearchOptions &opts) const {
+                                                                     size_t fetch_k, const SearchOptions &opts,
+                                                                     const uint8_t *d_allow = nullptr) const {
         const size_t nq = lists.size(), out_k = 2 * fetch_k; // the merged list has at most fetch_k + fetch_k entries
         std::vector<uint32_t> q_off(1, 0), q_term, counts(nq);
         std::vector<float> q_idf;
@@ -766,9 +809,15 @@ class IndexSearcher {
         check(leann_device_upload(dk.p, keys.data(), keys.size() * 8));
         check(leann_device_upload(dd.p, dists.data(), dists.size() * 4));
         check(leann_device_upload(dc.p, counts.data(), nq * 4));
-        check(leann_bm25_hybrid_rerank_device(dev, nq, q_off.data(), q_term.data(), q_idf.data(), (const uint64_t *)dk.p, (const float *)dd.p,
-                                              (const uint32_t *)dc.p, fetch_k, opts.hybrid_alpha, opts.compat_polarity ? 1 : 0, out_k,
-                                              (uint64_t *)ok.p, (float *)os.p, (uint32_t *)oc.p, nullptr));
+        if (d_allow)
+            check(leann_bm25_hybrid_rerank_filtered_device(dev, nq, q_off.data(), q_term.data(), q_idf.data(), (const uint64_t *)dk.p,
+                                                           (const float *)dd.p, (const uint32_t *)dc.p, fetch_k, opts.hybrid_alpha,
+                                                           opts.compat_polarity ? 1 : 0, out_k, d_allow, 0, (uint64_t *)ok.p, (float *)os.p,
+                                                           (uint32_t *)oc.p, nullptr));
+        else
+            check(leann_bm25_hybrid_rerank_device(dev, nq, q_off.data(), q_term.data(), q_idf.data(), (const uint64_t *)dk.p, (const float *)dd.p,
+                                                  (const uint32_t *)dc.p, fetch_k, opts.hybrid_alpha, opts.compat_polarity ? 1 : 0, out_k,
+                                                  (uint64_t *)ok.p, (float *)os.p, (uint32_t *)oc.p, nullptr));
         std::vector<uint64_t> rk(nq * out_k);
         std::vector<float> rs(nq * out_k);
         std::vector<uint32_t> rc(nq);
@@ -814,12 +863,91 @@ class IndexSearcher {
         if (host_log_debug()) fprintf(stderr, "DEBUG leann: host pass over %zu passages, filter registered in %.3f ms\n", n, ms());
         return remember(key, raw);
     }
+    // The walk answers from the pool of evaluated nodes (20-33 x complexity for M = 16-32): widen it so that the pool is
+    // expected to hold >= 8 x fetch_k allowed passages (selectivity s: complexity >= 8 fetch_k / (20 s)), capped at 1024.
+    size_t filter_complexity(const RegisteredFilter &rf, size_t complexity, size_t fetch_k) const {
+        const size_t n_rows = std::max<size_t>(leann_backend_len(backend_.get()), 1);
+        if (rf.allowed > 0) {
+            const double s_sel = (double)rf.allowed / (double)n_rows;
+            complexity = std::min<size_t>(1024, std::max<size_t>(complexity, (size_t)std::ceil(8.0 * (double)fetch_k / (20.0 * s_sel))));
+        }
+        return complexity;
+    }
     RegisteredFilter remember(const std::string &key, leann_filter *raw) const {
         RegisteredFilter rf;
         rf.handle = std::shared_ptr<leann_filter>(raw, [](leann_filter *p) { leann_backend_filter_free(p); });
         rf.allowed = leann_backend_filter_count(raw);
         if (filters_->size() >= 16) filters_->clear();
         return (*filters_)[key.empty() ? std::string("\x01anon") : key] = std::move(rf);
+    }
+    // `--hybrid-filter inside`: what the BM25 half of a hybrid query may see — the registered filter's bitmap (valid AND match AND live)
+    // under --device-filter, else the live positions of an index with removals (an all-ones filter, registered once: the handle's
+    // removals do not change while the index is open); null when neither applies or the mode is off.  d_allow is on the BM25 handle's
+    // device: the registered bitmap itself (leann_backend_filter_bitmap_device), or, for a composite handle, whose filter has no whole
+    // bitmap, a copy made here from the per-passage loop and kept with the entry.  `host` is the same bitmap for the host BM25 path.
+    struct HybridMask {
+        RegisteredFilter filter;      // keeps the registered bitmap alive
+        std::shared_ptr<void> own;    // a composite handle: the copy on the first device
+        const uint8_t *d_allow = nullptr;
+        std::vector<uint8_t> host;
+        size_t allowed = 0;
+        bool allows(size_t i) const { return (i >> 3) < host.size() && ((host[i >> 3] >> (i & 7)) & 1); }
+    };
+    std::shared_ptr<const HybridMask> hybrid_mask(const SearchOptions &opts, const Bm25Scorer &scorer) const {
+        if (!opts.hybrid || !opts.hybrid_filter_inside || !backend_) return nullptr;
+        const bool by_filter = opts.filter && opts.device_filter;
+        if (!by_filter && removed_.empty()) return nullptr;
+        const size_t n = leann_backend_len(backend_.get());
+        if (scorer.num_docs() != n) { // the bitmap is over the backend's positions
+            fprintf(stderr, "WARN --hybrid-filter inside: %zu passages, %zu index rows; the filter acts after the rerank\n", scorer.num_docs(), n);
+            return nullptr;
+        }
+        const std::string key = by_filter ? (opts.filter_key.empty() ? std::string("\x01anon") : opts.filter_key) : std::string("\x02live");
+        {
+            std::lock_guard<std::mutex> lk(*bm25_mu_);
+            auto it = masks_->find(key);
+            if (it != masks_->end() && (!by_filter || !opts.filter_key.empty())) return it->second;
+        }
+        auto m = std::make_shared<HybridMask>();
+        const size_t nbytes = (n + 7) / 8;
+        if (by_filter) {
+            m->filter = device_filter(*opts.filter, opts.filter_key);
+        } else {
+            std::vector<uint8_t> ones(nbytes + 1, 0xFF);
+            leann_filter *raw = nullptr;
+            check(leann_backend_filter_create(backend_.get(), ones.data(), &raw)); // ANDs the live mask
+            m->filter.handle = std::shared_ptr<leann_filter>(raw, [](leann_filter *p) { leann_backend_filter_free(p); });
+            m->filter.allowed = leann_backend_filter_count(raw);
+        }
+        m->allowed = m->filter.allowed;
+        m->host.assign(nbytes, 0);
+        size_t n_pos = 0;
+        const int rc = leann_backend_filter_bitmap_device(m->filter.handle.get(), &m->d_allow, &n_pos);
+        if (rc == LEANN_OK) {
+            if (n_pos != n) throw Error("registered filter covers " + std::to_string(n_pos) + " positions, the index has " + std::to_string(n));
+            check(leann_device_download(m->host.data(), const_cast<uint8_t *>(m->d_allow), nbytes));
+        } else if (rc == LEANN_ERR_UNSUPPORTED) { // a composite handle: the bitmap over global positions, made here, on the first device
+            for (size_t i = 0; i < n; i++) {
+                if (is_removed(i)) continue;
+                bool ok = !by_filter;
+                if (by_filter) {
+                    std::string id = i < id_map_.size() ? id_map_[i] : std::to_string(i);
+                    try { ok = opts.filter->matches(passages_.get(id).metadata); } catch (...) {}
+                }
+                if (ok) m->host[i >> 3] |= (uint8_t)(1u << (i & 7));
+            }
+            void *p = nullptr;
+            check(leann_device_malloc(bm25_device_id_, std::max<size_t>(nbytes, 16), &p));
+            m->own = std::shared_ptr<void>(p, [](void *q) { leann_device_free(q); });
+            check(leann_device_upload(p, m->host.data(), nbytes));
+            m->d_allow = (const uint8_t *)p;
+        } else {
+            check(rc);
+        }
+        std::lock_guard<std::mutex> lk(*bm25_mu_);
+        if (masks_->size() >= 16) masks_->clear();
+        (*masks_)[key] = m;
+        return m;
     }
     // The device path of device_filter (include/leann_backend.h "metadata filters evaluated on the device"): the open index keeps one
     // columnar store; a field gets its column the first time a filter names it, by ONE pass over the passages that extracts the fields
@@ -933,6 +1061,8 @@ class IndexSearcher {
     std::vector<std::string> id_map_;
     std::vector<uint8_t> removed_; // bitmap of removed positions; empty when nothing is removed
     std::shared_ptr<std::map<std::string, RegisteredFilter>> filters_ = std::make_shared<std::map<std::string, RegisteredFilter>>();
+    std::shared_ptr<std::map<std::string, std::shared_ptr<const HybridMask>>> masks_ =
+        std::make_shared<std::map<std::string, std::shared_ptr<const HybridMask>>>();
     mutable std::shared_ptr<Bm25Scorer> bm25_;
     struct Bm25Device { // the scorer's postings in HBM; one per loaded index, shared by its copies like the mutex that guards it
         std::shared_ptr<leann_bm25> handle;

@@ -10,8 +10,13 @@
       in HBM — WITHOUT the graph walk; `with_walk_queries_per_s` adds --walk-ms-per-batch (default: the 31.6 ms per 16 384 queries of
       the recorded vamana10m1536_r32 --hybrid run, scaled to the batch) and is a derived figure, not a measurement
   (d) the same batch at 64 positives per query through leann_hybrid_rerank_device (the sparse call), to show it did not get slower
+  (e) --allow-share S[,S...]: (a) and (c) again under one random allow-bitmap that allows a share S of the passages (the *_filtered
+      calls), each next to the unmasked call on the same queries in the same run.  Scoring and reset are the same work in both, so the
+      difference of the two (a) times is the selection sweep's; `masked_over_unmasked` is the ratio of the whole calls
+  (f) --query-by-query N: the hybrid leg for the first N queries of (c) one call per query — the shape of a host that cannot batch —
+      next to one call for the same N queries
 
-  python scripts/bm25_bench.py [--passages 10000000] [--terms 20000] [--batch 16384] [--repeats 5]
+  python scripts/bm25_bench.py [--passages 10000000] [--terms 20000] [--batch 16384] [--repeats 5] [--allow-share 1.0,0.1,0.01]
 Warm-up runs first, medians of `--repeats` timed runs (host wall clock around calls that return when the device is done; outputs are
 allocated before the clock starts).  Every step runs under --step-limit seconds; a step that exceeds it ends the script.  Each line
 carries `overflow_fallbacks`: how often a chunk's candidate lists overflowed and the segment sorter selected instead (counted from
@@ -52,6 +57,7 @@ def synth_corpus_blocked(seed, n_docs, n_terms, block=500_000):
         t = (pair // np.uint64(n_docs)).astype(np.int64)
         parts.append((t, (pair % np.uint64(n_docs)).astype(np.uint32), tf.astype(np.uint32)))
         counts += np.bincount(t, minlength=n_terms)
+        print(f"bm25_bench: corpus, {min(d0 + block, n_docs)} of {n_docs} passages", file=sys.stderr, flush=True)
     post_off = np.zeros(n_terms + 1, np.uint64)
     post_off[1:] = np.cumsum(counts, dtype=np.uint64)
     post_doc, post_tf = np.empty(int(post_off[-1]), np.uint32), np.empty(int(post_off[-1]), np.uint32)
@@ -108,6 +114,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--step-limit", type=int, default=300)
     ap.add_argument("--walk-ms-per-batch", type=float, default=None)
+    ap.add_argument("--allow-share", default="", help="comma-separated shares of allowed passages, e.g. 1.0,0.1,0.01")
+    ap.add_argument("--query-by-query", type=int, default=0, metavar="N")
     a = ap.parse_args()
     global STEP_LIMIT
     STEP_LIMIT = a.step_limit
@@ -170,6 +178,40 @@ def main():
     print(json.dumps(dict(what="c_batch_bm25_plus_rerank_without_walk", queries=a.batch, seconds=med, queries_per_s=a.batch / med,
                           postings_per_s=postings / med, overflow_fallbacks=ovf, assumed_walk_seconds=walk,
                           with_walk_queries_per_s_derived=a.batch / (med + walk))), flush=True)
+    # (e) under an allow-bitmap, beside the unmasked call on the same queries
+    packed_a, postings_a = pack(bm25_ref.synth_queries(13, nqa, a.terms))
+    for share in [float(x) for x in a.allow_share.split(",") if x]:
+        member = np.ones(post.n_docs, bool) if share >= 1.0 else rng.random(post.n_docs) < share
+        d_allow = la.DeviceArray.from_host(np.packbits(member, bitorder="little"))
+        plain, _ = timed(lambda: idx.search_batch_device(packed_a, fetch_k, out=out), a.warmup, a.repeats)
+        masked, ovf = timed(lambda: idx.search_batch_device(packed_a, fetch_k, out=out, allow=d_allow), a.warmup, a.repeats)
+        print(json.dumps(dict(what="e_score_select_reset_masked", allow_share=share, allowed=int(member.sum()), queries=nqa,
+                              unmasked_seconds=plain, masked_seconds=masked, masked_over_unmasked=masked / plain,
+                              sweep_difference_us_per_query=(masked - plain) / nqa * 1e6, overflow_fallbacks=ovf)), flush=True)
+        plain, _ = timed(lambda: idx.hybrid_rerank_device(packed, dk, dd, dc, fetch_k, 0.7, True, top_k), 1, max(3, a.repeats // 2))
+        masked, ovf = timed(lambda: idx.hybrid_rerank_device(packed, dk, dd, dc, fetch_k, 0.7, True, top_k, allow=d_allow), 1,
+                            max(3, a.repeats // 2))
+        print(json.dumps(dict(what="e_batch_bm25_plus_rerank_masked", allow_share=share, queries=a.batch, unmasked_seconds=plain,
+                              masked_seconds=masked, masked_over_unmasked=masked / plain, masked_queries_per_s=a.batch / masked,
+                              overflow_fallbacks=ovf)), flush=True)
+        d_allow.free()
+    # (f) one call per query against one call for all of them
+    if a.query_by_query:
+        n1 = min(a.query_by_query, a.batch)
+        q_off, q_term, q_idf = packed
+        singles = [(np.array([0, q_off[i + 1] - q_off[i]], np.uint32), q_term[q_off[i]:q_off[i + 1]], q_idf[q_off[i]:q_off[i + 1]])
+                   for i in range(n1)]
+        lists1 = [ann_lists(1) for _ in range(n1)]
+        head = (q_off[:n1 + 1].copy(), q_term[:q_off[n1]], q_idf[:q_off[n1]])
+        dkn, ddn, dcn = ann_lists(n1)
+
+        def one_by_one():
+            for qq, (k1, d1, c1) in zip(singles, lists1):
+                idx.hybrid_rerank_device(qq, k1, d1, c1, fetch_k, 0.7, True, top_k)
+        each, _ = timed(one_by_one, 1, 3)
+        together, _ = timed(lambda: idx.hybrid_rerank_device(head, dkn, ddn, dcn, fetch_k, 0.7, True, top_k), 1, 3)
+        print(json.dumps(dict(what="f_query_by_query_against_one_call", queries=n1, query_by_query_seconds=each, one_call_seconds=together,
+                              query_by_query_queries_per_s=n1 / each, one_call_queries_per_s=n1 / together)), flush=True)
     # (d) the sparse call at 64 positives per query
     stride = 64
     pos = np.sort(rng.integers(0, post.n_docs, size=(a.batch, stride)).astype(np.uint32), axis=1)
