@@ -12,7 +12,8 @@ HOST     := leann-rs_amd/host
 CXXFLAGS := -O2 -std=c++17 -ffp-contract=off -Wall -Wextra -Wno-unused-parameter
 
 all: $(CSRC)/libleann_hip.so oracle $(HOST)/leann $(HOST)/host_selftest $(HOST)/host_selftest_asan $(HOST)/serve_bench $(HOST)/row_screen_selftest \
-     $(HOST)/encode_plan_selftest $(HOST)/search_plan_selftest $(HOST)/device_mem_selftest $(HOST)/topk_plan_selftest $(HOST)/meta_plan_selftest
+     $(HOST)/encode_plan_selftest $(HOST)/search_plan_selftest $(HOST)/device_mem_selftest $(HOST)/topk_plan_selftest $(HOST)/meta_plan_selftest \
+     $(HOST)/meta_batch_selftest
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -71,12 +72,19 @@ $(HOST)/meta_plan_selftest: $(HOST)/meta_plan_selftest.cpp $(CSRC)/meta_plan.h i
 	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -o $@ \
 	    $(HOST)/meta_plan_selftest.cpp
 
+# how a batch of metadata filters is cut into launches (csrc/meta_batch_plan.h: shared programs, union columns, relocated words) and
+# what every planned launch answers per row, on the CPU under AddressSanitizer + UBSan: no GPU, no library
+$(HOST)/meta_batch_selftest: $(HOST)/meta_batch_selftest.cpp $(CSRC)/meta_batch_plan.h $(CSRC)/meta_plan.h include/leann_backend.h
+	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -o $@ \
+	    $(HOST)/meta_batch_selftest.cpp
+
 oracle:
 	$(MAKE) -s -C oracle
 
 clean:
 	rm -f $(CSRC)/*.o $(CSRC)/*.so $(HOST)/leann $(HOST)/host_selftest $(HOST)/host_selftest_asan $(HOST)/serve_bench $(HOST)/row_screen_selftest \
-	      $(HOST)/encode_plan_selftest $(HOST)/search_plan_selftest $(HOST)/device_mem_selftest $(HOST)/topk_plan_selftest $(HOST)/meta_plan_selftest
+	      $(HOST)/encode_plan_selftest $(HOST)/search_plan_selftest $(HOST)/device_mem_selftest $(HOST)/topk_plan_selftest $(HOST)/meta_plan_selftest \
+	      $(HOST)/meta_batch_selftest
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

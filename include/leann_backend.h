@@ -613,6 +613,43 @@ int leann_meta_eval(const leann_meta *m, const leann_meta_node *nodes, size_t n_
  * leann_backend_search_filtered[_exact]_batch_device, leann_scan_topk_device and leann_recompute_search_batch_device. */
 int leann_meta_eval_device(const leann_meta *m, const leann_meta_node *nodes, size_t n_nodes, const uint8_t *d_and, uint8_t *d_bitmap,
                            uint32_t *d_n_allowed, void *stream);
+/* n_out filters -> n_out bitmaps in one pass over the columns; bitmap i = what leann_meta_eval[_device] writes for filter i, bit for
+ * bit.  Filter i is nodes[node_off[i] .. node_off[i + 1]) in prefix order (node_off[0] == 0, monotone).  Bitmap i starts at
+ * bitmaps + i * stride: any stride >= ceil(n / 8) and any base alignment; of a row only the first ceil(n / 8) bytes are written (pad
+ * bits zero), the bytes between rows are left as they are.  Equal filters (the same compiled program, csrc/meta_batch_plan.h) are
+ * evaluated once: *n_distinct (optional) says how many programs ran.  A launch of meta_eval_batch_kernel takes up to 64 distinct
+ * programs over up to 16 distinct columns and 2^20 words of sets / bitsets; a batch beyond that is cut into several launches, never
+ * refused.  n_allowed [n_out]: optional counts.  n_out == 0 is LEANN_OK with nothing written.
+ * The _device form compiles and plans on the host, copies programs, pairs and words into a per-stream scratch block of the store
+ * with ONE stream-ordered copy from pageable host memory (so, like its single twin, it cannot be captured into a HIP graph), enqueues
+ * one kernel per launch on `stream` and returns without waiting.  d_and: optional, ONE device bitmap ANDed into every output.
+ * d_n_allowed [n_out]: optional device counters, zeroed on the stream and then set.  Every argument is validated before any device
+ * work, LEANN_ERR_INVALID naming it: a null store, nodes, offsets or bitmaps; node_off[0] != 0 or non-monotone offsets; stride <
+ * ceil(n / 8); a filter meta_compile refuses, as "filter <i>: <its message>". */
+int leann_meta_eval_batch(const leann_meta *m, const leann_meta_node *nodes, const size_t *node_off, size_t n_out,
+                          uint8_t *bitmaps, size_t stride, size_t *n_allowed /* [n_out], optional */, size_t *n_distinct /* optional */);
+int leann_meta_eval_batch_device(const leann_meta *m, const leann_meta_node *nodes, const size_t *node_off, size_t n_out,
+                                 const uint8_t *d_and /* optional, ONE bitmap for all */, uint8_t *d_bitmaps, size_t stride,
+                                 uint32_t *d_n_allowed /* [n_out], optional */, size_t *n_distinct /* optional */, void *stream);
+/* nq queries, query i under filter i: evaluate, then search.  Defined by delegation: query i's keys, f32 distance bits, count and
+ * four stats are what leann_backend_search_filtered_batch_device (mode 0, the walk) or leann_backend_search_filtered_exact_batch_device
+ * (mode 1; d_stats is not written) return for bitmap i = filter i evaluated by leann_meta_eval_device — on a composite, narrow-row or
+ * recompute-on handle too, their refusals (LEANN_ERR_UNSUPPORTED for mode 1 on narrow rows and recompute-on handles) included.  The
+ * delegated calls AND the index's live mask themselves.  d_n_allowed [nq]: optional, the rows filter i allows (before the live
+ * mask): what a caller needs to split a batch between the modes itself.  The bitmaps live in library scratch, at most 1 GiB at a
+ * time: the batch runs in chunks of max(1, 1 GiB / stride) queries, stride = ceil(n / 8) rounded up to 16, each chunk planned,
+ * evaluated and searched on its own (LEANN_DEBUG_META_BATCH_BYTES: a test hook that overrides the 1 GiB).  The scratch must outlive
+ * the work, so the _device form synchronises `stream` before it returns and cannot be captured into a HIP graph.
+ * LEANN_ERR_INVALID before any device work: a null argument or top_k == 0; leann_meta_len(m) != leann_backend_len(h); a store on
+ * another device than the handle's (a composite handle: its first device); a mode other than 0 or 1; bad offsets or a bad filter as
+ * in leann_meta_eval_batch.  After any error nothing of the call's stays allocated.  The host form takes host pointers for queries
+ * and results (stats and n_allowed optional). */
+int leann_backend_search_meta_batch_device(const leann_backend *h, const leann_meta *m, const float *d_queries, size_t nq, size_t top_k,
+                                           size_t complexity, const leann_meta_node *nodes, const size_t *node_off, int mode /* 0 walk, 1 exact */,
+                                           uint64_t *d_keys, float *d_dists, uint32_t *d_counts, uint32_t *d_stats, uint32_t *d_n_allowed, void *stream);
+int leann_backend_search_meta_batch(const leann_backend *h, const leann_meta *m, const float *queries, size_t nq, size_t top_k,
+                                    size_t complexity, const leann_meta_node *nodes, const size_t *node_off, int mode /* 0 walk, 1 exact */,
+                                    uint64_t *keys, float *dists, uint32_t *counts, uint32_t *stats, uint32_t *n_allowed);
 /* leann_backend_filter_create with the bitmap evaluated on the device (valid AND match, then the index's live mask) instead of
  * uploaded: the resulting leann_filter is the one leann_backend_filter_create makes from the same bitmap.  leann_meta_len(m) !=
  * leann_backend_len(h) or a store on another device than the handle's (a composite handle: its first device) -> LEANN_ERR_INVALID.

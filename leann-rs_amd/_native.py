@@ -118,6 +118,15 @@ SIGNATURES = {
     "leann_meta_eval": (C.c_int, [vp, vp, C.c_size_t, u8p, C.POINTER(C.c_size_t)]),
     "leann_meta_eval_device": (C.c_int, [vp, vp, C.c_size_t, vp, vp, vp, vp]),
     "leann_backend_filter_create_meta": (C.c_int, [vp, vp, vp, C.c_size_t, C.POINTER(vp)]),
+    # (a batch of filter trees: one leann_meta_node array and node_off [n_out + 1])
+    "leann_meta_eval_batch": (C.c_int, [vp, vp, C.POINTER(C.c_size_t), C.c_size_t, u8p, C.c_size_t, C.POINTER(C.c_size_t),
+                                        C.POINTER(C.c_size_t)]),
+    "leann_meta_eval_batch_device": (C.c_int, [vp, vp, C.POINTER(C.c_size_t), C.c_size_t, vp, vp, C.c_size_t, vp, C.POINTER(C.c_size_t),
+                                               vp]),
+    "leann_backend_search_meta_batch_device": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.POINTER(C.c_size_t), C.c_int,
+                                                         vp, vp, vp, vp, vp, vp]),
+    "leann_backend_search_meta_batch": (C.c_int, [vp, vp, f32p, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.POINTER(C.c_size_t), C.c_int,
+                                                  u64p, f32p, u32p, u32p, u32p]),
     "leann_backend_search_filtered_exact_batch_device": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp]),
     "leann_backend_search_filtered_batch_device": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t,
                                                             vp, vp, vp, vp, vp]),

@@ -215,6 +215,39 @@ class BackendSearcher:
         del keep
         return Filter(h)
 
+    def search_meta_batch(self, meta, queries, filters, top_k, complexity, mode="walk"):
+        """nq queries, query i under filters[i] (trees or their text) evaluated on the device from a metadata.MetaColumns store;
+        mode: "walk" | "exact".  Returns keys, dists, counts and the rows each filter allows."""
+        from .metadata import encode_trees
+        Q = np.ascontiguousarray(queries, np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dims():
+            raise LeannError(1, f"queries must be [nq x {self.dims()}]")
+        nq = Q.shape[0]
+        if len(filters) != nq:
+            raise LeannError(1, f"{len(filters)} filters for {nq} queries")
+        nodes, off, _, keep = encode_trees(filters)
+        keys = np.full((nq, top_k), np.iinfo(np.uint64).max, np.uint64)
+        dists = np.full((nq, top_k), np.inf, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        allowed = np.zeros(nq, np.uint32)
+        N.check(N.lib().leann_backend_search_meta_batch(self._h, meta._h, _p(Q, f32p), nq, top_k, complexity, nodes, off,
+                                                        {"walk": 0, "exact": 1}[mode], _p(keys, u64p), _p(dists, f32p), _p(counts, u32p),
+                                                        None, _p(allowed, u32p)))
+        del keep
+        return keys, dists, counts, allowed
+
+    def search_meta_batch_device(self, meta, d_queries, nq, filters, top_k, complexity, d_keys, d_dists, d_counts, d_stats=None,
+                                 d_n_allowed=None, mode="walk", stream=None):
+        """the same with device pointers (ints); synchronises `stream` before it returns.  mode may also be given as its number."""
+        from .metadata import encode_trees
+        if len(filters) != nq:
+            raise LeannError(1, f"{len(filters)} filters for {nq} queries")
+        nodes, off, _, keep = encode_trees(filters)
+        N.check(N.lib().leann_backend_search_meta_batch_device(self._h, meta._h, d_queries, nq, top_k, complexity, nodes, off,
+                                                               {"walk": 0, "exact": 1}.get(mode, mode), d_keys, d_dists, d_counts,
+                                                               d_stats, d_n_allowed, stream))
+        del keep
+
     def search_filter_batch(self, queries, top_k, complexity, flt, mode="auto"):
         """nq queries under a registered filter; mode: "walk" | "exact" | "auto" (the library chooses by the filter's selectivity)"""
         Q = np.ascontiguousarray(queries, np.float32)

@@ -73,6 +73,7 @@ static LeannKnobs *read_knobs_from_env() {
     if (const char *e = getenv("LEANN_COALESCE")) k->coalesce_off = !strcmp(e, "off") || !strcmp(e, "0");
     if (const char *e = getenv("LEANN_STAMP_BUF")) k->stamp_buf = strtoull(e, nullptr, 0);
     if (const char *e = getenv("LEANN_META_DEVICE")) k->meta_device = strcmp(e, "0") != 0;
+    if (const char *e = getenv("LEANN_DEBUG_META_BATCH_BYTES")) k->meta_batch_bytes = strtoull(e, nullptr, 0);
     return k;
 }
 static std::atomic<const LeannKnobs *> g_knobs{nullptr};

@@ -46,6 +46,8 @@ struct LeannKnobs {
     unsigned long long stamp_buf = 0; // LEANN_STAMP_BUF (diagnostic builds only)
     bool meta_device = true;         // LEANN_META_DEVICE=0: a host that evaluates metadata filters on the device (the C++ IndexSearcher)
                                      // takes its per-passage loop instead (A/B runs; leann_meta_device_enabled)
+    unsigned long long meta_batch_bytes = 0; // LEANN_DEBUG_META_BATCH_BYTES: the bitmap scratch leann_backend_search_meta_batch* holds at a
+                                     // time instead of 1 GiB, so that small tests cross chunk boundaries (0 = unset)
 };
 const LeannKnobs &leann_knobs();
 extern "C" void leann_debug_reload_env(void);

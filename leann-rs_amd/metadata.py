@@ -169,9 +169,8 @@ def _fill_value(dst, v, keep, in_list=False):
         raise LeannError(1, f"metadata filter: unsupported value {v!r}")
 
 
-def encode_tree(flt):
-    """(MetaNode array in prefix order, node count, objects to keep alive while the array is in use)"""
-    flat, keep = [], []
+def _flatten(flt):
+    flat = []
 
     def walk(f):
         if f[0] == "cond":
@@ -183,8 +182,12 @@ def encode_tree(flt):
             for c in f[1]:
                 walk(c)
     walk(_as_filter(flt))
-    nodes = (MetaNode * len(flat))()
-    for nd, f in zip(nodes, flat):
+    return flat
+
+
+def _fill_nodes(nodes, at, flat, keep):
+    for i, f in enumerate(flat):
+        nd = nodes[at + i]
         if f[0] == "cond":
             field = C.create_string_buffer(f[1].encode())
             keep.append(field)
@@ -192,7 +195,27 @@ def encode_tree(flt):
             _fill_value(nd.value, f[3], keep)
         else:
             nd.kind, nd.n_children = {"and": 1, "or": 2}[f[0]], len(f[1])
+
+
+def encode_tree(flt):
+    """(MetaNode array in prefix order, node count, objects to keep alive while the array is in use)"""
+    flat, keep = _flatten(flt), []
+    nodes = (MetaNode * len(flat))()
+    _fill_nodes(nodes, 0, flat, keep)
     return nodes, len(flat), keep
+
+
+def encode_trees(filters):
+    """a batch of filters as the ABI takes it: (one MetaNode array, node_off as a size_t array [len(filters) + 1], number of filters,
+    objects to keep alive while the arrays are in use)"""
+    flats, keep = [_flatten(f) for f in filters], []
+    off = (C.c_size_t * (len(flats) + 1))()
+    for i, flat in enumerate(flats):
+        off[i + 1] = off[i] + len(flat)
+    nodes = (MetaNode * max(off[len(flats)], 1))()
+    for i, flat in enumerate(flats):
+        _fill_nodes(nodes, off[i], flat, keep)
+    return nodes, off, len(flats), keep
 
 
 # ---- leann_meta ----------------------------------------------------------------------------------------------------------------
@@ -299,6 +322,28 @@ class MetaColumns:
         nodes, k, keep = encode_tree(flt)
         N.check(N.lib().leann_meta_eval_device(self._h, nodes, k, d_and, d_bitmap, d_n_allowed, stream))
         del keep
+
+    def eval_batch(self, filters, with_count=False):
+        """the allow-bitmaps of a batch of filters in one pass over the columns: np.uint8 [len(filters), ceil(n / 8)], row i what
+        eval(filters[i]) returns (and the numbers of allowed rows, np.int64 [len(filters)])"""
+        nodes, off, k, keep = encode_trees(filters)
+        nbytes = (self.len() + 7) // 8
+        out = np.zeros((k, max(nbytes, 1)), np.uint8)
+        cnt = (C.c_size_t * max(k, 1))()
+        N.check(N.lib().leann_meta_eval_batch(self._h, nodes, off, k, out.ctypes.data_as(u8p), out.shape[1], cnt, None))
+        del keep
+        out = out[:, :nbytes]
+        return (out, np.array(cnt[:k], np.int64)) if with_count else out
+
+    def eval_batch_device(self, filters, d_bitmaps, stride, d_and=None, d_n_allowed=None, stream=None):
+        """enqueue the batch into device memory (pointers as ints) on `stream`: bitmap i at d_bitmaps + i * stride, d_n_allowed u32
+        [len(filters)]; returns without waiting, with the number of distinct programs that run"""
+        nodes, off, k, keep = encode_trees(filters)
+        distinct = C.c_size_t(0)
+        N.check(N.lib().leann_meta_eval_batch_device(self._h, nodes, off, k, d_and, d_bitmaps, stride, d_n_allowed, C.byref(distinct),
+                                                     stream))
+        del keep
+        return int(distinct.value)
 
     def close(self):
         if self._h:
