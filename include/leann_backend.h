@@ -660,6 +660,68 @@ int leann_backend_filter_create_meta(const leann_backend *h, const leann_meta *m
  * not look at it: it is for a host that keeps a per-passage loop beside the device path (host/leann_host.hpp) and wants one switch. */
 int leann_meta_device_enabled(void);
 
+/* ---- refining results on exact rows (additive; csrc/refine.hip) -----------------------------------------------------------
+ * A bf16 or int8 index walks rounded rows and reports their distances, a recompute-on index 1 - <f, Wq> / ||W^T f||.  Refining is what
+ * FAISS IndexRefine and DiskANN's full-precision rerank do: the walk fetches fetch_k >= top_k candidates, only those are scored again
+ * on the exact f32 rows, the best top_k are returned.  The exact rows are an object of their own, beside the index: they may sit in
+ * HBM or in pinned host memory that the kernel reads in place across the bus (10-40 rows per query), so that an int8 index keeps its
+ * quarter of the DEVICE memory.  Every existing entry point, the refusals of narrow-row handles included, is exactly as it was.
+ *
+ * A leann_exact_rows names f32 rows [n x ld] the device can read, for positions key_offset .. key_offset + n - 1; ld % 4 == 0,
+ * ld >= dims, padding zero, dims in [1, 4096], n < 2^32 - 1.
+ *   _from_device  borrows rows on `device` (e.g. leann_backend_device_rows of an f32 handle); they must outlive the object.
+ *   _from_host    copies host rows [n x dims]: placement LEANN_EXACT_ROWS_HBM into device memory, LEANN_EXACT_ROWS_HOST into a
+ *                 library-owned block of pinned, device-mapped host memory (hipHostMalloc; no managed memory, nothing that needs
+ *                 XNACK).  If that block cannot be had: LEANN_ERR_DEVICE, the message naming placement 0 as the way out — never a
+ *                 silent fall-back.
+ *   _open         a "<stem>.embeddings" file (raw LE f32 [n x dims], src/index/embeddings.rs:21-153; `leann build --recompute` writes it
+ *                 beside the index) through the reader leann_backend_open uses for a stock directory; a missing file ->
+ *                 LEANN_ERR_NOT_FOUND naming `leann build --recompute`, a length that is no whole number of rows -> LEANN_ERR_FORMAT.
+ * An unknown placement, dims outside [1, 4096], a null pointer -> LEANN_ERR_INVALID before any device work.  _close waits for the
+ * device before it frees what the object owns.
+ *
+ * leann_rerank_batch_device.  Query q has the candidates d_keys[q * fetch_k + i], i < min(d_counts[q], fetch_k).  A candidate is VALID
+ * when key_offset <= key < key_offset + n; every other key — the UINT64_MAX tail value included — is skipped, counted in d_skipped[q]
+ * (optional [nq]) and no row is read for it: the kernel range-checks every key before it forms an address, so a list with garbage in
+ * it cannot fault the device.  Result: the valid candidates ordered by (dist, key) ascending, the first top_k of them;
+ * dist = 1 - canonical dot(q, X[key - key_offset]), the distance the f32 traversal kernels compute (wave_dist_rows, csrc/search.cuh;
+ * orc_dist_canon, oracle/oracle.c), so A REFINED DISTANCE IS, BIT FOR BIT, WHAT AN F32 INDEX OVER THE SAME ROWS REPORTS FOR THAT KEY.
+ * Unused tail: UINT64_MAX / +inf.  A key listed twice is returned twice.  Limits: 1 <= top_k <= fetch_k <= 1024; the queries have the
+ * rows' dims.  Queries, lists and results are on the rows' device.  The call only ENQUEUES one kernel on `stream`: it allocates
+ * nothing, copies nothing and does not wait, so it can stand in a captured HIP graph.
+ *
+ * leann_backend_search_refined_batch_device is defined by delegation: leann_backend_search_filtered_batch_device(h, ..., top_k =
+ * fetch_k, complexity, d_allow, allow_stride, ...) into library scratch (d_allow == NULL: the unfiltered search), then the rerank
+ * above; d_stats are the walk's.  ef = max(complexity, fetch_k) by the existing rule, so a fetch_k above `complexity` widens the beam.
+ * It works on every handle the walk works on — f32, bf16, int8, recompute-on, and composite handles, whose keys are global and whose
+ * lists live on the first device.  The scratch must outlive the work, so the call SYNCHRONISES `stream` before it returns and cannot
+ * be captured into a HIP graph.  LEANN_ERR_INVALID before any device work, the message naming the argument: a null argument; top_k ==
+ * 0, fetch_k > 1024, top_k > fetch_k; the rows' dims differ from the handle's; the rows sit on another device than the handle's (a
+ * composite handle: its first); the rows' positions do not cover [key_offset_h, key_offset_h + len) of the handle.  After any error
+ * nothing of the call's stays allocated.  leann_backend_search_refined_batch is the host-pointer twin: queries, allow-bitmap(s) and
+ * results (stats optional, [nq x 4]) on the host. */
+typedef struct leann_exact_rows leann_exact_rows;
+enum { LEANN_EXACT_ROWS_HBM = 0, LEANN_EXACT_ROWS_HOST = 1 };
+int leann_exact_rows_from_device(const float *d_rows, size_t n, size_t dims, size_t ld, int device, uint64_t key_offset,
+                                 leann_exact_rows **out);
+int leann_exact_rows_from_host(const float *rows, size_t n, size_t dims, int device, uint64_t key_offset, int placement,
+                               leann_exact_rows **out);
+int leann_exact_rows_open(const char *embeddings_path, size_t dims, int device, uint64_t key_offset, int placement,
+                          leann_exact_rows **out);
+size_t leann_exact_rows_len(const leann_exact_rows *r);
+int leann_exact_rows_placement(const leann_exact_rows *r); /* -1 for NULL */
+void leann_exact_rows_close(leann_exact_rows *r);
+int leann_rerank_batch_device(const leann_exact_rows *r, const float *d_queries, size_t nq, const uint64_t *d_keys,
+                              const uint32_t *d_counts, size_t fetch_k, size_t top_k, uint64_t *d_out_keys, float *d_out_dists,
+                              uint32_t *d_out_counts, uint32_t *d_skipped /* optional [nq] */, void *stream);
+int leann_backend_search_refined_batch_device(const leann_backend *h, const leann_exact_rows *r, const float *d_queries, size_t nq,
+                                              size_t top_k, size_t fetch_k, size_t complexity, const uint8_t *d_allow,
+                                              size_t allow_stride, uint64_t *d_keys, float *d_dists, uint32_t *d_counts,
+                                              uint32_t *d_stats, void *stream);
+int leann_backend_search_refined_batch(const leann_backend *h, const leann_exact_rows *r, const float *queries, size_t nq,
+                                       size_t top_k, size_t fetch_k, size_t complexity, const uint8_t *allow, size_t allow_stride,
+                                       uint64_t *keys, float *dists, uint32_t *counts, uint32_t *stats /* optional */);
+
 /* ---- sharded indexes (the reference has no counterpart: IndexSearcher owns one Box<dyn BackendSearcher>,
  * src/index/searcher.rs:68) --------------------------------------------------------------------------------------------------
  * One process, G devices: the composite handle leann_backend_open returns for a device list, or built here from rows / handles.

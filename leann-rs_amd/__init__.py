@@ -4,8 +4,8 @@ Layout: csrc/ (HIP kernels + C ABI, built into csrc/libleann_hip.so), host/ (C++
 reference's index layer + `leann search` CLI), and this thin ctypes mirror used by tests and bench.
 """
 from ._native import LeannError, lib, device_count, LIB_PATH  # noqa: F401
-from .backend import (BackendBuilder, BackendSearcher, BackendType, DiskAnnSearcher,  # noqa: F401
-                      HnswSearcher, RowType, ShardedIndex, quantize_i8, round_bf16)
+from .backend import (BackendBuilder, BackendSearcher, BackendType, DiskAnnSearcher, ExactRows,  # noqa: F401
+                      HnswSearcher, RowType, ShardedIndex, quantize_i8, rerank_batch_device, round_bf16)
 from .bm25 import Bm25Index  # noqa: F401
 from .device import DeviceArray, sync  # noqa: F401
 from .metadata import MetaColumns, parse_filter  # noqa: F401

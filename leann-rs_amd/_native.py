@@ -131,6 +131,17 @@ SIGNATURES = {
     "leann_backend_search_filtered_batch_device": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t,
                                                             vp, vp, vp, vp, vp]),
     "leann_backend_device_rows": (vp, [vp]),
+    "leann_exact_rows_from_device": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_uint64, C.POINTER(vp)]),
+    "leann_exact_rows_from_host": (C.c_int, [f32p, C.c_size_t, C.c_size_t, C.c_int, C.c_uint64, C.c_int, C.POINTER(vp)]),
+    "leann_exact_rows_open": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_uint64, C.c_int, C.POINTER(vp)]),
+    "leann_exact_rows_len": (C.c_size_t, [vp]),
+    "leann_exact_rows_placement": (C.c_int, [vp]),
+    "leann_exact_rows_close": (None, [vp]),
+    "leann_rerank_batch_device": (C.c_int, [vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp]),
+    "leann_backend_search_refined_batch_device": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t,
+                                                            vp, vp, vp, vp, vp]),
+    "leann_backend_search_refined_batch": (C.c_int, [vp, vp, f32p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, u8p, C.c_size_t,
+                                                     u64p, f32p, u32p, u32p]),
     "leann_synth_rows_device": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                          C.c_float, C.c_uint32, C.c_uint64, C.c_uint64, vp, vp]),
     "leann_scan_topk_device": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_size_t,

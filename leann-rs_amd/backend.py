@@ -272,6 +272,32 @@ class BackendSearcher:
         N.check(N.lib().leann_backend_search_filtered_batch_device(self._h, d_queries, nq, top_k, complexity, d_allow,
                                                                    allow_stride, d_keys, d_dists, d_counts, d_stats, stream))
 
+    def search_refined_batch(self, queries, top_k, fetch_k, complexity, rows, allow=None):
+        """the walk at top_k = fetch_k, then its candidates scored again on the exact rows of an ExactRows: the best top_k by the
+        f32 distance.  allow: None, or as in search_filtered_batch.  Returns keys, dists, counts."""
+        Q = np.ascontiguousarray(queries, np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dims():
+            raise LeannError(1, f"queries must be [nq x {self.dims()}]")
+        nq, stride = Q.shape[0], 0
+        if allow is not None:
+            allow = np.ascontiguousarray(allow, np.uint8)
+            stride = 0 if allow.ndim == 1 else allow.shape[1]
+            if allow.shape[-1] < (self.len() + 7) // 8 or (allow.ndim == 2 and allow.shape[0] != nq):
+                raise LeannError(1, "allow-bitmap shape does not match the index / the batch")
+        keys = np.full((nq, max(top_k, 1)), np.iinfo(np.uint64).max, np.uint64)
+        dists = np.full((nq, max(top_k, 1)), np.inf, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        N.check(N.lib().leann_backend_search_refined_batch(self._h, rows._h, _p(Q, f32p), nq, top_k, fetch_k, complexity,
+                                                           _p(allow, u8p), stride, _p(keys, u64p), _p(dists, f32p), _p(counts, u32p),
+                                                           None))
+        return keys, dists, counts
+
+    def search_refined_batch_device(self, rows, d_queries, nq, top_k, fetch_k, complexity, d_keys, d_dists, d_counts, d_allow=None,
+                                    allow_stride=0, d_stats=None, stream=None):
+        """the same with device pointers (ints); synchronises `stream` before it returns"""
+        N.check(N.lib().leann_backend_search_refined_batch_device(self._h, rows._h, d_queries, nq, top_k, fetch_k, complexity, d_allow,
+                                                                  allow_stride, d_keys, d_dists, d_counts, d_stats, stream))
+
     def set_coalescing(self, wait_us=200, max_batch=4096):
         """gather concurrent single-query search() callers into one batched launch ((0, 0) disables)"""
         N.check(N.lib().leann_backend_set_coalescing(self._h, wait_us, max_batch))
@@ -516,6 +542,74 @@ class Filter:
             self.close()
         except Exception:
             pass
+
+
+class ExactRows:
+    """exact f32 rows to refine search results on (leann_exact_rows, include/leann_backend.h "refining results on exact rows"):
+    placement "hbm" keeps them in device memory, "host" in pinned host memory the rerank kernel reads in place"""
+    PLACEMENTS = {"hbm": 0, "host": 1}
+
+    def __init__(self, handle, keep=None):
+        self._h = handle
+        self._keep = keep  # from_device: whatever owns the borrowed rows
+
+    @classmethod
+    def _placement(cls, placement):
+        if isinstance(placement, str) and placement not in cls.PLACEMENTS:
+            raise LeannError(1, f"placement = {placement!r} is neither 'hbm' nor 'host'")
+        return cls.PLACEMENTS.get(placement, placement)  # (an unknown number goes to the library, which refuses it)
+
+    @classmethod
+    def from_host(cls, X, device=0, key_offset=0, placement="hbm"):
+        X = np.ascontiguousarray(X, np.float32)
+        if X.ndim != 2:
+            raise LeannError(1, "ExactRows.from_host: rows must be [n x dims]")
+        h = C.c_void_p()
+        N.check(N.lib().leann_exact_rows_from_host(_p(X, f32p), X.shape[0], X.shape[1], device, key_offset, cls._placement(placement),
+                                                   C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_device(cls, d_rows_ptr, n, dims, ld, device=0, key_offset=0, keep=None):
+        """borrowed rows [n x ld] on `device` (e.g. BackendSearcher.device_rows_ptr() of an f32 index): they must outlive this object"""
+        h = C.c_void_p()
+        N.check(N.lib().leann_exact_rows_from_device(d_rows_ptr, n, dims, ld, device, key_offset, C.byref(h)))
+        return cls(h, keep)
+
+    @classmethod
+    def open(cls, path, dims, device=0, key_offset=0, placement="hbm"):
+        """a "<stem>.embeddings" file: raw f32 [n x dims], as `leann build --recompute` writes it beside the index"""
+        h = C.c_void_p()
+        N.check(N.lib().leann_exact_rows_open(os.fsencode(str(path)), dims, device, key_offset, cls._placement(placement), C.byref(h)))
+        return cls(h)
+
+    def len(self):
+        return int(N.lib().leann_exact_rows_len(self._h))
+
+    __len__ = len
+
+    def placement(self):
+        return {0: "hbm", 1: "host"}[N.lib().leann_exact_rows_placement(self._h)]
+
+    def close(self):
+        if self._h:
+            N.lib().leann_exact_rows_close(self._h)
+            self._h = None
+            self._keep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def rerank_batch_device(rows, d_queries, nq, d_keys, d_counts, fetch_k, top_k, d_out_keys, d_out_dists, d_out_counts, d_skipped=None,
+                        stream=None):
+    """leann_rerank_batch_device: the candidate lists d_keys [nq x fetch_k] scored on the exact rows, best top_k out; device pointers
+    (ints).  Only enqueues on `stream`."""
+    N.check(N.lib().leann_rerank_batch_device(rows._h, d_queries, nq, d_keys, d_counts, fetch_k, top_k, d_out_keys, d_out_dists,
+                                              d_out_counts, d_skipped, stream))
 
 
 class ShardedIndex:

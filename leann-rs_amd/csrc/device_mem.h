@@ -3,7 +3,7 @@
 // freed exactly once.  ScratchLease<T> is the same for a block of scan.hip's scratch pool: it goes back to the pool exactly once.
 // Plain C++17, no HIP types: every allocation goes through the four functions below (defined once, in api.hip over hipMalloc /
 // hipFree and in scan.hip over the pool), and the CPU selftest (host/device_mem_selftest.cpp) defines them over malloc / free to
-// count what the two types ask for.
+// count what the two types ask for.  PinnedBuf<T> is the host-memory counterpart (two functions of its own, refine.hip).
 #pragma once
 #include "../../include/leann_backend.h"
 #include <cassert>
@@ -52,6 +52,36 @@ struct DeviceBuf {
     }
     T *release() { T *q = p; p = nullptr; cap = 0; return q; } // ownership leaves the type (no caller in the library does this today)
     void reset() { leann_internal_device_release(p); p = nullptr; cap = 0; }
+};
+
+// DeviceBuf's host counterpart: a block of pinned host memory that is mapped into the current device's address space, so that a
+// kernel reads it in place across the bus (refine.hip: exact rows kept on the host).  `dev` is the address kernels use, `p` the
+// host's.  The two functions are defined once, in refine.hip, over hipHostMalloc / hipHostFree; a block counts in
+// leann_debug_device_blocks like any other the library owns.
+void *leann_internal_pinned_alloc(size_t bytes, void **dev); // null on failure
+void leann_internal_pinned_release(void *p);                 // null is fine
+template <typename T>
+struct PinnedBuf {
+    T *p = nullptr;
+    T *dev = nullptr;
+    size_t cap = 0; // in elements
+
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { reset(); }
+
+    int alloc(size_t count) { // into an empty buffer; the caller words the message of a failure
+        assert(!p);
+        const size_t bytes = count * sizeof(T);
+        void *d = nullptr;
+        p = static_cast<T *>(leann_internal_pinned_alloc(bytes ? bytes : 16, &d));
+        if (!p) return LEANN_ERR_DEVICE;
+        dev = static_cast<T *>(d);
+        cap = count;
+        return LEANN_OK;
+    }
+    void reset() { leann_internal_pinned_release(p); p = dev = nullptr; cap = 0; }
 };
 
 // A block of the scratch pool, given back by the destructor.  The pool's rule is the holder's to keep: every stream that touched the

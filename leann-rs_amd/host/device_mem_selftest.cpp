@@ -1,5 +1,5 @@
 // device_mem_selftest — the owning buffer type and the scratch-pool lease of the host side (csrc/device_mem.h) on the CPU, under
-// AddressSanitizer + UBSan: no GPU, no library.  The four functions the header declares (allocation, scratch pool) are defined HERE,
+// AddressSanitizer + UBSan: no GPU, no library.  The functions the header declares (allocation, scratch pool, pinned host blocks) are defined HERE,
 // over malloc / free with counters and a "fail the next N allocations" switch; that link-time seam is the whole hook.  A double free, a leak or a use after free is the
 // sanitizer's to report; the counters check what was asked for and in which order.
 #include "../csrc/device_mem.h"
@@ -52,6 +52,23 @@ void leann_internal_scratch_release(void *p) {
     if (!p) return;
     g_leased--;
     g_returns++;
+    free(p);
+}
+
+static long g_pinned = 0, g_pins = 0, g_unpins = 0; // PinnedBuf's two functions: the "device address" is the host's plus a constant
+static size_t g_last_pin_bytes = 0;
+void *leann_internal_pinned_alloc(size_t bytes, void **dev) {
+    *dev = nullptr;
+    g_last_pin_bytes = bytes;
+    if (g_fail_next > 0) { g_fail_next--; return nullptr; }
+    char *p = static_cast<char *>(malloc(bytes));
+    if (p) { g_pinned++; g_pins++; *dev = p + 1; }
+    return p;
+}
+void leann_internal_pinned_release(void *p) {
+    if (!p) return;
+    g_pinned--;
+    g_unpins++;
     free(p);
 }
 
@@ -200,6 +217,23 @@ int main() {
         CHECK(a.acquire(1) == LEANN_OK && a.p && g_leased == 1);
     }
     CHECK(g_leased == 0 && g_acquires == g_returns);
+
+    { // pinned host block: count * sizeof(T) bytes asked for, both addresses kept, freed exactly once; reset() twice frees once; a
+      // failed allocation leaves the buffer empty with LEANN_ERR_DEVICE and a later one succeeds; a zero count still yields a block
+        PinnedBuf<float> a;
+        CHECK(a.p == nullptr && a.dev == nullptr && a.cap == 0);
+        CHECK(a.alloc(6) == LEANN_OK && a.p && g_last_pin_bytes == 24 && a.cap == 6 && g_pinned == 1);
+        CHECK(reinterpret_cast<char *>(a.dev) == reinterpret_cast<char *>(a.p) + 1);
+        a.p[5] = 1.0f;
+        const long unpins = g_unpins;
+        a.reset();
+        a.reset();
+        CHECK(a.p == nullptr && a.dev == nullptr && a.cap == 0 && g_pinned == 0 && g_unpins == unpins + 1);
+        g_fail_next = 1;
+        CHECK(a.alloc(100) == LEANN_ERR_DEVICE && a.p == nullptr && a.dev == nullptr && a.cap == 0 && g_pinned == 0);
+        CHECK(a.alloc(0) == LEANN_OK && a.p && a.cap == 0 && g_last_pin_bytes > 0 && g_pinned == 1);
+    }
+    CHECK(g_pinned == 0 && g_pins == g_unpins && g_pins == 2);
 
     CHECK(g_live == 0 && g_allocs == g_frees);
     if (g_failed) { fprintf(stderr, "device_mem_selftest: %d check(s) FAILED\n", g_failed); return 1; }

@@ -29,6 +29,8 @@ struct SearchArgs {
     bool bm25_device = true;
     bool hybrid_filter_inside = false;
     std::optional<std::string> queries_file;
+    size_t refine = 0;           // additive: --refine <FETCH_K> (SearchOptions::refine_fetch_k)
+    bool refine_rows_host = true;
 };
 
 static void usage_search() {
@@ -55,6 +57,10 @@ static void usage_search() {
          "                                     with --hybrid, one device BM25 + rerank call; prints a JSON array with one result array per query\n"
          "      --bm25 <WHERE>                 (additive) where hybrid mode scores BM25: device (inverted index in HBM) or host; same output [default: device] [possible values: device, host]\n"
          "      --hybrid-filter <WHEN>         (additive) hybrid mode: inside = BM25 and its rerank see only what --device-filter allows and no removed passage; post = filter after the rerank [default: post] [possible values: inside, post]\n"
+         "      --refine <FETCH_K>             (additive) fetch FETCH_K candidates from the walk and score them again on the exact f32 rows of\n"
+         "                                     documents.embeddings (`leann build --recompute`): an int8 / bf16 index then prints an f32 index's scores;\n"
+         "                                     not with --hybrid (short queries are not switched to hybrid either)\n"
+         "      --refine-rows <WHERE>          (additive) where --refine keeps the exact rows: host (pinned memory read across the bus) or hbm [default: host] [possible values: hbm, host]\n"
          "  -h, --help                         Print help");
 }
 
@@ -97,12 +103,17 @@ static int run_search(int argc, char **argv) {
         else if (name == "--queries-file") a.queries_file = val();
         else if (name == "--bm25") { std::string w = val(); if (w != "device" && w != "host") throw Error("invalid value '" + w + "' for '--bm25 <WHERE>' [possible values: device, host]"); a.bm25_device = w == "device"; }
         else if (name == "--hybrid-filter") { std::string w = val(); if (w != "inside" && w != "post") throw Error("invalid value '" + w + "' for '--hybrid-filter <WHEN>' [possible values: inside, post]"); a.hybrid_filter_inside = w == "inside"; }
+        else if (name == "--refine") { a.refine = std::stoul(val()); if (a.refine == 0) throw Error("invalid value '0' for '--refine <FETCH_K>': at least 1"); }
+        else if (name == "--refine-rows") { std::string w = val(); if (w != "hbm" && w != "host") throw Error("invalid value '" + w + "' for '--refine-rows <WHERE>' [possible values: hbm, host]"); a.refine_rows_host = w == "host"; }
         else if (name == "-v" || name == "--verbose" || name == "-q" || name == "--quiet") {}
         else if (!s.empty() && s[0] == '-' && s.size() > 1) throw Error("unexpected argument '" + s + "' found");
         else if (!have_query) { a.query = s; have_query = true; }
         else throw Error("unexpected argument '" + s + "' found");
     }
     if (!have_query && !a.queries_file) throw Error("the following required arguments were not provided:\n  <QUERY>");
+    if (a.refine && a.hybrid)
+        throw Error("--refine together with --hybrid is not supported: the hybrid rerank blends the walk's distances, and refining inside it "
+                    "is a follow-up; drop one of the two");
 
     // search.rs:75-88
     std::string index_name;
@@ -132,7 +143,7 @@ static int run_search(int argc, char **argv) {
     }
     size_t word_count = 0;
     { std::istringstream ws(a.query); for (std::string w; ws >> w;) word_count++; }
-    const bool use_hybrid = a.hybrid || (a.auto_hybrid && word_count <= 3); // search.rs:147-148
+    const bool use_hybrid = a.hybrid || (a.auto_hybrid && word_count <= 3 && !a.refine); // search.rs:147-148 (--refine: never switched on by itself)
 
     auto embed_query = [&](const std::string &text) -> std::vector<float> {
         if (a.query_vector_file) {
@@ -180,6 +191,7 @@ static int run_search(int argc, char **argv) {
         if (filter) opts.with_filter(*filter);
         if (filter && a.device_filter) opts.with_device_filter(*a.filter);
         if (a.hybrid) opts.with_hybrid("", a.hybrid_alpha);
+        if (a.refine) opts.with_refine(a.refine, a.refine_rows_host);
         opts.with_compat_polarity(a.compat_polarity).with_bm25_device(a.bm25_device).with_hybrid_filter_inside(a.hybrid_filter_inside);
         lj::Value all = lj::Value::array();
         for (auto &rs : searcher.search_batch_with_options(embeddings, texts, opts)) all.a->push_back(results_json(rs));
@@ -196,6 +208,7 @@ static int run_search(int argc, char **argv) {
         if (filter) opts.with_filter(*filter);
         if (filter && a.device_filter) opts.with_device_filter(*a.filter);
         if (use_hybrid) opts.with_hybrid(a.query, a.hybrid_alpha);
+        if (a.refine) opts.with_refine(a.refine, a.refine_rows_host);
         opts.with_compat_polarity(a.compat_polarity).with_bm25_device(a.bm25_device).with_hybrid_filter_inside(a.hybrid_filter_inside);
         results = searcher.search_with_options(q, opts);
     };

@@ -514,7 +514,15 @@ struct SearchOptions {
     // that the post-filter then drops, and a removed or filtered-out best hit does not set max_bm25.  false (default): the filter and
     // the removals act after the rerank, as before.  `leann search --hybrid-filter inside|post`.
     bool hybrid_filter_inside = false;
+    // Additive (include/leann_backend.h "refining results on exact rows"): the walk fetches refine_fetch_k candidates (at least what
+    // the search asks of the backend), they are scored again on the exact f32 rows of "<stem>.embeddings" and the best are kept: an int8
+    // or bf16 index then returns the distances — hence the scores — an f32 index reports.  0 = off.  refine_rows_host: the exact rows
+    // stay in pinned host memory that the kernel reads in place (the index keeps its share of the device memory); false: in HBM.
+    // Hybrid mode is left alone: refine together with hybrid is refused.  `leann search --refine <FETCH_K> [--refine-rows hbm|host]`.
+    size_t refine_fetch_k = 0;
+    bool refine_rows_host = true;
     SearchOptions(size_t k, size_t c) : top_k(k), complexity(c) {}
+    SearchOptions &with_refine(size_t fetch_k, bool rows_on_host = true) { refine_fetch_k = fetch_k; refine_rows_host = rows_on_host; return *this; }
     SearchOptions &with_device_filter(std::string key) { device_filter = true; filter_key = std::move(key); return *this; }
     SearchOptions &with_filter(MetadataFilter f) { filter = std::move(f); return *this; }
     SearchOptions &with_hybrid(std::string q, float alpha) { hybrid = true; hybrid_alpha = alpha; query_text = std::move(q); return *this; }
@@ -560,6 +568,7 @@ class IndexSearcher {
         leann_backend *h = nullptr;
         check(leann_backend_open(index_path.c_str(), backend, meta.dimensions, device, &h));
         s.backend_.reset(h, leann_backend_close);
+        s.index_path_ = index_path;
         s.bm25_device_id_ = (int)std::strtol(device ? device : "0", nullptr, 10); // a list / range: its first device holds the result lists
         // removed positions (leann_backend_remove / `leann delete`), read once per handle: the backend never returns them, but BM25
         // is scored over every passage of the store and would bring them back through the hybrid branch
@@ -588,6 +597,10 @@ class IndexSearcher {
         if (query_embedding.size() != leann_backend_dims(backend_.get()))
             throw Error("query embedding has " + std::to_string(query_embedding.size()) + " dimensions, index has " +
                         std::to_string(leann_backend_dims(backend_.get())));
+        if (opts.refine_fetch_k) { // the walk's candidates scored again on the exact rows; the score is the refined distance (N1, as below)
+            auto lists = refined_lists(query_embedding.data(), 1, opts, fetch_k);
+            return assemble_results(std::move(lists[0]), opts, fetch_k);
+        }
         if (opts.filter && opts.device_filter) {
             // every returned position already passes the filter, so no over-fetch is needed for it
             if (!opts.hybrid) { fetch_k = opts.top_k; }
@@ -662,6 +675,17 @@ class IndexSearcher {
                                                                      const SearchOptions &opts) const {
         const size_t nq = query_embeddings.size(), dims = leann_backend_dims(backend_.get());
         if (query_texts.size() != nq) throw Error("search_batch_with_options: one query text per embedding is required");
+        if (opts.refine_fetch_k) { // one walk and one rerank for the whole batch; per query the result of search_with_options
+            std::vector<float> q(nq * dims);
+            for (size_t i = 0; i < nq; i++) {
+                if (query_embeddings[i].size() != dims)
+                    throw Error("query embedding has " + std::to_string(query_embeddings[i].size()) + " dimensions, index has " + std::to_string(dims));
+                std::copy(query_embeddings[i].begin(), query_embeddings[i].end(), q.begin() + i * dims);
+            }
+            std::vector<std::vector<SearchResult>> refined;
+            for (auto &list : refined_lists(q.data(), nq, opts, opts.filter ? opts.top_k * 5 : opts.top_k)) refined.push_back(finish_results(list, opts));
+            return refined;
+        }
         const size_t fetch_k = opts.top_k * 5;
         leann_bm25 *dev = (opts.hybrid && device_bm25_applies(opts, fetch_k)) ? bm25_device(bm25()) : nullptr;
         std::vector<std::vector<SearchResult>> out;
@@ -745,6 +769,42 @@ class IndexSearcher {
     bool is_empty() const { return len() == 0; }
 
   private:
+    // `want` results per query from the walk at max(refine_fetch_k, want) candidates, refined on the exact rows (opened on first use)
+    std::vector<std::vector<std::pair<size_t, float>>> refined_lists(const float *q, size_t nq, const SearchOptions &opts, size_t want) const {
+        if (opts.hybrid)
+            throw Error("--refine together with --hybrid is not supported: the hybrid rerank blends the walk's distances, and refining "
+                        "inside it is a follow-up; drop one of the two");
+        if (opts.filter && opts.device_filter)
+            throw Error("--refine together with --device-filter is not supported yet; without --device-filter the filter acts after the refined search");
+        want = std::max<size_t>(want, 1);
+        const size_t fetch_k = std::max(opts.refine_fetch_k, want);
+        std::vector<uint64_t> keys(nq * want);
+        std::vector<float> dists(nq * want);
+        std::vector<uint32_t> counts(nq);
+        check(leann_backend_search_refined_batch(backend_.get(), exact_rows(opts.refine_rows_host), q, nq, want, fetch_k, opts.complexity, nullptr,
+                                                 0, keys.data(), dists.data(), counts.data(), nullptr));
+        std::vector<std::vector<std::pair<size_t, float>>> lists(nq);
+        for (size_t i = 0; i < nq; i++)
+            for (size_t j = 0; j < counts[i]; j++) lists[i].emplace_back((size_t)keys[i * want + j], dists[i * want + j]);
+        return lists;
+    }
+    const leann_exact_rows *exact_rows(bool on_host) const {
+        std::lock_guard<std::mutex> lk(*bm25_mu_);
+        std::shared_ptr<leann_exact_rows> &slot = exact_->handle[on_host ? 1 : 0];
+        if (!slot) {
+            const std::string emb = with_extension(index_path_, "embeddings");
+            if (!file_exists(emb))
+                throw Error("--refine needs the exact rows, and " + emb + " does not exist: build the index with `leann build --recompute`, "
+                            "which writes them beside the index");
+            leann_exact_rows *raw = nullptr;
+            check(leann_exact_rows_open(emb.c_str(), leann_backend_dims(backend_.get()), bm25_device_id_, 0,
+                                        on_host ? LEANN_EXACT_ROWS_HOST : LEANN_EXACT_ROWS_HBM, &raw));
+            slot.reset(raw, leann_exact_rows_close);
+            if (host_log_debug())
+                fprintf(stderr, "DEBUG leann: %zu exact rows of %s kept in %s\n", leann_exact_rows_len(raw), emb.c_str(), on_host ? "pinned host memory" : "HBM");
+        }
+        return slot.get();
+    }
     bool is_removed(size_t pos) const { return (pos >> 3) < removed_.size() && ((removed_[pos >> 3] >> (pos & 7)) & 1); }
     const Bm25Scorer &bm25() const {
         std::lock_guard<std::mutex> lk(*bm25_mu_);
@@ -1058,6 +1118,9 @@ class IndexSearcher {
     std::shared_ptr<MetaStore> meta_ = std::make_shared<MetaStore>();
     PassageStore passages_;
     std::shared_ptr<leann_backend> backend_;
+    std::string index_path_;
+    struct ExactRows { std::shared_ptr<leann_exact_rows> handle[2]; }; // [0] in HBM, [1] in pinned host memory; opened by the first refined search
+    std::shared_ptr<ExactRows> exact_ = std::make_shared<ExactRows>();
     std::vector<std::string> id_map_;
     std::vector<uint8_t> removed_; // bitmap of removed positions; empty when nothing is removed
     std::shared_ptr<std::map<std::string, RegisteredFilter>> filters_ = std::make_shared<std::map<std::string, RegisteredFilter>>();
