@@ -18,6 +18,9 @@ all: $(CSRC)/libleann_hip.so oracle $(HOST)/leann $(HOST)/host_selftest $(HOST)/
 $(CSRC)/%.o: $(CSRC)/%.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# scan_lists.hip's scores are single fmaf chains: no packed-f32 forms of them
+$(CSRC)/scan_lists.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+
 $(CSRC)/libleann_hip.so: $(HIP_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HIP_OBJS)
 

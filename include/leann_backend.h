@@ -324,6 +324,31 @@ int leann_backend_search_filtered_exact_batch_device(const leann_backend *h, con
                                                      size_t nq, size_t top_k, const uint8_t *d_allow,
                                                      size_t allow_stride, uint64_t *d_keys, float *d_dists,
                                                      uint32_t *d_counts, void *stream);
+/* ---- exact search over per-query position lists (additive; DESIGN.md §4 "score_lists_kernel", csrc/scan_lists.hip) ------------------------
+ * Reference: the metadata filter around the backend call, src/index/searcher.rs:129-133,:190-194 — per query: over-fetch, then drop
+ * what the filter rejects.  A caller that already holds the allowed positions of each query (a tenant's row ids, an ACL's list, a
+ * BM25 posting list) passes them as they are instead of building a bitmap of n / 8 bytes per query.
+ * Definition.  Query i's answer is what leann_backend_search_filtered_exact_batch_device returns for query i under the bitmap whose
+ * set bits are the valid entries of its list, bit for bit: dist = 1 - s, s the single chain acc = fmaf(x[j], q[j], acc), j ascending
+ * from acc = +0 over dims rounded up to a multiple of 32 with zeros; results ascending by (dist, key), ties to the lower position;
+ * keys = position + key_offset; the unused tail is UINT64_MAX / +inf; counts [nq].
+ * Lists.  list_off [n_lists + 1] (HOST, from 0, monotone; a list holds fewer than 2^31 entries) cuts d_lists into lists of positions
+ * local to h.  Query i is scanned over list q_list[i] (HOST, [nq]); q_list == NULL: n_lists == nq and query i takes list i.  A list need
+ * not be sorted.  A position listed twice is returned twice (as leann_rerank_batch_device does).  A position >= leann_backend_len(h)
+ * is skipped and counted in d_skipped[i] (optional, [nq]); a removed position is skipped and not counted; every position is
+ * range-checked before it becomes an address.  An empty list gives count 0.
+ * LEANN_ERR_INVALID, before any device work and naming the argument: a null argument, top_k outside [1, 1024], list_off[0] != 0 or
+ * non-monotone offsets, q_list[i] >= n_lists, q_list == NULL with n_lists != nq.  LEANN_ERR_UNSUPPORTED: a recompute-on, bf16 or int8
+ * handle (no f32 rows to scan), and a composite handle (lists are local to one handle: pass bitmaps, which are sliced per shard).
+ * The _device form uses library scratch and synchronises `stream` before it returns; it cannot be captured into a HIP graph. */
+int leann_backend_search_exact_lists_batch_device(const leann_backend *h, const float *d_queries, size_t nq, size_t top_k,
+                                                  const uint64_t *list_off, const uint32_t *d_lists, size_t n_lists,
+                                                  const uint32_t *q_list, uint64_t *d_keys, float *d_dists, uint32_t *d_counts,
+                                                  uint32_t *d_skipped, void *stream);
+/* ... queries, lists and results on the host */
+int leann_backend_search_exact_lists_batch(const leann_backend *h, const float *queries, size_t nq, size_t top_k,
+                                           const uint64_t *list_off, const uint32_t *lists, size_t n_lists, const uint32_t *q_list,
+                                           uint64_t *keys, float *dists, uint32_t *counts, uint32_t *skipped);
 /* device pointer of the rows (for ground-truth scans); NULL for a composite handle and for a handle without f32 rows (bf16 or int8 rows) */
 const float *leann_backend_device_rows(const leann_backend *h);
 

@@ -128,6 +128,9 @@ SIGNATURES = {
     "leann_backend_search_meta_batch": (C.c_int, [vp, vp, f32p, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.POINTER(C.c_size_t), C.c_int,
                                                   u64p, f32p, u32p, u32p, u32p]),
     "leann_backend_search_filtered_exact_batch_device": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp]),
+    "leann_backend_search_exact_lists_batch_device": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, u64p, vp, C.c_size_t, u32p, vp, vp, vp, vp, vp]),
+    "leann_backend_search_exact_lists_batch": (C.c_int, [vp, f32p, C.c_size_t, C.c_size_t, u64p, u32p, C.c_size_t, u32p, u64p, f32p, u32p,
+                                                         u32p]),
     "leann_backend_search_filtered_batch_device": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t,
                                                             vp, vp, vp, vp, vp]),
     "leann_backend_device_rows": (vp, [vp]),

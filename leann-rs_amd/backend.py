@@ -197,6 +197,40 @@ class BackendSearcher:
         N.check(N.lib().leann_backend_search_filtered_exact_batch_device(self._h, d_queries, nq, top_k, d_allow, allow_stride,
                                                                          d_keys, d_dists, d_counts, stream))
 
+    def search_exact_lists_batch(self, queries, top_k, lists, q_list=None):
+        """exact answer of query i over the positions of lists[q_list[i]] (q_list None: lists[i]); lists: a sequence of uint32 position
+        arrays, unsorted and with duplicates if the caller likes.  Returns keys, dists, counts and, per query, how many listed positions
+        lay beyond the index."""
+        Q = np.ascontiguousarray(queries, np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dims():
+            raise LeannError(1, f"queries must be [nq x {self.dims()}]")
+        parts = [np.ascontiguousarray(l, np.uint32).reshape(-1) for l in lists]
+        off = np.zeros(len(parts) + 1, np.uint64)
+        off[1:] = np.cumsum([p.shape[0] for p in parts], dtype=np.uint64)
+        flat = np.concatenate(parts) if parts else np.zeros(0, np.uint32)
+        flat = np.ascontiguousarray(flat if flat.size else np.zeros(1, np.uint32), np.uint32)
+        ql = None if q_list is None else np.ascontiguousarray(q_list, np.uint32)
+        if ql is not None and ql.shape != (Q.shape[0],):
+            raise LeannError(1, "q_list must hold one list number per query")
+        nq = Q.shape[0]
+        keys = np.full((nq, top_k), np.iinfo(np.uint64).max, np.uint64)
+        dists = np.full((nq, top_k), np.inf, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        skipped = np.zeros(nq, np.uint32)
+        N.check(N.lib().leann_backend_search_exact_lists_batch(self._h, _p(Q, f32p), nq, top_k, _p(off, u64p), _p(flat, u32p), len(parts),
+                                                               None if ql is None else _p(ql, u32p), _p(keys, u64p), _p(dists, f32p),
+                                                               _p(counts, u32p), _p(skipped, u32p)))
+        return keys, dists, counts, skipped
+
+    def search_exact_lists_batch_device(self, d_queries, nq, top_k, list_off, d_lists, n_lists, q_list, d_keys, d_dists, d_counts,
+                                        d_skipped=None, stream=None):
+        """list_off (uint64 [n_lists + 1]) and q_list (uint32 [nq] or None) are host arrays, everything else device pointers"""
+        off = np.ascontiguousarray(list_off, np.uint64)
+        ql = None if q_list is None else np.ascontiguousarray(q_list, np.uint32)
+        N.check(N.lib().leann_backend_search_exact_lists_batch_device(self._h, d_queries, nq, top_k, _p(off, u64p), d_lists, n_lists,
+                                                                      None if ql is None else _p(ql, u32p), d_keys, d_dists, d_counts,
+                                                                      d_skipped, stream))
+
     def register_filter(self, allow):
         """upload + compact an allow-bitmap once; returns a Filter for search_filter_batch (close() it when done)"""
         allow = np.ascontiguousarray(allow, np.uint8)

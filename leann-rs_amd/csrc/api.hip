@@ -592,6 +592,9 @@ static int search_filtered_batch_host_impl(const leann_backend *hc, const float 
     leann_backend *h = const_cast<leann_backend *>(hc);
     // exact scan of the allowed rows, or the walk with the filter inside?  FILTER_AUTO (registered filters only: the count is known):
     // exact up to 5 % of the rows / 64k rows for small batches, 1.5 % for large ones, when the index stores vectors
+    // (how an exact answer is computed is a second rule, scan.hip: one bitmap per query and nq > 1 -> batched compaction and
+    // score_lists_kernel, scan_lists.hip — 1.13 ms against 9.05 ms for 64 queries under 64 filters at 1M x 768, profiles/exact_lists.md;
+    // a bitmap shared by the batch, a registered filter and a single query keep the MFMA list kernel: no crossover was measured there)
     bool exact = mode == FILTER_EXACT;
     const leann_backend *first = hc && hc->sharded ? leann_internal_sharded_shard(hc->sharded, 0) : hc;
     const bool stored_vectors = first && !first->g.feat_h && !leann_internal_narrow_rows(first); // f32 rows an exact scan can read

@@ -288,6 +288,19 @@ int leann_internal_filtered_exact(const float *d_rows, size_t n, size_t dims, si
 // scan.hip: bitmap over n positions -> *list, the allowed positions ascending (left empty when there are none), *n_list; synchronises
 // the stream once for the count.  The lease ends only once the stream that read the list is synchronised.
 int leann_internal_compact_allow(const uint8_t *d_allow, size_t n, ScratchLease<uint32_t> *list, size_t *n_list, hipStream_t st);
+// scan.hip: the same for nq bitmaps `stride` bytes apart in one pass -> one CSR: list q at [(*off)[q], (*off)[q + 1]) of *lists
+int leann_internal_compact_allow_batch(const uint8_t *d_allow, size_t stride, size_t n, size_t nq, ScratchLease<uint32_t> *lists,
+                                       std::vector<uint64_t> *off, hipStream_t st);
+// scan_lists.hip: exact top-k of query i over the listed positions of list q_list[i] (null: list i) — score_lists_kernel, one launch
+// for every query's rows.  list_off [n_lists + 1] is on the host and checked by the caller, d_lists on the device; d_live: optional
+// live mask (a position whose bit is clear is skipped); d_skipped: optional [nq], entries >= n per query.  Results as
+// leann_internal_filtered_exact's.  Returns with `st` synchronised.
+int leann_internal_exact_lists(const float *d_rows, size_t n, size_t dims, size_t ld, const uint8_t *d_live, const float *d_queries, size_t nq,
+                               size_t top_k, const uint64_t *list_off, const uint32_t *d_lists, const uint32_t *q_list, uint64_t key_offset,
+                               uint64_t *d_keys, float *d_dists, uint32_t *d_counts, uint32_t *d_skipped, hipStream_t st);
+// Whether leann_internal_filtered_exact sends per-query bitmaps (allow_stride != 0, nq > 1) through the two functions above instead of
+// compacting and scanning query by query.  The measurement that decides it: profiles/exact_lists.md, shape a.
+constexpr bool LEANN_EXACT_LISTS_ROUTING = true;
 int leann_internal_and_live_inplace(const leann_backend *h, uint8_t *d_bitmap);
 // scan.hip: segment top-k of a score slab and the reduction of its winners (bm25.hip's segment fallback, and the select step below)
 int leann_internal_topk_chunk(const float *S, size_t rows, size_t nq, uint32_t k, const uint8_t *allow, uint64_t pos0, uint64_t *cand,
@@ -295,6 +308,9 @@ int leann_internal_topk_chunk(const float *S, size_t rows, size_t nq, uint32_t k
 int leann_internal_scan_finish_ex(uint64_t *candA, uint64_t *candB, size_t cand_len, size_t total_segs, size_t nq, uint32_t k,
                                   uint64_t key_offset, uint64_t *d_keys, float *d_scores, uint32_t *d_counts, hipStream_t st,
                                   const uint32_t *idx, int as_dist);
+int leann_internal_keys_finish(uint64_t *candA, uint64_t *candB, size_t cand_len, size_t m, bool sorted, size_t nq, uint32_t k,
+                               uint64_t key_offset, uint64_t *d_keys, float *d_scores, uint32_t *d_counts, hipStream_t st, const uint32_t *idx,
+                               int as_dist);
 // scan.hip: k-way merge of per-shard results (shard.hip, the sharded recompute search)
 int leann_internal_merge_strided(const void *keys, const void *dists, const void *counts, size_t kstride, size_t dstride, size_t cstride,
                                  size_t n_shards, size_t nq, size_t k_in, size_t k_out, int descending, uint64_t *d_out_keys,

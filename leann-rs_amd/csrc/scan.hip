@@ -445,13 +445,19 @@ int leann_internal_topk_chunk(const float *S, size_t rows, size_t nq, uint32_t k
 // idx: keys are indices into a row list (score_mfma_kernel<true>); as_dist: report 1 - score, the backends' distance
 int leann_internal_scan_finish_ex(uint64_t *candA, uint64_t *candB, size_t cand_len, size_t total_segs, size_t nq, uint32_t k, uint64_t key_offset,
                           uint64_t *d_keys, float *d_scores, uint32_t *d_counts, hipStream_t st, const uint32_t *idx, int as_dist) {
-    size_t m = total_segs * k;
+    return leann_internal_keys_finish(candA, candB, cand_len, total_segs * k, true, nq, k, key_offset, d_keys, d_scores, d_counts, st, idx, as_dist);
+}
+// the same over m keys per query (cand_len >= max(m, k), the rest 0xFF); !sorted: the m keys are several ascending runs, not one, so at
+// least one round runs even when m <= k (scan_lists.hip: chunks of 256 keys under a top_k above 256)
+int leann_internal_keys_finish(uint64_t *candA, uint64_t *candB, size_t cand_len, size_t m, bool sorted, size_t nq, uint32_t k, uint64_t key_offset,
+                               uint64_t *d_keys, float *d_scores, uint32_t *d_counts, hipStream_t st, const uint32_t *idx, int as_dist) {
     uint64_t *src = candA, *dst = candB;
-    while (m > k) {
+    while (m > k || !sorted) {
         unsigned segs = (unsigned)((m + SEG - 1) / SEG);
         hipLaunchKernelGGL(topk_keys_kernel, dim3(segs, (unsigned)nq), dim3(256), 0, st, src, (uint32_t)m, (uint32_t)cand_len, k, dst,
                            (uint32_t)cand_len);
         m = (size_t)segs * k;
+        sorted = true;
         std::swap(src, dst);
     }
     hipLaunchKernelGGL(finalize_scan_kernel, dim3((unsigned)nq), dim3(64), 0, st, src, (uint32_t)cand_len, (uint32_t)nq, k, key_offset,
@@ -586,7 +592,8 @@ __device__ __forceinline__ uint32_t allow_word(const uint8_t *__restrict__ allow
     if (n - lo < 32) v &= (1u << (uint32_t)(n - lo)) - 1u;
     return v;
 }
-__global__ void __launch_bounds__(256) allow_count_kernel(const uint8_t *__restrict__ allow, uint64_t n, uint32_t *__restrict__ blk) {
+// (the three steps are device functions: the kernels below run them on one bitmap, the *_batch_kernel forms on one bitmap per blockIdx.y)
+__device__ __forceinline__ void allow_count_step(const uint8_t *__restrict__ allow, uint64_t n, uint32_t *__restrict__ blk) {
     __shared__ uint32_t part[4];
     uint32_t c = __popc(allow_word(allow, n, (uint64_t)blockIdx.x * 256 + threadIdx.x));
     for (int o = 32; o; o >>= 1) c += __shfl_xor(c, o);
@@ -594,7 +601,10 @@ __global__ void __launch_bounds__(256) allow_count_kernel(const uint8_t *__restr
     __syncthreads();
     if (threadIdx.x == 0) blk[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
 }
-__global__ void __launch_bounds__(1024) allow_offsets_kernel(uint32_t *__restrict__ blk, uint32_t nb) { // in place: counts -> exclusive offsets, blk[nb] = total
+__global__ void __launch_bounds__(256) allow_count_kernel(const uint8_t *__restrict__ allow, uint64_t n, uint32_t *__restrict__ blk) {
+    allow_count_step(allow, n, blk);
+}
+__device__ __forceinline__ void allow_offsets_step(uint32_t *__restrict__ blk, uint32_t nb) { // in place: counts -> exclusive offsets, blk[nb] = total
     __shared__ uint32_t sh[1024];
     __shared__ uint32_t carry;
     if (threadIdx.x == 0) carry = 0;
@@ -616,8 +626,9 @@ __global__ void __launch_bounds__(1024) allow_offsets_kernel(uint32_t *__restric
     }
     if (threadIdx.x == 0) blk[nb] = carry;
 }
-__global__ void __launch_bounds__(256) allow_scatter_kernel(const uint8_t *__restrict__ allow, uint64_t n, const uint32_t *__restrict__ blk,
-                                                            uint32_t *__restrict__ out) {
+__global__ void __launch_bounds__(1024) allow_offsets_kernel(uint32_t *__restrict__ blk, uint32_t nb) { allow_offsets_step(blk, nb); }
+__device__ __forceinline__ void allow_scatter_step(const uint8_t *__restrict__ allow, uint64_t n, const uint32_t *__restrict__ blk,
+                                                   uint32_t *__restrict__ out) {
     __shared__ uint32_t sh[256];
     const uint64_t w = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     uint32_t v = allow_word(allow, n, w);
@@ -636,6 +647,60 @@ __global__ void __launch_bounds__(256) allow_scatter_kernel(const uint8_t *__res
         out[dst++] = (uint32_t)(w * 32 + b);
         v &= v - 1;
     }
+}
+__global__ void __launch_bounds__(256) allow_scatter_kernel(const uint8_t *__restrict__ allow, uint64_t n, const uint32_t *__restrict__ blk,
+                                                            uint32_t *__restrict__ out) {
+    allow_scatter_step(allow, n, blk, out);
+}
+// Batched forms: bitmap q = blockIdx.y at allow + q * stride, its block offsets at blk + q * (nb + 1); the offsets kernel also gathers
+// the totals into tot[q], and the scatter writes list q at out + base[q] — one CSR of ascending position lists.
+__global__ void __launch_bounds__(256) allow_count_batch_kernel(const uint8_t *__restrict__ allow, size_t stride, uint64_t n, uint32_t nb,
+                                                                uint32_t *__restrict__ blk) {
+    allow_count_step(allow + blockIdx.y * stride, n, blk + (size_t)blockIdx.y * (nb + 1));
+}
+__global__ void __launch_bounds__(1024) allow_offsets_batch_kernel(uint32_t *__restrict__ blk, uint32_t nb, uint32_t *__restrict__ tot) {
+    uint32_t *mine = blk + (size_t)blockIdx.x * (nb + 1);
+    allow_offsets_step(mine, nb);
+    if (threadIdx.x == 0) tot[blockIdx.x] = mine[nb]; // (written by this thread just above)
+}
+__global__ void __launch_bounds__(256) allow_scatter_batch_kernel(const uint8_t *__restrict__ allow, size_t stride, uint64_t n, uint32_t nb,
+                                                                  const uint32_t *__restrict__ blk, const uint64_t *__restrict__ base,
+                                                                  uint32_t *__restrict__ out) {
+    allow_scatter_step(allow + blockIdx.y * stride, n, blk + (size_t)blockIdx.y * (nb + 1), out + base[blockIdx.y]);
+}
+// nq bitmaps `stride` bytes apart -> *lists, list q = the allowed positions of bitmap q ascending at [off[q], off[q + 1]) (off: nq + 1
+// entries, host).  The counts come to the host once: one stream synchronisation for the batch.  The lease rule is compact_allow's.
+int leann_internal_compact_allow_batch(const uint8_t *d_allow, size_t stride, size_t n, size_t nq, ScratchLease<uint32_t> *lists,
+                                       std::vector<uint64_t> *off, hipStream_t st) {
+    const uint32_t nb = (uint32_t)((n + 8191) / 8192);
+    ScratchLease<uint32_t> blk, tot;
+    ScratchLease<uint64_t> base;
+    std::vector<uint32_t> h_tot(nq);
+    lists->reset();
+    off->assign(nq + 1, 0);
+    if (int e0 = blk.acquire(nq * ((size_t)nb + 1))) return e0;
+    if (int e0 = tot.acquire(nq)) return e0;
+    if (int e0 = base.acquire(nq)) return e0;
+    hipLaunchKernelGGL(allow_count_batch_kernel, dim3(nb, (unsigned)nq), dim3(256), 0, st, d_allow, stride, (uint64_t)n, nb, blk.p);
+    hipLaunchKernelGGL(allow_offsets_batch_kernel, dim3((unsigned)nq), dim3(1024), 0, st, blk.p, nb, tot.p);
+    hipError_t e = hipMemcpyAsync(h_tot.data(), tot, 4 * nq, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    for (size_t q = 0; q < nq; q++) (*off)[q + 1] = (*off)[q] + h_tot[q];
+    const uint64_t total = (*off)[nq];
+    if (e == hipSuccess && total && lists->acquire(total) != LEANN_OK) e = hipErrorOutOfMemory;
+    if (e == hipSuccess && total) {
+        e = hipMemcpyAsync(base, off->data(), 8 * nq, hipMemcpyHostToDevice, st);
+        hipLaunchKernelGGL(allow_scatter_batch_kernel, dim3(nb, (unsigned)nq), dim3(256), 0, st, d_allow, stride, (uint64_t)n, nb, blk.p, base.p, lists->p);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(st); // blk, tot and base go back to the pool on return
+    }
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(st);
+        lists->reset();
+        leann_set_error("HIP error: %s (compact_allow_batch)", hipGetErrorString(e));
+        return LEANN_ERR_DEVICE;
+    }
+    return LEANN_OK;
 }
 int leann_internal_compact_allow(const uint8_t *d_allow, size_t n, ScratchLease<uint32_t> *list, size_t *n_list, hipStream_t st) {
     const uint32_t nb = (uint32_t)((n + 8191) / 8192);
@@ -692,6 +757,22 @@ int leann_internal_filtered_exact(const float *d_rows, size_t n, size_t dims, si
     if (top_k == 0 || top_k > SEG / 2 || n >= (1ull << 32)) {
         leann_set_error("exact filtered search: top_k must be in [1, %d] and the index smaller than 2^32 rows (top_k=%zu n=%zu)", SEG / 2, top_k, n);
         return LEANN_ERR_INVALID;
+    }
+    // One bitmap per query, more than one query: the bitmaps become one CSR of position lists in a single pass (one synchronisation
+    // for the counts instead of one per query) and score_lists_kernel (scan_lists.hip) scans every query's rows in one launch.  The
+    // batch is cut so that even all-ones bitmaps stay within 2^28 list entries (1 GiB) at a time.
+    if (allow_stride && nq > 1 && LEANN_EXACT_LISTS_ROUTING) {
+        const size_t per_batch = std::max<size_t>(1, std::min<size_t>(4096, ((size_t)1 << 28) / std::max<size_t>(n, 1)));
+        for (size_t q0 = 0; q0 < nq; q0 += per_batch) {
+            const size_t nb = std::min(per_batch, nq - q0);
+            ScratchLease<uint32_t> lists; // both calls below leave the stream synchronised
+            std::vector<uint64_t> off;
+            if (int rc = leann_internal_compact_allow_batch(d_allow + q0 * allow_stride, allow_stride, n, nb, &lists, &off, st)) return rc;
+            if (int rc = leann_internal_exact_lists(d_rows, n, dims, ld, nullptr, d_queries + q0 * dims, nb, top_k, off.data(), lists, nullptr,
+                                                    key_offset, d_keys + q0 * top_k, d_dists + q0 * top_k, d_counts + q0, nullptr, st))
+                return rc;
+        }
+        return LEANN_OK;
     }
     const size_t groups = allow_stride ? nq : 1, per = allow_stride ? 1 : nq;
     for (size_t g = 0; g < groups; g++) {
