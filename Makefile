@@ -20,6 +20,8 @@ $(CSRC)/%.o: $(CSRC)/%.hip $(HDRS)
 
 # scan_lists.hip's scores are single fmaf chains: no packed-f32 forms of them
 $(CSRC)/scan_lists.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# scan_i8.hip's distances are wave_dist_rows_i8's fmaf chains: the same
+$(CSRC)/scan_i8.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(CSRC)/libleann_hip.so: $(HIP_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HIP_OBJS)

@@ -747,6 +747,44 @@ int leann_backend_search_refined_batch(const leann_backend *h, const leann_exact
                                        size_t top_k, size_t fetch_k, size_t complexity, const uint8_t *allow, size_t allow_stride,
                                        uint64_t *keys, float *dists, uint32_t *counts, uint32_t *stats /* optional */);
 
+/* ---- exhaustive search on int8 rows (additive; csrc/scan_i8.hip, csrc/i8_rows.h) ---------------------------------------------
+ * A brute-force answer over an int8 handle (LEANN_ROWS_I8), on the integer matrix cores, optionally under ONE allow-bitmap shared by
+ * the batch.  Every existing entry point — the refusals of exact filtered search, filter mode 1 and the exact-lists call on narrow
+ * handles included, filter modes 1 and 2 as they are — behaves exactly as before.
+ *
+ * Definition.  The handle has exponents e_j, codes c_ij and widened rows Xq (row types, above); q is a query.
+ *   1. q'_j = q_j * 2^-e_j in f32: the value the int8 walk stages.
+ *   2. amax = max_j |q'_j| = m * 2^x (frexpf);  E = (m <= 127/128 ? 7 : 6) - x.  E is NOT clamped to +-32.
+ *   3. cq_j = clamp(rne(q'_j * 2^E), -127, 127).  The product is the exact scaling ldexpf(q'_j, E): it cannot overflow (|q'_j| * 2^E <
+ *      128 whatever E is, even where 2^E is no float), and where it underflows the code is 0 either way.
+ *   4. amax == 0: all codes are 0 (E reads 0).  A q'_j that is not finite — q_j is not, or the f32 product of step 1 overflowed; a
+ *      product that underflowed is simply the small or zero f32 value it is — : the query has no codes and its count is 0.
+ *   5. s_i = sum_j cq_j * c_ij in int32: exact in any order (127^2 * 4096 < 2^31).
+ *   6. The candidates are the fetch_k rows with the largest (float)s_i — v_cvt_f32_i32, round to nearest even: exact for row stores of at
+ *      most 1 024 bytes (127^2 * 1024 < 2^24), above that it only merges near-ties — among the rows that are live (not removed) and
+ *      allowed; ties go to the lower position.
+ *   7. Each candidate gets d = 1 - canonical dot(q, Xq_i), bit for bit the distance an int8 walk reports for that key.  The candidates
+ *      are sorted ascending by (d as an ordered float, position); the first top_k come back as position + key_offset, the unused tail as
+ *      UINT64_MAX / +inf, and counts[q] = min(top_k, rows live and allowed).
+ * With fetch_k >= the number of allowed rows the answer is the exact top-k over Xq; otherwise it is approximate in the candidate set
+ * only, never in a returned distance.  An f32 refine needs no new code: call with top_k = fetch_k and hand keys and counts to
+ * leann_rerank_batch_device.
+ *
+ * Limits: 1 <= top_k <= fetch_k <= 1024 (what leann_scan_topk_device allows for top_k).  d_allow: NULL or a device bitmap of
+ * ceil(len / 8) bytes, bits at or behind len ignored.  An empty index: counts 0.  LEANN_ERR_INVALID for a null argument or a k out of
+ * range; LEANN_ERR_UNSUPPORTED, on the host before any device work, the message naming the way out: an f32 handle (use leann_backend_
+ * search_filtered_exact_batch or leann_scan_topk_device), a bf16 handle (its screen would have to round the query: another definition),
+ * a recompute-on handle, a composite handle (search the shards, merge with leann_merge_topk_device).  The call takes library scratch
+ * and returns with `stream` SYNCHRONISED; it cannot be captured into a HIP graph.  _search_flat_batch is the host-pointer twin.
+ * leann_quantize_query_i8: steps 1-4 on the host, no device — codes_out [d] in ELEMENT order, *E_out = E, or INT32_MIN with all-zero
+ * codes for a query of step 4's second kind: the reference the device quantiser is held to. */
+int leann_backend_search_flat_batch_device(const leann_backend *h, const float *d_queries, size_t nq, size_t top_k, size_t fetch_k,
+                                           const uint8_t *d_allow /* shared bitmap or NULL */, uint64_t *d_keys, float *d_dists,
+                                           uint32_t *d_counts, void *stream);
+int leann_backend_search_flat_batch(const leann_backend *h, const float *queries, size_t nq, size_t top_k, size_t fetch_k,
+                                    const uint8_t *allow /* shared bitmap or NULL */, uint64_t *keys, float *dists, uint32_t *counts);
+int leann_quantize_query_i8(const float *q, size_t d, const int8_t *exps, int8_t *codes_out, int32_t *E_out);
+
 /* ---- sharded indexes (the reference has no counterpart: IndexSearcher owns one Box<dyn BackendSearcher>,
  * src/index/searcher.rs:68) --------------------------------------------------------------------------------------------------
  * One process, G devices: the composite handle leann_backend_open returns for a device list, or built here from rows / handles.

@@ -57,6 +57,20 @@ def quantize_i8(x):
     return exps, codes
 
 
+def quantize_query_i8(q, exps):
+    """one query [d] and an int8 index's column exponents [d] -> (codes int8 [d] in element order, E): the query codes of the flat
+    search (include/leann_backend.h "exhaustive search on int8 rows"), the library's own reference, on the host; E is
+    -2**31 and the codes are zero for a query whose scaled elements are not all finite"""
+    q = np.ascontiguousarray(q, np.float32).reshape(-1)
+    exps = np.ascontiguousarray(exps, np.int8).reshape(-1)
+    if q.shape != exps.shape:
+        raise LeannError(1, "quantize_query_i8: the query and the exponents differ in length")
+    codes, E = np.zeros(q.shape[0], np.int8), C.c_int32(0)
+    i8p = C.POINTER(C.c_int8)
+    N.check(N.lib().leann_quantize_query_i8(_p(q, f32p), q.shape[0], exps.ctypes.data_as(i8p), codes.ctypes.data_as(i8p), C.byref(E)))
+    return codes, E.value
+
+
 def _p(a, t):
     return a.ctypes.data_as(t) if a is not None else None
 
@@ -305,6 +319,29 @@ class BackendSearcher:
                                      d_counts, d_stats=None, stream=None):
         N.check(N.lib().leann_backend_search_filtered_batch_device(self._h, d_queries, nq, top_k, complexity, d_allow,
                                                                    allow_stride, d_keys, d_dists, d_counts, d_stats, stream))
+
+    def search_flat_batch(self, queries, top_k, fetch_k, allow=None):
+        """int8 handles: every live and allowed row screened by the int32 dot product of query codes and row codes, the fetch_k best
+        scored with the walk's distance, the best top_k returned.  allow: None or ONE bitmap [ceil(len/8)] for the batch."""
+        Q = np.ascontiguousarray(queries, np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dims():
+            raise LeannError(1, f"queries must be [nq x {self.dims()}]")
+        if allow is not None:
+            allow = np.ascontiguousarray(allow, np.uint8)
+            if allow.ndim != 1 or allow.shape[0] < (self.len() + 7) // 8:
+                raise LeannError(1, "allow-bitmap must be one bitmap of ceil(len / 8) bytes")
+        nq = Q.shape[0]
+        keys = np.full((nq, max(top_k, 1)), np.iinfo(np.uint64).max, np.uint64)
+        dists = np.full((nq, max(top_k, 1)), np.inf, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        N.check(N.lib().leann_backend_search_flat_batch(self._h, _p(Q, f32p), nq, top_k, fetch_k, _p(allow, u8p), _p(keys, u64p),
+                                                        _p(dists, f32p), _p(counts, u32p)))
+        return keys, dists, counts
+
+    def search_flat_batch_device(self, d_queries, nq, top_k, fetch_k, d_keys, d_dists, d_counts, d_allow=None, stream=None):
+        """the same with device pointers (ints); synchronises `stream` before it returns"""
+        N.check(N.lib().leann_backend_search_flat_batch_device(self._h, d_queries, nq, top_k, fetch_k, d_allow, d_keys, d_dists,
+                                                               d_counts, stream))
 
     def search_refined_batch(self, queries, top_k, fetch_k, complexity, rows, allow=None):
         """the walk at top_k = fetch_k, then its candidates scored again on the exact rows of an ExactRows: the best top_k by the

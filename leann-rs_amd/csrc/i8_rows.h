@@ -32,6 +32,25 @@ LEANN_I8_FN int8_t i8_code(float x, float scale) {
     return (int8_t)(r > 127.f ? 127.f : r < -127.f ? -127.f : r);
 }
 
+// ---- the flat search's query codes (include/leann_backend.h "exhaustive search on int8 rows"; scan_i8.hip) ---------------------------
+// The query, scaled as the walk stages it (q'_j = q_j 2^-e_j in f32), gets ONE power-of-two scale of its own: amax = max_j |q'_j| =
+// m 2^x (frexpf), E = (m <= 127 / 128 ? 7 : 6) - x — the rows' rule, but never clamped, q' being arbitrarily far from unit scale —
+// and cq_j = clamp(rne(q'_j 2^E), -127, 127).  The product is taken as ldexpf(q'_j, E), an exact scaling: |q'_j| 2^E < 128 cannot
+// overflow whatever E is (2^E itself need not be a float), and a result below the normal range rounds to a code of 0 either way.
+// A query with a q'_j that is not finite (the f32 product q_j 2^-e_j overflowed, or q_j was not finite) has no codes.
+#define LEANN_I8_QUERY_NONFINITE INT32_MIN // what E reads for such a query; its codes are all zero
+LEANN_I8_FN bool i8_query_finite(float amax) { return amax <= 3.402823466e38f; } // false for NaN too
+LEANN_I8_FN int i8_query_exponent(float amax) { // amax finite, >= 0; 0 for the all-zero query (every code is 0 whatever E is)
+    if (!(amax > 0.f)) return 0;
+    int x;
+    const float m = frexpf(amax, &x);
+    return (m <= 0.9921875f ? 7 : 6) - x;
+}
+LEANN_I8_FN int8_t i8_query_code(float qs, int E) {
+    const float r = rintf(ldexpf(qs, E));
+    return (int8_t)(r > 127.f ? 127.f : r < -127.f ? -127.f : r);
+}
+
 // The store's pitch: dims rounded up to 128 — a row is whole, aligned 128-B lines.
 LEANN_I8_FN uint32_t i8_store_ld(uint32_t d) { return (d + 127u) & ~127u; }
 // Where element j of a row sits in its store row of ldb bytes.  Whole 1 024-element blocks are interleaved so that lane l (elements
