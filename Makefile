@@ -22,6 +22,8 @@ $(CSRC)/%.o: $(CSRC)/%.hip $(HDRS)
 $(CSRC)/scan_lists.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 # scan_i8.hip's distances are wave_dist_rows_i8's fmaf chains: the same
 $(CSRC)/scan_i8.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# scan_lists_i8.hip's scores are integer sums; its one f32 step is a cast, and nothing there is to be packed into f32 pairs either
+$(CSRC)/scan_lists_i8.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(CSRC)/libleann_hip.so: $(HIP_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HIP_OBJS)

@@ -92,7 +92,8 @@ int leann_backend_search_filtered_batch(const leann_backend *h, const float *que
  * list of allowed positions and only those rows are scanned (f32 matrix cores, one k-ordered fmaf chain per pair, like
  * leann_scan_topk_device): top_k best allowed positions by distance 1 - <x, q>, ties to the lower position; cost is
  * proportional to the number of allowed rows, independent of the graph.  The host-side planner
- * (host/leann_host.hpp IndexSearcher) switches to it below 5 % allowed (single queries; ~1.5 % is the crossover in 16k-query batches).  Needs stored vectors. */
+ * (host/leann_host.hpp IndexSearcher) switches to it below 5 % allowed (single queries; ~1.5 % is the crossover in 16k-query batches).  Needs stored vectors.
+ * (An int8 handle is refused here; its way out is leann_backend_search_flat_filtered_batch, below.) */
 int leann_backend_search_filtered_exact_batch(const leann_backend *h, const float *queries, size_t nq,
                                               size_t top_k, const uint8_t *allow, size_t allow_stride,
                                               uint64_t *keys, float *dists, uint32_t *counts);
@@ -340,6 +341,7 @@ int leann_backend_search_filtered_exact_batch_device(const leann_backend *h, con
  * LEANN_ERR_INVALID, before any device work and naming the argument: a null argument, top_k outside [1, 1024], list_off[0] != 0 or
  * non-monotone offsets, q_list[i] >= n_lists, q_list == NULL with n_lists != nq.  LEANN_ERR_UNSUPPORTED: a recompute-on, bf16 or int8
  * handle (no f32 rows to scan), and a composite handle (lists are local to one handle: pass bitmaps, which are sliced per shard).
+ * (An int8 handle's way out is leann_backend_search_flat_lists_batch, below.)
  * The _device form uses library scratch and synchronises `stream` before it returns; it cannot be captured into a HIP graph. */
 int leann_backend_search_exact_lists_batch_device(const leann_backend *h, const float *d_queries, size_t nq, size_t top_k,
                                                   const uint64_t *list_off, const uint32_t *d_lists, size_t n_lists,
@@ -659,7 +661,8 @@ int leann_meta_eval_batch_device(const leann_meta *m, const leann_meta_node *nod
 /* nq queries, query i under filter i: evaluate, then search.  Defined by delegation: query i's keys, f32 distance bits, count and
  * four stats are what leann_backend_search_filtered_batch_device (mode 0, the walk) or leann_backend_search_filtered_exact_batch_device
  * (mode 1; d_stats is not written) return for bitmap i = filter i evaluated by leann_meta_eval_device — on a composite, narrow-row or
- * recompute-on handle too, their refusals (LEANN_ERR_UNSUPPORTED for mode 1 on narrow rows and recompute-on handles) included.  The
+ * recompute-on handle too, their refusals (LEANN_ERR_UNSUPPORTED for mode 1 on narrow rows and recompute-on handles) included (an int8
+ * handle's way out: leann_meta_eval_batch_device, then leann_backend_search_flat_filtered_batch_device over its bitmaps).  The
  * delegated calls AND the index's live mask themselves.  d_n_allowed [nq]: optional, the rows filter i allows (before the live
  * mask): what a caller needs to split a batch between the modes itself.  The bitmaps live in library scratch, at most 1 GiB at a
  * time: the batch runs in chunks of max(1, 1 GiB / stride) queries, stride = ceil(n / 8) rounded up to 16, each chunk planned,
@@ -749,7 +752,7 @@ int leann_backend_search_refined_batch(const leann_backend *h, const leann_exact
 
 /* ---- exhaustive search on int8 rows (additive; csrc/scan_i8.hip, csrc/i8_rows.h) ---------------------------------------------
  * A brute-force answer over an int8 handle (LEANN_ROWS_I8), on the integer matrix cores, optionally under ONE allow-bitmap shared by
- * the batch.  Every existing entry point — the refusals of exact filtered search, filter mode 1 and the exact-lists call on narrow
+ * the batch (one list or bitmap per query: the next section).  Every existing entry point — the refusals of exact filtered search, filter mode 1 and the exact-lists call on narrow
  * handles included, filter modes 1 and 2 as they are — behaves exactly as before.
  *
  * Definition.  The handle has exponents e_j, codes c_ij and widened rows Xq (row types, above); q is a query.
@@ -784,6 +787,49 @@ int leann_backend_search_flat_batch_device(const leann_backend *h, const float *
 int leann_backend_search_flat_batch(const leann_backend *h, const float *queries, size_t nq, size_t top_k, size_t fetch_k,
                                     const uint8_t *allow /* shared bitmap or NULL */, uint64_t *keys, float *dists, uint32_t *counts);
 int leann_quantize_query_i8(const float *q, size_t d, const int8_t *exps, int8_t *codes_out, int32_t *E_out);
+
+/* ---- exhaustive search on int8 rows, per query (additive; csrc/scan_lists_i8.hip) ---------------------------------------
+ * The flat search above with query i answered over ITS OWN rows: a position list (a tenant's ids, an ACL, a posting list) or its own
+ * allow-bitmap — the multi-tenant form leann_backend_search_exact_lists_batch and the strided exact filtered search give an f32 handle,
+ * which both refuse an int8 one.  One launch scores every query's rows, on the vector ALU's packed 8-bit dot product.
+ *
+ * Definition.  Steps 1-5 and 7 of "exhaustive search on int8 rows" above, unchanged: the query codes cq against the index's column
+ * exponents, s_i = sum_j cq_j * c_ij in int32, count 0 for a query whose q' is not finite, d = 1 - canonical dot(q, Xq_i) — the int8
+ * walk's distance —, the answer ascending by (d, position), keys = position + key_offset, the tail UINT64_MAX / +inf.  Step 6 per list:
+ *   6'. The candidates of query i are the fetch_k entries of its list with the largest (float)s, ties to the lower position, among the
+ *       entries that are below leann_backend_len(h) and live.
+ * Lists: those of leann_backend_search_exact_lists_batch, word for word.  list_off [n_lists + 1] (HOST, from 0, monotone; a list holds
+ * fewer than 2^31 entries) cuts d_lists (device) into lists of positions local to h.  Query i takes list q_list[i] (HOST, [nq]);
+ * q_list == NULL: n_lists == nq and query i takes list i.  A list need not be sorted.  A position listed twice is a candidate twice and
+ * may be returned twice.  A position >= leann_backend_len(h) is skipped and counted in d_skipped[i] (optional, [nq]); a removed
+ * position is skipped and not counted; every entry is range- and live-checked before it becomes an address.  An empty list gives
+ * count 0.  counts[i] = min(top_k, valid entries).  With fetch_k >= the valid entries the answer is the exact top-k over Xq of the
+ * listed rows.  Limits: 1 <= top_k <= fetch_k <= 1024.
+ * Two facts follow.  For a list without duplicates or out-of-range entries, query i's answer is, bit for bit, what
+ * leann_backend_search_flat_batch returns for that one query under the bitmap of the list.  And the per-query-bitmap call equals the
+ * lists call over the set bits of each bitmap:
+ * leann_backend_search_flat_filtered_batch[_device]: d_allow holds nq bitmaps allow_stride bytes apart (allow_stride >= ceil(len / 8),
+ * bits at or behind len ignored); they are ANDed with the live mask, compacted into one CSR of ascending lists in one pass and searched
+ * by the lists kernel.  allow_stride == 0 or d_allow == NULL: exactly leann_backend_search_flat_batch[_device] (one shared bitmap, or
+ * none).  Per-query metadata filters need no call of their own: leann_meta_eval_batch_device writes the nq bitmaps, this call searches
+ * them.
+ * LEANN_ERR_INVALID, on the host before any device work and naming the argument: a null argument, a k out of range, list_off[0] != 0
+ * or non-monotone offsets, q_list[i] >= n_lists, q_list == NULL with n_lists != nq, an allow_stride below ceil(len / 8) — the handle
+ * is not read before the first four.  LEANN_ERR_UNSUPPORTED, the message naming the way out: f32, bf16, recompute-on and composite
+ * handles, as the flat call refuses them.  The calls take library scratch, return with `stream` SYNCHRONISED and cannot be captured
+ * into a HIP graph.  Out of scope: bf16 handles, composite handles. */
+int leann_backend_search_flat_lists_batch_device(const leann_backend *h, const float *d_queries, size_t nq, size_t top_k, size_t fetch_k,
+                                                 const uint64_t *list_off, const uint32_t *d_lists, size_t n_lists, const uint32_t *q_list,
+                                                 uint64_t *d_keys, float *d_dists, uint32_t *d_counts, uint32_t *d_skipped, void *stream);
+/* ... queries, lists and results on the host */
+int leann_backend_search_flat_lists_batch(const leann_backend *h, const float *queries, size_t nq, size_t top_k, size_t fetch_k,
+                                          const uint64_t *list_off, const uint32_t *lists, size_t n_lists, const uint32_t *q_list,
+                                          uint64_t *keys, float *dists, uint32_t *counts, uint32_t *skipped);
+int leann_backend_search_flat_filtered_batch_device(const leann_backend *h, const float *d_queries, size_t nq, size_t top_k, size_t fetch_k,
+                                                    const uint8_t *d_allow, size_t allow_stride, uint64_t *d_keys, float *d_dists,
+                                                    uint32_t *d_counts, void *stream);
+int leann_backend_search_flat_filtered_batch(const leann_backend *h, const float *queries, size_t nq, size_t top_k, size_t fetch_k,
+                                             const uint8_t *allow, size_t allow_stride, uint64_t *keys, float *dists, uint32_t *counts);
 
 /* ---- sharded indexes (the reference has no counterpart: IndexSearcher owns one Box<dyn BackendSearcher>,
  * src/index/searcher.rs:68) --------------------------------------------------------------------------------------------------

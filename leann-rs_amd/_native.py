@@ -147,6 +147,12 @@ SIGNATURES = {
                                                      u64p, f32p, u32p, u32p]),
     "leann_backend_search_flat_batch_device": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp]),
     "leann_backend_search_flat_batch": (C.c_int, [vp, f32p, C.c_size_t, C.c_size_t, C.c_size_t, u8p, u64p, f32p, u32p]),
+    "leann_backend_search_flat_lists_batch_device": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, u64p, vp, C.c_size_t, u32p, vp, vp, vp,
+                                                               vp, vp]),
+    "leann_backend_search_flat_lists_batch": (C.c_int, [vp, f32p, C.c_size_t, C.c_size_t, C.c_size_t, u64p, u32p, C.c_size_t, u32p, u64p, f32p,
+                                                        u32p, u32p]),
+    "leann_backend_search_flat_filtered_batch_device": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp]),
+    "leann_backend_search_flat_filtered_batch": (C.c_int, [vp, f32p, C.c_size_t, C.c_size_t, C.c_size_t, u8p, C.c_size_t, u64p, f32p, u32p]),
     "leann_quantize_query_i8": (C.c_int, [f32p, C.c_size_t, C.POINTER(C.c_int8), C.POINTER(C.c_int8), C.POINTER(C.c_int32)]),
     "leann_synth_rows_device": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                          C.c_float, C.c_uint32, C.c_uint64, C.c_uint64, vp, vp]),

@@ -343,6 +343,68 @@ class BackendSearcher:
         N.check(N.lib().leann_backend_search_flat_batch_device(self._h, d_queries, nq, top_k, fetch_k, d_allow, d_keys, d_dists,
                                                                d_counts, stream))
 
+    def search_flat_lists_batch(self, queries, top_k, fetch_k, lists, q_list=None):
+        """int8 handles: search_flat_batch with query i screened over the positions of lists[q_list[i]] (q_list None: lists[i]) only;
+        lists as in search_exact_lists_batch: uint32 position arrays, unsorted and with duplicates if the caller likes.  Returns keys,
+        dists, counts and, per query, how many listed positions lay beyond the index."""
+        Q = np.ascontiguousarray(queries, np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dims():
+            raise LeannError(1, f"queries must be [nq x {self.dims()}]")
+        parts = [np.ascontiguousarray(l, np.uint32).reshape(-1) for l in lists]
+        off = np.zeros(len(parts) + 1, np.uint64)
+        off[1:] = np.cumsum([p.shape[0] for p in parts], dtype=np.uint64)
+        flat = np.concatenate(parts) if parts else np.zeros(0, np.uint32)
+        flat = np.ascontiguousarray(flat if flat.size else np.zeros(1, np.uint32), np.uint32)
+        ql = None if q_list is None else np.ascontiguousarray(q_list, np.uint32)
+        if ql is not None and ql.shape != (Q.shape[0],):
+            raise LeannError(1, "q_list must hold one list number per query")
+        nq = Q.shape[0]
+        keys = np.full((nq, max(top_k, 1)), np.iinfo(np.uint64).max, np.uint64)
+        dists = np.full((nq, max(top_k, 1)), np.inf, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        skipped = np.zeros(nq, np.uint32)
+        N.check(N.lib().leann_backend_search_flat_lists_batch(self._h, _p(Q, f32p), nq, top_k, fetch_k, _p(off, u64p), _p(flat, u32p),
+                                                              len(parts), None if ql is None else _p(ql, u32p), _p(keys, u64p),
+                                                              _p(dists, f32p), _p(counts, u32p), _p(skipped, u32p)))
+        return keys, dists, counts, skipped
+
+    def search_flat_lists_batch_device(self, d_queries, nq, top_k, fetch_k, list_off, d_lists, n_lists, q_list, d_keys, d_dists, d_counts,
+                                       d_skipped=None, stream=None):
+        """list_off (uint64 [n_lists + 1]) and q_list (uint32 [nq] or None) are host arrays, everything else device pointers;
+        synchronises `stream` before it returns"""
+        off = np.ascontiguousarray(list_off, np.uint64)
+        ql = None if q_list is None else np.ascontiguousarray(q_list, np.uint32)
+        N.check(N.lib().leann_backend_search_flat_lists_batch_device(self._h, d_queries, nq, top_k, fetch_k, _p(off, u64p), d_lists, n_lists,
+                                                                     None if ql is None else _p(ql, u32p), d_keys, d_dists, d_counts,
+                                                                     d_skipped, stream))
+
+    def search_flat_filtered_batch(self, queries, top_k, fetch_k, allow):
+        """int8 handles: search_flat_batch with query i under its own bitmap allow[i] ([nq x stride], stride >= ceil(len / 8)); a
+        one-dimensional allow is ONE bitmap for the batch, i.e. search_flat_batch.  Per-query metadata filters need no call of their
+        own: MetaColumns.eval_batch gives the nq bitmaps for this call, eval_batch_device leaves them on the device for
+        search_flat_filtered_batch_device."""
+        Q = np.ascontiguousarray(queries, np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dims():
+            raise LeannError(1, f"queries must be [nq x {self.dims()}]")
+        allow = np.ascontiguousarray(allow, np.uint8)
+        stride = 0 if allow.ndim == 1 else allow.shape[1]
+        if allow.shape[-1] < (self.len() + 7) // 8 or (allow.ndim == 2 and allow.shape[0] != Q.shape[0]):
+            raise LeannError(1, "allow-bitmap shape does not match the index / the batch")
+        nq = Q.shape[0]
+        keys = np.full((nq, max(top_k, 1)), np.iinfo(np.uint64).max, np.uint64)
+        dists = np.full((nq, max(top_k, 1)), np.inf, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        N.check(N.lib().leann_backend_search_flat_filtered_batch(self._h, _p(Q, f32p), nq, top_k, fetch_k, _p(allow, u8p), stride,
+                                                                 _p(keys, u64p), _p(dists, f32p), _p(counts, u32p)))
+        return keys, dists, counts
+
+    def search_flat_filtered_batch_device(self, d_queries, nq, top_k, fetch_k, d_allow, allow_stride, d_keys, d_dists, d_counts,
+                                          stream=None):
+        """the same with device pointers (ints); allow_stride: bytes from one query's bitmap to the next, 0 for one shared bitmap;
+        synchronises `stream` before it returns"""
+        N.check(N.lib().leann_backend_search_flat_filtered_batch_device(self._h, d_queries, nq, top_k, fetch_k, d_allow, allow_stride,
+                                                                        d_keys, d_dists, d_counts, stream))
+
     def search_refined_batch(self, queries, top_k, fetch_k, complexity, rows, allow=None):
         """the walk at top_k = fetch_k, then its candidates scored again on the exact rows of an ExactRows: the best top_k by the
         f32 distance.  allow: None, or as in search_filtered_batch.  Returns keys, dists, counts."""

@@ -298,6 +298,24 @@ int leann_internal_compact_allow_batch(const uint8_t *d_allow, size_t stride, si
 int leann_internal_exact_lists(const float *d_rows, size_t n, size_t dims, size_t ld, const uint8_t *d_live, const float *d_queries, size_t nq,
                                size_t top_k, const uint64_t *list_off, const uint32_t *d_lists, const uint32_t *q_list, uint64_t key_offset,
                                uint64_t *d_keys, float *d_dists, uint32_t *d_counts, uint32_t *d_skipped, hipStream_t st);
+// scan_lists.hip: what every lists call asks of its HOST arrays — list_off[0] == 0, monotone offsets, lists shorter than 2^31 entries,
+// q_list[i] < n_lists, q_list == NULL only with n_lists == nq — LEANN_ERR_INVALID and a message that starts with `who` otherwise
+int leann_internal_lists_check_offsets(const char *who, size_t nq, const uint64_t *list_off, const void *lists, size_t n_lists, const uint32_t *q_list);
+// scan_i8.hip: the two ends of a search that screens int8 rows by the int32 dot product of codes (the flat search there, the lists
+// search of scan_lists_i8.hip).  _quantize: checks the handle's store, then quantize_queries_i8_kernel — Qc [nq rounded up to
+// leann_internal_i8_query_rows x g.row_bytes] in store order, padding zero; bad [nq]: 1 for a query without codes.  _rescore:
+// rescore_i8_kernel<T> — cand [nq x fetch_k] positions and cand_cnt [nq] -> the answer, count 0 for a bad query.  Both stream-ordered.
+inline size_t leann_internal_i8_query_rows(size_t nq) { return (nq + 63) / 64 * 64; }
+int leann_internal_quantize_queries_i8(const leann_backend *h, const float *d_queries, size_t nq, int8_t *Qc, uint32_t *bad, hipStream_t st);
+int leann_internal_rescore_i8(const leann_backend *h, const float *d_queries, size_t nq, const uint64_t *cand, const uint32_t *cand_cnt,
+                              const uint32_t *bad, uint32_t fetch_k, uint32_t top_k, uint64_t *d_keys, float *d_dists, uint32_t *d_counts,
+                              hipStream_t st);
+// scan_i8.hip: what every search that screens int8 rows refuses, the message starting with `who`.  _args: null arguments and k outside
+// 1 <= top_k <= fetch_k <= 1024, LEANN_ERR_INVALID, the handle not read; _handle: composite, recompute-on, f32 and bf16 handles,
+// LEANN_ERR_UNSUPPORTED, the message naming the way out.
+int leann_internal_flat_check_args(const char *who, const leann_backend *h, const void *queries, size_t nq, size_t top_k, size_t fetch_k,
+                                   const void *keys, const void *dists, const void *counts);
+int leann_internal_flat_check_handle(const char *who, const leann_backend *h, size_t nq);
 // Whether leann_internal_filtered_exact sends per-query bitmaps (allow_stride != 0, nq > 1) through the two functions above instead of
 // compacting and scanning query by query.  The measurement that decides it: profiles/exact_lists.md, shape a.
 constexpr bool LEANN_EXACT_LISTS_ROUTING = true;

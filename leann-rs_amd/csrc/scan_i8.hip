@@ -257,6 +257,34 @@ static RescoreKernel rescore_kernel_of(int T) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
+// The two ends of a screen over int8 rows (internal.h): the flat search below and the lists search (scan_lists_i8.hip) launch them.
+static_assert(FLAT_BQ == 64, "leann_internal_i8_query_rows pads the query codes to the score tile");
+int leann_internal_quantize_queries_i8(const leann_backend *h, const float *d_queries, size_t nq, int8_t *Qc, uint32_t *bad, hipStream_t st) {
+    const GraphView &g = h->g;
+    const uint32_t ldb = g.row_bytes;
+    if (!g.X || !g.norms || (ldb & 127u) || ldb < g.ld || !rescore_kernel_of(search_width_T((g.ld + 255) / 256))) {
+        leann_set_error("int8 rows: the handle's row store or its column scales are missing or malformed (pitch %u B for %u elements)", ldb, g.ld);
+        return LEANN_ERR_INVALID;
+    }
+    hipLaunchKernelGGL(quantize_queries_i8_kernel, dim3((unsigned)leann_internal_i8_query_rows(nq)), dim3(64), 0, st, d_queries, (uint32_t)nq, g.d,
+                       g.norms, ldb, Qc, bad);
+    HIP_CHECK_RET(hipGetLastError());
+    return LEANN_OK;
+}
+int leann_internal_rescore_i8(const leann_backend *h, const float *d_queries, size_t nq, const uint64_t *cand, const uint32_t *cand_cnt,
+                              const uint32_t *bad, uint32_t fetch_k, uint32_t top_k, uint64_t *d_keys, float *d_dists, uint32_t *d_counts,
+                              hipStream_t st) {
+    const GraphView &g = h->g;
+    const RescoreKernel rescore = rescore_kernel_of(search_width_T((g.ld + 255) / 256));
+    if (!rescore) { leann_set_error("int8 rows: no rescore kernel for rows of %u elements", g.ld); return LEANN_ERR_INVALID; }
+    RescoreArgs a{};
+    a.X = reinterpret_cast<const int8_t *>(g.X); a.n = g.n; a.ldb = g.row_bytes; a.d = g.d; a.ld = g.ld; a.scales = g.norms; a.Q = d_queries;
+    a.cand = cand; a.cand_cnt = cand_cnt; a.bad = bad; a.fetch_k = fetch_k; a.top_k = top_k; a.key_offset = h->key_offset;
+    a.out_keys = d_keys; a.out_dists = d_dists; a.out_counts = d_counts;
+    hipLaunchKernelGGL(rescore, dim3((unsigned)nq), dim3(256), 0, st, a);
+    HIP_CHECK_RET(hipGetLastError());
+    return LEANN_OK;
+}
 // The screen follows scan_topk_impl (scan.hip) with k = fetch_k: plan, scratch, begin, per chunk { score, select }, finish, once more on
 // the slab schedule if a candidate list overflowed.  Returns with `st` synchronised.
 static int flat_i8_run(leann_backend *h, const float *d_queries, size_t nq, size_t top_k, size_t fetch_k, const uint8_t *d_allow,
@@ -264,12 +292,7 @@ static int flat_i8_run(leann_backend *h, const float *d_queries, size_t nq, size
     const GraphView &g = h->g;
     const int8_t *X = reinterpret_cast<const int8_t *>(g.X);
     const uint32_t ldb = g.row_bytes, k = (uint32_t)fetch_k;
-    const RescoreKernel rescore = rescore_kernel_of(search_width_T((g.ld + 255) / 256));
-    if (!X || !g.norms || (ldb & 127u) || ldb < g.ld || !rescore) {
-        leann_set_error("int8 rows: the handle's row store or its column scales are missing or malformed (pitch %u B for %u elements)", ldb, g.ld);
-        return LEANN_ERR_INVALID;
-    }
-    const size_t nq_pad = (nq + FLAT_BQ - 1) / FLAT_BQ * FLAT_BQ;
+    const size_t nq_pad = leann_internal_i8_query_rows(nq);
     // every return, early ones included, gives the scratch back — after the stream is idle (SyncFirst is declared last, so it runs first)
     ScratchLease<int8_t> Qc;
     ScratchLease<uint32_t> bad, candC, list;
@@ -284,8 +307,7 @@ static int flat_i8_run(leann_backend *h, const float *d_queries, size_t nq, size
     if (int e = candK.acquire(nq * k)) return e;
     if (int e = candS.acquire(nq * k)) return e;
     if (int e = candC.acquire(nq)) return e;
-    hipLaunchKernelGGL(quantize_queries_i8_kernel, dim3((unsigned)nq_pad), dim3(64), 0, st, d_queries, (uint32_t)nq, g.d, g.norms, ldb, Qc.p, bad.p);
-    HIP_CHECK_RET(hipGetLastError());
+    if (int rc = leann_internal_quantize_queries_i8(h, d_queries, nq, Qc, bad, st)) return rc;
     // the rows of the screen: all of them, or the allowed AND live ones as an ascending list
     const uint8_t *allow = nullptr;
     size_t allow_stride = 0, m = g.n;
@@ -321,20 +343,15 @@ static int flat_i8_run(leann_backend *h, const float *d_queries, size_t nq, size
         if (rc != LEANN_OK) return rc;
         if (!overflowed) break;
     }
-    RescoreArgs a{};
-    a.X = X; a.n = g.n; a.ldb = ldb; a.d = g.d; a.ld = g.ld; a.scales = g.norms; a.Q = d_queries;
-    a.cand = candK; a.cand_cnt = candC; a.bad = bad; a.fetch_k = k; a.top_k = (uint32_t)top_k; a.key_offset = h->key_offset;
-    a.out_keys = d_keys; a.out_dists = d_dists; a.out_counts = d_counts;
-    hipLaunchKernelGGL(rescore, dim3((unsigned)nq), dim3(256), 0, st, a);
-    HIP_CHECK_RET(hipGetLastError());
+    if (int rc = leann_internal_rescore_i8(h, d_queries, nq, candK, candC, bad, k, (uint32_t)top_k, d_keys, d_dists, d_counts, st)) return rc;
     HIP_CHECK_RET(hipStreamSynchronize(st));
     return LEANN_OK;
 }
 
-// what both entry points refuse, on the host, before any device work: null arguments, then k out of range (the handle is not read
-// before these), then the handles the screen is not defined for
-static int flat_check(const char *who, const leann_backend *h, const void *queries, size_t nq, size_t top_k, size_t fetch_k, const void *keys,
-                      const void *dists, const void *counts) {
+// what the entry points refuse, on the host, before any device work (internal.h; the lists search of scan_lists_i8.hip refuses the
+// same): null arguments, then k out of range (the handle is not read before these), then the handles the screen is not defined for
+int leann_internal_flat_check_args(const char *who, const leann_backend *h, const void *queries, size_t nq, size_t top_k, size_t fetch_k,
+                                   const void *keys, const void *dists, const void *counts) {
     if (!h || (nq && (!queries || !keys || !dists || !counts))) {
         leann_set_error("%s: null %s", who, !h ? "handle" : !queries ? "queries" : !keys ? "keys" : !dists ? "dists" : "counts");
         return LEANN_ERR_INVALID;
@@ -342,6 +359,9 @@ static int flat_check(const char *who, const leann_backend *h, const void *queri
     if (top_k == 0) { leann_set_error("%s: top_k = 0", who); return LEANN_ERR_INVALID; }
     if (fetch_k > FLAT_MAX_K) { leann_set_error("%s: fetch_k = %zu is above %zu", who, fetch_k, FLAT_MAX_K); return LEANN_ERR_INVALID; }
     if (top_k > fetch_k) { leann_set_error("%s: top_k = %zu is above fetch_k = %zu", who, top_k, fetch_k); return LEANN_ERR_INVALID; }
+    return LEANN_OK;
+}
+int leann_internal_flat_check_handle(const char *who, const leann_backend *h, size_t nq) {
     if (h->sharded) {
         leann_set_error("%s is not available on a composite handle (search each shard with leann_backend_shard(h, g) and merge with leann_merge_topk_device)", who);
         return LEANN_ERR_UNSUPPORTED;
@@ -365,6 +385,11 @@ static int flat_check(const char *who, const leann_backend *h, const void *queri
         return LEANN_ERR_INVALID;
     }
     return LEANN_OK;
+}
+static int flat_check(const char *who, const leann_backend *h, const void *queries, size_t nq, size_t top_k, size_t fetch_k, const void *keys,
+                      const void *dists, const void *counts) {
+    if (int rc = leann_internal_flat_check_args(who, h, queries, nq, top_k, fetch_k, keys, dists, counts)) return rc;
+    return leann_internal_flat_check_handle(who, h, nq);
 }
 
 extern "C" int leann_backend_search_flat_batch_device(const leann_backend *hc, const float *d_queries, size_t nq, size_t top_k, size_t fetch_k,

@@ -36,19 +36,9 @@
 #include "common.cuh"
 #include "../../include/leann_backend.h"
 #include "internal.h"
+#include "lists_plan.h"
 #include <algorithm>
-#include <numeric>
 #include <vector>
-
-constexpr int LISTS_QT = 8;        // queries of one tile of a shared list
-constexpr uint32_t LISTS_ROWS = 256; // listed rows of one chunk
-struct ListUnit {
-    uint64_t off;  // first entry of the chunk in d_lists
-    uint32_t cnt;  // entries of the chunk, 1 .. 256
-    uint32_t chunk; // chunk number within its list: the slot in cand
-    uint32_t q0;   // first query of the tile in qord
-    uint32_t nqt;  // queries of the tile, 1 .. QT
-};
 
 template <int QT, bool FAST>
 __global__ void __launch_bounds__(256) score_lists_kernel(const float *__restrict__ X, uint64_t n, uint32_t d, uint32_t ld,
@@ -167,29 +157,12 @@ static int lists_slice(const float *X, size_t n, size_t dims, size_t ld, const u
                        uint64_t key_offset, uint64_t *d_keys, float *d_dists, uint32_t *d_counts, uint32_t *d_skipped, hipStream_t st) {
     const uint32_t kk = std::min<uint32_t>(k, LISTS_ROWS);
     const size_t m = max_chunks * kk, cand_len = std::max<size_t>(m, k);
-    auto list_of = [&](size_t q) -> size_t { return q_list ? q_list[q_base + q] : q_base + q; };
-    // queries sorted by list (stable); units of lone queries first (QT = 1), then the tiles of shared lists
-    std::vector<uint32_t> ord(nq);
-    std::iota(ord.begin(), ord.end(), 0u);
-    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return list_of(a) < list_of(b); });
-    std::vector<ListUnit> lone, tiled;
-    for (size_t i = 0; i < nq;) {
-        const size_t l = list_of(ord[i]);
-        size_t j = i;
-        while (j < nq && list_of(ord[j]) == l) j++;
-        const uint64_t len = list_off[l + 1] - list_off[l];
-        for (size_t t = i; t < j; t += LISTS_QT) {
-            const uint32_t nqt = (uint32_t)std::min<size_t>(LISTS_QT, j - t);
-            for (uint64_t c = 0; c * LISTS_ROWS < len; c++)
-                (nqt == 1 ? lone : tiled).push_back(ListUnit{list_off[l] + c * LISTS_ROWS, (uint32_t)std::min<uint64_t>(LISTS_ROWS, len - c * LISTS_ROWS),
-                                                              (uint32_t)c, (uint32_t)t, nqt});
-        }
-        i = j;
-    }
-    const size_t n_units = lone.size() + tiled.size();
+    // queries sorted by list (stable); units of lone queries first (QT = 1), then the tiles of shared lists (lists_plan.h)
+    const ListsPlan plan = lists_plan_units(nq, list_off, q_list, q_base);
+    const std::vector<uint32_t> &ord = plan.ord;
+    const std::vector<ListUnit> &table = plan.table;
+    const size_t n_units = table.size(), n_lone = plan.n_lone, n_tiled = plan.n_tiled();
     if (n_units >= (1ull << 31)) { leann_set_error("exact lists search: %zu work units in one slice", n_units); return LEANN_ERR_INVALID; }
-    std::vector<ListUnit> table(lone);
-    table.insert(table.end(), tiled.begin(), tiled.end());
     ScratchLease<uint64_t> candA, candB;
     ScratchLease<ListUnit> d_units;
     ScratchLease<uint32_t> d_ord;
@@ -210,10 +183,10 @@ static int lists_slice(const float *X, size_t n, size_t dims, size_t ld, const u
     hipLaunchKernelGGL((score_lists_kernel<QT_, FAST_>), dim3((unsigned)(count)), dim3(256), 0, st, X, (uint64_t)n, (uint32_t)dims,          \
                        (uint32_t)ld, d_live, Q, (uint32_t)dims, d_units.p + (first), d_ord.p, d_lists, kk, candA.p, (uint32_t)cand_len,      \
                        d_skipped)
-    if (!lone.empty()) { if (fast) LEANN_LISTS_LAUNCH(1, true, 0, lone.size()); else LEANN_LISTS_LAUNCH(1, false, 0, lone.size()); }
-    if (!tiled.empty()) {
-        if (fast) LEANN_LISTS_LAUNCH(LISTS_QT, true, lone.size(), tiled.size());
-        else LEANN_LISTS_LAUNCH(LISTS_QT, false, lone.size(), tiled.size());
+    if (n_lone) { if (fast) LEANN_LISTS_LAUNCH(1, true, 0, n_lone); else LEANN_LISTS_LAUNCH(1, false, 0, n_lone); }
+    if (n_tiled) {
+        if (fast) LEANN_LISTS_LAUNCH(LISTS_QT, true, n_lone, n_tiled);
+        else LEANN_LISTS_LAUNCH(LISTS_QT, false, n_lone, n_tiled);
     }
 #undef LEANN_LISTS_LAUNCH
     HIP_CHECK_RET(hipGetLastError());
@@ -230,26 +203,35 @@ int leann_internal_exact_lists(const float *d_rows, size_t n, size_t dims, size_
         leann_set_error("exact lists search: top_k must be in [1, %d] and the index smaller than 2^32 rows (top_k=%zu n=%zu)", SEG / 2, top_k, n);
         return LEANN_ERR_INVALID;
     }
-    const uint32_t k = (uint32_t)top_k, kk = std::min<uint32_t>(k, LISTS_ROWS);
-    auto chunks_of = [&](size_t q) -> size_t {
-        const size_t l = q_list ? q_list[q] : q;
-        return (size_t)((list_off[l + 1] - list_off[l] + LISTS_ROWS - 1) / LISTS_ROWS);
-    };
-    // query slices: the two candidate buffers of a slice stay within the scan pool's 64 MiB blocks (a lone longer list takes what it needs)
-    constexpr size_t CAND_BYTES = (size_t)32 << 20;
+    const uint32_t k = (uint32_t)top_k;
+    // query slices: the two candidate buffers of a slice stay within the scan pool's 64 MiB blocks (lists_plan.h)
     for (size_t q0 = 0; q0 < nq;) {
-        size_t q1 = q0, max_chunks = 0;
-        while (q1 < nq) {
-            const size_t c = std::max(max_chunks, chunks_of(q1));
-            if (q1 > q0 && (q1 - q0 + 1) * std::max<size_t>(c * kk, k) * sizeof(uint64_t) > CAND_BYTES) break;
-            max_chunks = c;
-            q1++;
-        }
+        size_t max_chunks = 0;
+        const size_t q1 = lists_plan_slice_end(q0, nq, k, list_off, q_list, &max_chunks);
         if (int rc = lists_slice(d_rows, n, dims, ld, d_live, d_queries + q0 * dims, q1 - q0, k, list_off, d_lists, q_list, q0, max_chunks, key_offset,
                                  d_keys + q0 * top_k, d_dists + q0 * top_k, d_counts + q0, d_skipped ? d_skipped + q0 : nullptr, st))
             return rc;
         q0 = q1;
     }
+    return LEANN_OK;
+}
+
+// what every lists call asks of list_off and q_list (HOST arrays), naming the argument; `lists` may be null only when every list is empty
+int leann_internal_lists_check_offsets(const char *who, size_t nq, const uint64_t *list_off, const void *lists, size_t n_lists, const uint32_t *q_list) {
+    if (list_off[0] != 0) { leann_set_error("%s: list_off[0] = %llu, not 0", who, (unsigned long long)list_off[0]); return LEANN_ERR_INVALID; }
+    for (size_t l = 0; l < n_lists; l++)
+        if (list_off[l + 1] < list_off[l] || list_off[l + 1] - list_off[l] >= (1ull << 31)) {
+            leann_set_error("%s: list_off[%zu] = %llu after %llu: offsets must be monotone and a list shorter than 2^31 entries", who, l + 1,
+                            (unsigned long long)list_off[l + 1], (unsigned long long)list_off[l]);
+            return LEANN_ERR_INVALID;
+        }
+    if (list_off[n_lists] && !lists) { leann_set_error("%s: null lists", who); return LEANN_ERR_INVALID; }
+    if (!q_list && n_lists != nq) {
+        leann_set_error("%s: q_list is null, so query i takes list i, but n_lists = %zu and nq = %zu", who, n_lists, nq);
+        return LEANN_ERR_INVALID;
+    }
+    for (size_t i = 0; q_list && i < nq; i++)
+        if (q_list[i] >= n_lists) { leann_set_error("%s: q_list[%zu] = %u, n_lists = %zu", who, i, q_list[i], n_lists); return LEANN_ERR_INVALID; }
     return LEANN_OK;
 }
 
@@ -274,21 +256,7 @@ static int lists_check(const char *who, const leann_backend *h, const void *quer
         return LEANN_ERR_UNSUPPORTED;
     }
     if (top_k == 0 || top_k > SEG / 2) { leann_set_error("%s: top_k = %zu is outside [1, %d]", who, top_k, SEG / 2); return LEANN_ERR_INVALID; }
-    if (list_off[0] != 0) { leann_set_error("%s: list_off[0] = %llu, not 0", who, (unsigned long long)list_off[0]); return LEANN_ERR_INVALID; }
-    for (size_t l = 0; l < n_lists; l++)
-        if (list_off[l + 1] < list_off[l] || list_off[l + 1] - list_off[l] >= (1ull << 31)) {
-            leann_set_error("%s: list_off[%zu] = %llu after %llu: offsets must be monotone and a list shorter than 2^31 entries", who, l + 1,
-                            (unsigned long long)list_off[l + 1], (unsigned long long)list_off[l]);
-            return LEANN_ERR_INVALID;
-        }
-    if (list_off[n_lists] && !lists) { leann_set_error("%s: null lists", who); return LEANN_ERR_INVALID; }
-    if (!q_list && n_lists != nq) {
-        leann_set_error("%s: q_list is null, so query i takes list i, but n_lists = %zu and nq = %zu", who, n_lists, nq);
-        return LEANN_ERR_INVALID;
-    }
-    for (size_t i = 0; q_list && i < nq; i++)
-        if (q_list[i] >= n_lists) { leann_set_error("%s: q_list[%zu] = %u, n_lists = %zu", who, i, q_list[i], n_lists); return LEANN_ERR_INVALID; }
-    return LEANN_OK;
+    return leann_internal_lists_check_offsets(who, nq, list_off, lists, n_lists, q_list);
 }
 
 extern "C" int leann_backend_search_exact_lists_batch_device(const leann_backend *h, const float *d_queries, size_t nq, size_t top_k,
