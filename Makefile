@@ -24,6 +24,8 @@ $(CSRC)/scan_lists.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-o
 $(CSRC)/scan_i8.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 # scan_lists_i8.hip's scores are integer sums; its one f32 step is a cast, and nothing there is to be packed into f32 pairs either
 $(CSRC)/scan_lists_i8.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# scan_bf16.hip's scores come off the matrix cores and its distances are wave_dist_rows_bf16's fmaf chains: nothing to pack there either
+$(CSRC)/scan_bf16.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(CSRC)/libleann_hip.so: $(HIP_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HIP_OBJS)

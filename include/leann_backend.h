@@ -831,6 +831,46 @@ int leann_backend_search_flat_filtered_batch_device(const leann_backend *h, cons
 int leann_backend_search_flat_filtered_batch(const leann_backend *h, const float *queries, size_t nq, size_t top_k, size_t fetch_k,
                                              const uint8_t *allow, size_t allow_stride, uint64_t *keys, float *dists, uint32_t *counts);
 
+/* ---- exhaustive search on bf16 rows (additive; csrc/scan_bf16.hip) -----------------------------------------------------
+ * A brute-force answer over a bf16 handle (LEANN_ROWS_BF16), on the bf16 matrix cores, optionally under ONE allow-bitmap shared by the
+ * batch.  Every existing entry point behaves exactly as before — the int8 flat calls, the exact filtered search, filter mode 1 and the
+ * exact-lists call keep refusing a bf16 handle, and leann_backend_device_rows keeps returning NULL for it.
+ *
+ * Definition.  r = f32 -> bf16 round to nearest even, w = the exact widening (csrc/bf16.h); the handle's rows are x_i = r(X_i); q is
+ * a query.  The query is split, not rounded:
+ *   1. Query pieces.  hi_j = r(q_j), lo_j = r(q_j - w(hi_j)); the subtraction is exact in f32, and w(hi_j) + w(lo_j) is q_j to within
+ *      2^-17 |q_j|.  A query with an element that is not finite — or so large that r(q_j) is an infinity — has no pieces and its
+ *      count is 0.
+ *   2. Screen score.  s_i = sum_j (w(hi_j) + w(lo_j)) * w(x_ij).  Every product of two bf16 values is exact in f32; the sum is
+ *      accumulated in f32 on the matrix cores (v_mfma_f32_32x32x16_bf16) IN AN ORDER THIS DEFINITION LEAVES OPEN.
+ *   3. Candidates.  The fetch_k rows with the largest s_i among the rows that are live (not removed) and allowed; ties go to the lower
+ *      position.
+ *   4. Answer.  Each candidate gets d = 1 - canonical dot(q, w(x_i)), bit for bit the distance a bf16 walk reports for that key (the
+ *      same query staging, the same wave_dist_rows_bf16).  The candidates are sorted ascending by (d as an ordered float, position);
+ *      the first top_k come back as position + key_offset, the unused tail as UINT64_MAX / +inf, and counts[q] = min(top_k, rows live
+ *      and allowed).
+ * Consequences.  With fetch_k >= the number of live allowed rows the answer is the exact top-k over the bf16 rows.  Otherwise it is
+ * exact whenever the top_k-th and the (fetch_k + 1)-th canonical distances lie further apart than the screen's error — about 2^-17
+ * relative per product, plus the f32 accumulation —; it is approximate in the candidate set only, never in a returned distance.
+ * A row element that is not finite makes s_i a NaN or an infinity: where such a row ranks is whatever the select step's key gives that
+ * score (not specified, not tested).  Because the sum is order-free up to rounding, the store's element permutation is never undone:
+ * the pieces are written in store order once.
+ *
+ * Arguments, limits (1 <= top_k <= fetch_k <= 1024), d_allow, the empty index, key_offset and the stream contract (library scratch,
+ * returns with `stream` SYNCHRONISED, cannot be captured into a HIP graph): those of leann_backend_search_flat_batch[_device].
+ * LEANN_ERR_INVALID for a null argument or a k out of range; LEANN_ERR_UNSUPPORTED, on the host before any device work, the message
+ * naming the way out: an f32 handle (use leann_backend_search_filtered_exact_batch or leann_scan_topk_device), an int8 handle (use
+ * leann_backend_search_flat_batch), a recompute-on handle (use leann_recompute_search_batch_device), a composite handle (search the
+ * shards, merge with leann_merge_topk_device).  Out of scope: per-query lists and bitmaps on bf16 rows, composite handles.
+ * leann_split_query_bf16: step 1 on the host, no device — hi_out and lo_out [d] in ELEMENT order, written element by element
+ * whatever q holds: the reference the device split is held to. */
+int leann_backend_search_flat_bf16_batch_device(const leann_backend *h, const float *d_queries, size_t nq, size_t top_k, size_t fetch_k,
+                                                const uint8_t *d_allow /* shared bitmap or NULL */, uint64_t *d_keys, float *d_dists,
+                                                uint32_t *d_counts, void *stream);
+int leann_backend_search_flat_bf16_batch(const leann_backend *h, const float *queries, size_t nq, size_t top_k, size_t fetch_k,
+                                         const uint8_t *allow /* shared bitmap or NULL */, uint64_t *keys, float *dists, uint32_t *counts);
+int leann_split_query_bf16(const float *q, size_t d, uint16_t *hi_out, uint16_t *lo_out);
+
 /* ---- sharded indexes (the reference has no counterpart: IndexSearcher owns one Box<dyn BackendSearcher>,
  * src/index/searcher.rs:68) --------------------------------------------------------------------------------------------------
  * One process, G devices: the composite handle leann_backend_open returns for a device list, or built here from rows / handles.

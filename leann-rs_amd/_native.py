@@ -154,6 +154,9 @@ SIGNATURES = {
     "leann_backend_search_flat_filtered_batch_device": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp]),
     "leann_backend_search_flat_filtered_batch": (C.c_int, [vp, f32p, C.c_size_t, C.c_size_t, C.c_size_t, u8p, C.c_size_t, u64p, f32p, u32p]),
     "leann_quantize_query_i8": (C.c_int, [f32p, C.c_size_t, C.POINTER(C.c_int8), C.POINTER(C.c_int8), C.POINTER(C.c_int32)]),
+    "leann_backend_search_flat_bf16_batch_device": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp]),
+    "leann_backend_search_flat_bf16_batch": (C.c_int, [vp, f32p, C.c_size_t, C.c_size_t, C.c_size_t, u8p, u64p, f32p, u32p]),
+    "leann_split_query_bf16": (C.c_int, [f32p, C.c_size_t, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
     "leann_synth_rows_device": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                          C.c_float, C.c_uint32, C.c_uint64, C.c_uint64, vp, vp]),
     "leann_scan_topk_device": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_size_t,

@@ -71,6 +71,16 @@ def quantize_query_i8(q, exps):
     return codes, E.value
 
 
+def split_query_bf16(q):
+    """one query [d] -> (hi, lo) uint16 [d] in element order: the two bf16 pieces hi = r(q), lo = r(q - w(hi)) of the flat search on
+    bf16 rows (include/leann_backend.h "exhaustive search on bf16 rows"), the library's own reference, on the host"""
+    q = np.ascontiguousarray(q, np.float32).reshape(-1)
+    hi, lo = np.zeros(q.shape[0], np.uint16), np.zeros(q.shape[0], np.uint16)
+    u16p = C.POINTER(C.c_uint16)
+    N.check(N.lib().leann_split_query_bf16(_p(q, f32p), q.shape[0], hi.ctypes.data_as(u16p), lo.ctypes.data_as(u16p)))
+    return hi, lo
+
+
 def _p(a, t):
     return a.ctypes.data_as(t) if a is not None else None
 
@@ -342,6 +352,30 @@ class BackendSearcher:
         """the same with device pointers (ints); synchronises `stream` before it returns"""
         N.check(N.lib().leann_backend_search_flat_batch_device(self._h, d_queries, nq, top_k, fetch_k, d_allow, d_keys, d_dists,
                                                                d_counts, stream))
+
+    def search_flat_bf16_batch(self, queries, top_k, fetch_k, allow=None):
+        """bf16 handles: every live and allowed row screened on the bf16 matrix cores by its dot product with the query split into two
+        bf16 pieces (not rounded), the fetch_k best scored with the walk's distance, the best top_k returned.  allow: None or ONE bitmap
+        [ceil(len/8)] for the batch."""
+        Q = np.ascontiguousarray(queries, np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dims():
+            raise LeannError(1, f"queries must be [nq x {self.dims()}]")
+        if allow is not None:
+            allow = np.ascontiguousarray(allow, np.uint8)
+            if allow.ndim != 1 or allow.shape[0] < (self.len() + 7) // 8:
+                raise LeannError(1, "allow-bitmap must be one bitmap of ceil(len / 8) bytes")
+        nq = Q.shape[0]
+        keys = np.full((nq, max(top_k, 1)), np.iinfo(np.uint64).max, np.uint64)
+        dists = np.full((nq, max(top_k, 1)), np.inf, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        N.check(N.lib().leann_backend_search_flat_bf16_batch(self._h, _p(Q, f32p), nq, top_k, fetch_k, _p(allow, u8p), _p(keys, u64p),
+                                                             _p(dists, f32p), _p(counts, u32p)))
+        return keys, dists, counts
+
+    def search_flat_bf16_batch_device(self, d_queries, nq, top_k, fetch_k, d_keys, d_dists, d_counts, d_allow=None, stream=None):
+        """the same with device pointers (ints); synchronises `stream` before it returns"""
+        N.check(N.lib().leann_backend_search_flat_bf16_batch_device(self._h, d_queries, nq, top_k, fetch_k, d_allow, d_keys, d_dists,
+                                                                    d_counts, stream))
 
     def search_flat_lists_batch(self, queries, top_k, fetch_k, lists, q_list=None):
         """int8 handles: search_flat_batch with query i screened over the positions of lists[q_list[i]] (q_list None: lists[i]) only;
