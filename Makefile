@@ -26,6 +26,8 @@ $(CSRC)/scan_i8.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 $(CSRC)/scan_lists_i8.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 # scan_bf16.hip's scores come off the matrix cores and its distances are wave_dist_rows_bf16's fmaf chains: nothing to pack there either
 $(CSRC)/scan_bf16.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# scan_bits.hip's scores are integer sums off the matrix cores; its only f32 steps are a comparison and a cast: the same
+$(CSRC)/scan_bits.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(CSRC)/libleann_hip.so: $(HIP_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HIP_OBJS)

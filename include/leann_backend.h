@@ -871,6 +871,56 @@ int leann_backend_search_flat_bf16_batch(const leann_backend *h, const float *qu
                                          const uint8_t *allow /* shared bitmap or NULL */, uint64_t *keys, float *dists, uint32_t *counts);
 int leann_split_query_bf16(const float *q, size_t d, uint16_t *hi_out, uint16_t *lo_out);
 
+/* ---- sign-bit rows: 1-bit exhaustive search (additive; csrc/scan_bits.hip) ------------------------------------------------
+ * One bit per element of f32 rows, screened exhaustively on the integer matrix cores, the exact distances restored by the rerank of
+ * "refining results on exact rows": binary quantisation with oversampling and rescoring.  An object of its own beside the handles;
+ * every existing entry point behaves exactly as before.
+ *
+ * Definition.  A leann_bit_rows holds, for the positions key_offset .. key_offset + n - 1, one bit per element of X [n x dims].
+ *   1. Codes.  b_ij = 1 iff x_ij > c_j, a plain f32 comparison; c [dims] is an optional centre, NULL = all zeros.  A NaN on either
+ *      side, x_ij == c_j and -0 against +0 all give 0.  Bit j of a row is bit (j & 7) of byte (j >> 3); the row pitch is
+ *      16 * ceil(dims / 128) bytes (96 B at 768, 512 B at 4096), padding bits zero.  leann_bit_rows_export returns the rows in exactly
+ *      this layout; leann_pack_sign_bits computes it on the host, no device: the reference the pack kernel is held to.
+ *   2. Query codes.  Steps 2-4 of "exhaustive search on int8 rows" with every exponent 0: cq = leann_quantize_query_i8(q, dims,
+ *      zeros).  A query with an element that is not finite has no codes and its count is 0 (its keys and scores are all tail).  The
+ *      query is not centred: <q, c> is one constant per query and does not change the ranking.
+ *   3. Score.  t_i = sum_j cq_j * b_ij in int32: exact in any order, and |t_i| <= 127 * 4096 < 2^24, so (float)t_i is exact for every
+ *      supported width.  (The sign-vector dot sum_j cq_j (2 b_ij - 1) is 2 t_i - sum_j cq_j: the same ranking per query.)
+ *   4. Candidates.  The fetch_k allowed rows with the largest t_i, ties to the lower position, returned in that order: keys are
+ *      position + key_offset, scores (float)t_i, counts[q] = min(fetch_k, allowed rows); the tail is UINT64_MAX / -inf.
+ *   5. Refined search.  Step 4 into library scratch, then leann_rerank_batch_device on a leann_exact_rows, its top_k, skip and tail
+ *      (UINT64_MAX / +inf) rules unchanged.  With fetch_k >= n the answer is the exact f32 top-k, bit for bit; otherwise it is
+ *      approximate in the candidate set only, never in a returned distance.
+ * Limits: 1 <= top_k <= fetch_k <= 1024, dims in [1, 4096], n < 2^32 - 1.  d_allow: NULL or ONE device bitmap of ceil(n / 8) bytes
+ * shared by the batch, bits at or behind n ignored.  An empty object gives counts 0.  LEANN_ERR_INVALID, on the host before any device
+ * work and naming the argument: a null pointer, a k out of range, exact rows of other dims, on another device, or not covering the
+ * positions key_offset .. key_offset + n.  The search calls take library scratch, return with `stream` SYNCHRONISED and cannot be
+ * captured into a HIP graph.
+ *   _from_device  only reads d_rows [n x ld] (and d_center) on `device`: they need not outlive the object.
+ *   _from_host    stages the rows in slabs, so a collection larger than the free device memory can be packed. */
+typedef struct leann_bit_rows leann_bit_rows;
+int leann_bit_rows_from_device(const float *d_rows, size_t n, size_t dims, size_t ld, const float *d_center /* or NULL */, int device,
+                               uint64_t key_offset, leann_bit_rows **out);
+int leann_bit_rows_from_host(const float *rows, size_t n, size_t dims, const float *center /* or NULL */, int device, uint64_t key_offset,
+                             leann_bit_rows **out);
+size_t leann_bit_rows_len(const leann_bit_rows *b);
+size_t leann_bit_rows_dims(const leann_bit_rows *b);
+size_t leann_bit_rows_pitch(const leann_bit_rows *b); /* bytes per row */
+int leann_bit_rows_export(const leann_bit_rows *b, uint8_t *out /* [n x pitch], host */);
+void leann_bit_rows_close(leann_bit_rows *b);
+int leann_pack_sign_bits(const float *rows, size_t n, size_t dims, const float *center /* or NULL */, uint8_t *out /* [n x pitch] */);
+int leann_bit_rows_search_batch_device(const leann_bit_rows *b, const float *d_queries, size_t nq, size_t fetch_k,
+                                       const uint8_t *d_allow /* shared bitmap or NULL */, uint64_t *d_keys, float *d_scores,
+                                       uint32_t *d_counts, void *stream);
+int leann_bit_rows_search_batch(const leann_bit_rows *b, const float *queries, size_t nq, size_t fetch_k,
+                                const uint8_t *allow /* shared bitmap or NULL */, uint64_t *keys, float *scores, uint32_t *counts);
+int leann_bit_rows_search_refined_batch_device(const leann_bit_rows *b, const leann_exact_rows *r, const float *d_queries, size_t nq,
+                                               size_t top_k, size_t fetch_k, const uint8_t *d_allow /* shared bitmap or NULL */,
+                                               uint64_t *d_keys, float *d_dists, uint32_t *d_counts, void *stream);
+int leann_bit_rows_search_refined_batch(const leann_bit_rows *b, const leann_exact_rows *r, const float *queries, size_t nq, size_t top_k,
+                                        size_t fetch_k, const uint8_t *allow /* shared bitmap or NULL */, uint64_t *keys, float *dists,
+                                        uint32_t *counts);
+
 /* ---- sharded indexes (the reference has no counterpart: IndexSearcher owns one Box<dyn BackendSearcher>,
  * src/index/searcher.rs:68) --------------------------------------------------------------------------------------------------
  * One process, G devices: the composite handle leann_backend_open returns for a device list, or built here from rows / handles.

@@ -779,6 +779,131 @@ def rerank_batch_device(rows, d_queries, nq, d_keys, d_counts, fetch_k, top_k, d
                                               d_out_counts, d_skipped, stream))
 
 
+def pack_sign_bits(x, center=None):
+    """f32 rows [n x dims] -> uint8 [n x 16 * ceil(dims / 128)]: bit j of a row is x[j] > center[j] (center None: > 0), little-endian
+    within a byte, padding bits zero (include/leann_backend.h "sign-bit rows"): the library's own reference, on the host"""
+    x = np.ascontiguousarray(x, np.float32)
+    if x.ndim != 2 or x.shape[1] < 1:
+        raise LeannError(1, "pack_sign_bits: rows must be [n x dims]")
+    center = _center(center, x.shape[1])
+    out = np.zeros((x.shape[0], 16 * ((x.shape[1] + 127) // 128)), np.uint8)
+    N.check(N.lib().leann_pack_sign_bits(_p(x, f32p), x.shape[0], x.shape[1], _p(center, f32p), _p(out, u8p)))
+    return out
+
+
+def _center(center, dims):
+    if center is None:
+        return None
+    center = np.ascontiguousarray(center, np.float32).reshape(-1)
+    if center.shape[0] != dims:
+        raise LeannError(1, f"the centre must have {dims} elements")
+    return center
+
+
+class BitRows:
+    """sign-bit rows (leann_bit_rows, include/leann_backend.h "sign-bit rows"): one bit per element of f32 rows, searched exhaustively
+    on the integer matrix cores; search_refined_batch restores exact distances on an ExactRows"""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def from_host(cls, X, center=None, device=0, key_offset=0):
+        X = np.ascontiguousarray(X, np.float32)
+        if X.ndim != 2:
+            raise LeannError(1, "BitRows.from_host: rows must be [n x dims]")
+        h = C.c_void_p()
+        N.check(N.lib().leann_bit_rows_from_host(_p(X, f32p), X.shape[0], X.shape[1], _p(_center(center, X.shape[1]), f32p), device,
+                                                 key_offset, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_device(cls, d_rows_ptr, n, dims, ld, d_center_ptr=None, device=0, key_offset=0):
+        """f32 rows [n x ld] (and an optional centre [dims]) on `device`, device pointers (ints): only read, they need not outlive this object"""
+        h = C.c_void_p()
+        N.check(N.lib().leann_bit_rows_from_device(d_rows_ptr, n, dims, ld, d_center_ptr, device, key_offset, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_searcher(cls, searcher, d_center_ptr=None, device=0, key_offset=0):
+        """the bits of an f32 index's rows; a handle without f32 rows (bf16, int8, recompute-on, composite) is refused"""
+        ptr = searcher.device_rows_ptr()
+        if not ptr:
+            raise LeannError(1, "BitRows.from_searcher: the index has no f32 rows on one device (leann_backend_device_rows is NULL)")
+        return cls.from_device(ptr, searcher.len(), searcher.dims(), searcher.graph_info()["ld"], d_center_ptr, device, key_offset)
+
+    def len(self):
+        return int(N.lib().leann_bit_rows_len(self._h))
+
+    __len__ = len
+
+    def dims(self):
+        return int(N.lib().leann_bit_rows_dims(self._h))
+
+    def pitch(self):
+        return int(N.lib().leann_bit_rows_pitch(self._h))
+
+    def export(self):
+        """the rows as uint8 [n x pitch], exactly pack_sign_bits's layout"""
+        out = np.zeros((self.len(), self.pitch()), np.uint8)
+        N.check(N.lib().leann_bit_rows_export(self._h, _p(out, u8p)))
+        return out
+
+    def _host_args(self, queries, allow):
+        Q = np.ascontiguousarray(queries, np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dims():
+            raise LeannError(1, f"queries must be [nq x {self.dims()}]")
+        if allow is not None:
+            allow = np.ascontiguousarray(allow, np.uint8)
+            if allow.ndim != 1 or allow.shape[0] < (self.len() + 7) // 8:
+                raise LeannError(1, "allow-bitmap must be one bitmap of ceil(len / 8) bytes")
+        return Q, allow
+
+    def search_batch(self, queries, fetch_k, allow=None):
+        """the fetch_k allowed rows with the largest int32 score per query, ties to the lower position: (keys, scores, counts); the
+        tail is UINT64_MAX / -inf.  allow: None or ONE bitmap [ceil(len/8)] for the batch."""
+        Q, allow = self._host_args(queries, allow)
+        nq = Q.shape[0]
+        keys = np.full((nq, max(fetch_k, 1)), np.iinfo(np.uint64).max, np.uint64)
+        scores = np.full((nq, max(fetch_k, 1)), -np.inf, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        N.check(N.lib().leann_bit_rows_search_batch(self._h, _p(Q, f32p), nq, fetch_k, _p(allow, u8p), _p(keys, u64p), _p(scores, f32p),
+                                                    _p(counts, u32p)))
+        return keys, scores, counts
+
+    def search_batch_device(self, d_queries, nq, fetch_k, d_keys, d_scores, d_counts, d_allow=None, stream=None):
+        """the same with device pointers (ints); synchronises `stream` before it returns"""
+        N.check(N.lib().leann_bit_rows_search_batch_device(self._h, d_queries, nq, fetch_k, d_allow, d_keys, d_scores, d_counts, stream))
+
+    def search_refined_batch(self, exact_rows, queries, top_k, fetch_k, allow=None):
+        """search_batch's candidates scored again on the exact rows of an ExactRows: the best top_k by the f32 distance"""
+        Q, allow = self._host_args(queries, allow)
+        nq = Q.shape[0]
+        keys = np.full((nq, max(top_k, 1)), np.iinfo(np.uint64).max, np.uint64)
+        dists = np.full((nq, max(top_k, 1)), np.inf, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        N.check(N.lib().leann_bit_rows_search_refined_batch(self._h, exact_rows._h if exact_rows is not None else None, _p(Q, f32p), nq,
+                                                            top_k, fetch_k, _p(allow, u8p), _p(keys, u64p), _p(dists, f32p),
+                                                            _p(counts, u32p)))
+        return keys, dists, counts
+
+    def search_refined_batch_device(self, exact_rows, d_queries, nq, top_k, fetch_k, d_keys, d_dists, d_counts, d_allow=None, stream=None):
+        """the same with device pointers (ints); synchronises `stream` before it returns"""
+        N.check(N.lib().leann_bit_rows_search_refined_batch_device(self._h, exact_rows._h if exact_rows is not None else None, d_queries,
+                                                                   nq, top_k, fetch_k, d_allow, d_keys, d_dists, d_counts, stream))
+
+    def close(self):
+        if self._h:
+            N.lib().leann_bit_rows_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ShardedIndex:
     """leann_sharded (include/leann_backend.h "sharded indexes", csrc/shard.hip): the corpus partitioned into contiguous position
     ranges, one sub-index per shard; a search = per-shard traversal + gather of the per-shard lists + merge kernel.  One process

@@ -386,6 +386,15 @@ int leann_internal_topk_finish(TopkRun &run, uint64_t key_offset, const uint32_t
                                uint32_t *d_counts, bool *overflowed);
 int leann_internal_score(const float *X, size_t rows, size_t dims, size_t ld, const float *d_queries, size_t nq, size_t ldq, float *S,
                          hipStream_t st);
+// exact f32 rows to refine on (refine.hip makes and reads them; scan_bits.hip checks dims, device and covered positions before it delegates)
+struct leann_exact_rows {
+    const float *X = nullptr; // what the kernel reads: borrowed rows, `hbm`, or the device address of `host`
+    size_t n = 0, dims = 0, ld = 0;
+    int device = 0, placement = LEANN_EXACT_ROWS_HBM;
+    uint64_t key_offset = 0;
+    DeviceBuf<float> hbm;
+    PinnedBuf<float> host;
+};
 size_t leann_internal_feat_file_row_bytes(const GraphView &g);
 int leann_internal_feat_rows_to_host(const leann_backend *h, size_t r0, size_t rows, unsigned char *out);
 std::string leann_internal_index_file(const char *stem, int backend);

@@ -143,15 +143,7 @@ void leann_internal_pinned_release(void *p) {
 }
 
 // ---- the rows ------------------------------------------------------------------------------------------------------------------------
-struct leann_exact_rows {
-    const float *X = nullptr; // what the kernel reads: borrowed rows, `hbm`, or the device address of `host`
-    size_t n = 0, dims = 0, ld = 0;
-    int device = 0, placement = LEANN_EXACT_ROWS_HBM;
-    uint64_t key_offset = 0;
-    DeviceBuf<float> hbm;
-    PinnedBuf<float> host;
-};
-
+// (struct leann_exact_rows: internal.h — scan_bits.hip checks a bit-row object against it)
 static int check_rows_shape(const char *who, size_t n, size_t dims, int placement, const void *out) {
     if (!out) { leann_set_error("%s: null out", who); return LEANN_ERR_INVALID; }
     if (dims < 1 || dims > 4096) { leann_set_error("%s: dims = %zu is outside [1, 4096]", who, dims); return LEANN_ERR_INVALID; }
