@@ -28,6 +28,8 @@ $(CSRC)/scan_lists_i8.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp3
 $(CSRC)/scan_bf16.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 # scan_bits.hip's scores are integer sums off the matrix cores; its only f32 steps are a comparison and a cast: the same
 $(CSRC)/scan_bits.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# scan_mx4.hip's scores come off the block-scaled matrix cores and its codes are integer arithmetic on f32 bits: the same
+$(CSRC)/scan_mx4.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(CSRC)/libleann_hip.so: $(HIP_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HIP_OBJS)

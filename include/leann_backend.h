@@ -921,6 +921,60 @@ int leann_bit_rows_search_refined_batch(const leann_bit_rows *b, const leann_exa
                                         size_t fetch_k, const uint8_t *allow /* shared bitmap or NULL */, uint64_t *keys, float *dists,
                                         uint32_t *counts);
 
+/* ---- MXFP4 rows: 4-bit exhaustive search on the block-scaled matrix cores (additive; csrc/scan_mx4.hip) -----------------
+ * Four bits per element plus one scale byte per 32 elements (OCP microscaling, MXFP4): 408 B per 768-d row.  The rows are screened
+ * exhaustively against an MXFP8 query by v_mfma_scale_f32_32x32x64_f8f6f4, the exact distances restored by the rerank of "refining
+ * results on exact rows".  An object of its own beside the handles; every existing entry point behaves exactly as before.
+ *
+ * Definition.  A block is 32 consecutive elements of a row or a query; columns at or behind dims count as 0.  A k-tile is 256 elements
+ * (8 blocks); rows and query codes are padded to whole k-tiles, KT = ceil(dims / 256) of them.
+ *   1. Row block scale.  a = max |x_j| over the block, an element that is not finite counting as 0 (here and in step 2); E = the
+ *      biased exponent field of a as f32 (0 for zero and for denormals); the scale byte is sx = max(E - 2, 0), never 255;
+ *      y_j = x_j 2^(127 - sx), exact; the block's largest |y| lies in [4, 8) whenever E >= 2.
+ *   2. Row codes (E2M1).  The magnitude code is |y| rounded to nearest, ties to the even code, saturating:
+ *        |y| <= 0.25 -> 0 (0)      (0.25, 0.75) -> 1 (0.5)    [0.75, 1.25] -> 2 (1)    (1.25, 1.75) -> 3 (1.5)
+ *        [1.75, 2.5] -> 4 (2)      (2.5, 3.5)   -> 5 (3)      [3.5, 5]     -> 6 (4)    > 5          -> 7 (6)
+ *      Bit 3 of the nibble is the sign bit of x_j (set for -0 and for negatives that round to 0); an x_j that is not finite gives
+ *      nibble 0.  Element j is nibble (j & 1) of byte (j >> 1), low nibble first.  Layout, as leann_mx4_rows_export returns it:
+ *      codes [n x 128 KT] bytes (whole 128-B lines, 384 B at 768) and scales [n x 8 KT] bytes in block order (24 B at 768); padding
+ *      nibbles and the scales of all-padding blocks are 0.  leann_pack_mx4 computes both on the host, no device: the reference the
+ *      pack kernel is held to, byte for byte.
+ *   3. Query codes (MXFP8, OCP E4M3 "FN").  Per block sq = max(E - 8, 0) and y = q 2^(127 - sq); the code is y rounded to nearest even
+ *      in E4M3 (bias 7, subnormal step 2^-9, largest value 448 = 0x7E; what would round above 448 becomes 448), its sign bit the sign
+ *      bit of q.  codes [256 KT] bytes in element order, scales [8 KT]; padding zero.  A query with an element that is not finite has
+ *      no codes: its count is 0 and its answer all tail.  leann_quantize_query_mx8 is the host reference; for such a query it writes
+ *      zero codes and every scale byte 0xFF, the E8M0 NaN, which no finite query produces (sq <= 246).
+ *   4. Score.  t_i = sum over blocks of 2^(sx_ib + sq_b - 254) * sum_{j in block} A_j B_ij, A the query's E4M3 values and B the row's
+ *      E2M1 values, accumulated in f32 by the instruction.  Every product A_j B_ij is exact (at most 6 significant bits); the order
+ *      and the internal width of the sums are the hardware's and left open, as for bf16 rows.
+ *   5. Candidates, refined search, limits, refusals, empty object, stream semantics: steps 4 and 5 and the limits paragraph of
+ *      "sign-bit rows" word for word, with t_i in place of (float)t_i.  Ties go to the lower position; the tail is UINT64_MAX / -inf
+ *      for scores and the rerank's +inf for distances; 1 <= top_k <= fetch_k <= 1024, dims in [1, 4096], n < 2^32 - 1; d_allow is
+ *      NULL or ONE device bitmap of ceil(n / 8) bytes shared by the batch. */
+typedef struct leann_mx4_rows leann_mx4_rows;
+int leann_mx4_rows_from_device(const float *d_rows, size_t n, size_t dims, size_t ld, int device, uint64_t key_offset, leann_mx4_rows **out);
+int leann_mx4_rows_from_host(const float *rows, size_t n, size_t dims, int device, uint64_t key_offset, leann_mx4_rows **out);
+size_t leann_mx4_rows_len(const leann_mx4_rows *b);
+size_t leann_mx4_rows_dims(const leann_mx4_rows *b);
+size_t leann_mx4_rows_code_pitch(const leann_mx4_rows *b);  /* code bytes per row: 128 KT */
+size_t leann_mx4_rows_scale_pitch(const leann_mx4_rows *b); /* scale bytes per row: 8 KT */
+int leann_mx4_rows_export(const leann_mx4_rows *b, uint8_t *codes_out /* [n x code pitch], host */,
+                          uint8_t *scales_out /* [n x scale pitch], host */);
+void leann_mx4_rows_close(leann_mx4_rows *b);
+int leann_pack_mx4(const float *rows, size_t n, size_t dims, uint8_t *codes_out /* [n x 128 KT] */, uint8_t *scales_out /* [n x 8 KT] */);
+int leann_quantize_query_mx8(const float *q, size_t dims, uint8_t *codes_out /* [256 KT] */, uint8_t *scales_out /* [8 KT] */);
+int leann_mx4_rows_search_batch_device(const leann_mx4_rows *b, const float *d_queries, size_t nq, size_t fetch_k,
+                                       const uint8_t *d_allow /* shared bitmap or NULL */, uint64_t *d_keys, float *d_scores,
+                                       uint32_t *d_counts, void *stream);
+int leann_mx4_rows_search_batch(const leann_mx4_rows *b, const float *queries, size_t nq, size_t fetch_k,
+                                const uint8_t *allow /* shared bitmap or NULL */, uint64_t *keys, float *scores, uint32_t *counts);
+int leann_mx4_rows_search_refined_batch_device(const leann_mx4_rows *b, const leann_exact_rows *r, const float *d_queries, size_t nq,
+                                               size_t top_k, size_t fetch_k, const uint8_t *d_allow /* shared bitmap or NULL */,
+                                               uint64_t *d_keys, float *d_dists, uint32_t *d_counts, void *stream);
+int leann_mx4_rows_search_refined_batch(const leann_mx4_rows *b, const leann_exact_rows *r, const float *queries, size_t nq, size_t top_k,
+                                        size_t fetch_k, const uint8_t *allow /* shared bitmap or NULL */, uint64_t *keys, float *dists,
+                                        uint32_t *counts);
+
 /* ---- sharded indexes (the reference has no counterpart: IndexSearcher owns one Box<dyn BackendSearcher>,
  * src/index/searcher.rs:68) --------------------------------------------------------------------------------------------------
  * One process, G devices: the composite handle leann_backend_open returns for a device list, or built here from rows / handles.

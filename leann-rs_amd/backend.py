@@ -904,6 +904,128 @@ class BitRows:
             pass
 
 
+def _mx4_ktiles(dims):
+    return (dims + 255) // 256
+
+
+def pack_mx4(x):
+    """f32 rows [n x dims] -> (codes uint8 [n x 128 KT], scales uint8 [n x 8 KT]), KT = ceil(dims / 256): E2M1 nibbles, low nibble first,
+    and one E8M0 scale byte per 32 elements (include/leann_backend.h "MXFP4 rows"): the library's own reference, on the host"""
+    x = np.ascontiguousarray(x, np.float32)
+    if x.ndim != 2 or x.shape[1] < 1:
+        raise LeannError(1, "pack_mx4: rows must be [n x dims]")
+    kt = _mx4_ktiles(x.shape[1])
+    codes, scales = np.zeros((x.shape[0], 128 * kt), np.uint8), np.zeros((x.shape[0], 8 * kt), np.uint8)
+    N.check(N.lib().leann_pack_mx4(_p(x, f32p), x.shape[0], x.shape[1], _p(codes, u8p), _p(scales, u8p)))
+    return codes, scales
+
+
+def quantize_query_mx8(q):
+    """one f32 query -> (codes uint8 [256 KT] in OCP E4M3, scales uint8 [8 KT], finite): the host reference of the MXFP4 search's query
+    codes; a query with an element that is not finite has no codes (finite False, codes zero, scales 0xFF)"""
+    q = np.ascontiguousarray(q, np.float32).reshape(-1)
+    if q.shape[0] < 1:
+        raise LeannError(1, "quantize_query_mx8: the query is empty")
+    kt = _mx4_ktiles(q.shape[0])
+    codes, scales = np.zeros(256 * kt, np.uint8), np.zeros(8 * kt, np.uint8)
+    N.check(N.lib().leann_quantize_query_mx8(_p(q, f32p), q.shape[0], _p(codes, u8p), _p(scales, u8p)))
+    return codes, scales, bool(scales[0] != 0xFF)
+
+
+class Mx4Rows:
+    """MXFP4 rows (leann_mx4_rows, include/leann_backend.h "MXFP4 rows"): four bits per element and a scale byte per 32 of f32 rows,
+    searched exhaustively on the block-scaled matrix cores; search_refined_batch restores exact distances on an ExactRows"""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def from_host(cls, X, device=0, key_offset=0):
+        X = np.ascontiguousarray(X, np.float32)
+        if X.ndim != 2:
+            raise LeannError(1, "Mx4Rows.from_host: rows must be [n x dims]")
+        h = C.c_void_p()
+        N.check(N.lib().leann_mx4_rows_from_host(_p(X, f32p), X.shape[0], X.shape[1], device, key_offset, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_device(cls, d_rows_ptr, n, dims, ld, device=0, key_offset=0):
+        """f32 rows [n x ld] on `device`, a device pointer (int): only read, they need not outlive this object"""
+        h = C.c_void_p()
+        N.check(N.lib().leann_mx4_rows_from_device(d_rows_ptr, n, dims, ld, device, key_offset, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_searcher(cls, searcher, device=0, key_offset=0):
+        """the codes of an f32 index's rows; a handle without f32 rows (bf16, int8, recompute-on, composite) is refused"""
+        ptr = searcher.device_rows_ptr()
+        if not ptr:
+            raise LeannError(1, "Mx4Rows.from_searcher: the index has no f32 rows on one device (leann_backend_device_rows is NULL)")
+        return cls.from_device(ptr, searcher.len(), searcher.dims(), searcher.graph_info()["ld"], device, key_offset)
+
+    def len(self):
+        return int(N.lib().leann_mx4_rows_len(self._h))
+
+    __len__ = len
+
+    def dims(self):
+        return int(N.lib().leann_mx4_rows_dims(self._h))
+
+    def export(self):
+        """(codes uint8 [n x code pitch], scales uint8 [n x scale pitch]), exactly pack_mx4's layout"""
+        L = N.lib()
+        codes = np.zeros((self.len(), int(L.leann_mx4_rows_code_pitch(self._h))), np.uint8)
+        scales = np.zeros((self.len(), int(L.leann_mx4_rows_scale_pitch(self._h))), np.uint8)
+        N.check(L.leann_mx4_rows_export(self._h, _p(codes, u8p), _p(scales, u8p)))
+        return codes, scales
+
+    _host_args = BitRows._host_args
+
+    def search_batch(self, queries, fetch_k, allow=None):
+        """the fetch_k allowed rows with the largest block-scaled score per query, ties to the lower position: (keys, scores,
+        counts); the tail is UINT64_MAX / -inf.  allow: None or ONE bitmap [ceil(len/8)] for the batch."""
+        Q, allow = self._host_args(queries, allow)
+        nq = Q.shape[0]
+        keys = np.full((nq, max(fetch_k, 1)), np.iinfo(np.uint64).max, np.uint64)
+        scores = np.full((nq, max(fetch_k, 1)), -np.inf, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        N.check(N.lib().leann_mx4_rows_search_batch(self._h, _p(Q, f32p), nq, fetch_k, _p(allow, u8p), _p(keys, u64p), _p(scores, f32p),
+                                                    _p(counts, u32p)))
+        return keys, scores, counts
+
+    def search_batch_device(self, d_queries, nq, fetch_k, d_keys, d_scores, d_counts, d_allow=None, stream=None):
+        """the same with device pointers (ints); synchronises `stream` before it returns"""
+        N.check(N.lib().leann_mx4_rows_search_batch_device(self._h, d_queries, nq, fetch_k, d_allow, d_keys, d_scores, d_counts, stream))
+
+    def search_refined_batch(self, exact_rows, queries, top_k, fetch_k, allow=None):
+        """search_batch's candidates scored again on the exact rows of an ExactRows: the best top_k by the f32 distance"""
+        Q, allow = self._host_args(queries, allow)
+        nq = Q.shape[0]
+        keys = np.full((nq, max(top_k, 1)), np.iinfo(np.uint64).max, np.uint64)
+        dists = np.full((nq, max(top_k, 1)), np.inf, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        N.check(N.lib().leann_mx4_rows_search_refined_batch(self._h, exact_rows._h if exact_rows is not None else None, _p(Q, f32p), nq,
+                                                            top_k, fetch_k, _p(allow, u8p), _p(keys, u64p), _p(dists, f32p),
+                                                            _p(counts, u32p)))
+        return keys, dists, counts
+
+    def search_refined_batch_device(self, exact_rows, d_queries, nq, top_k, fetch_k, d_keys, d_dists, d_counts, d_allow=None, stream=None):
+        """the same with device pointers (ints); synchronises `stream` before it returns"""
+        N.check(N.lib().leann_mx4_rows_search_refined_batch_device(self._h, exact_rows._h if exact_rows is not None else None, d_queries,
+                                                                   nq, top_k, fetch_k, d_allow, d_keys, d_dists, d_counts, stream))
+
+    def close(self):
+        if self._h:
+            N.lib().leann_mx4_rows_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ShardedIndex:
     """leann_sharded (include/leann_backend.h "sharded indexes", csrc/shard.hip): the corpus partitioned into contiguous position
     ranges, one sub-index per shard; a search = per-shard traversal + gather of the per-shard lists + merge kernel.  One process
