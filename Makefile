@@ -30,6 +30,8 @@ $(CSRC)/scan_bf16.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-op
 $(CSRC)/scan_bits.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 # scan_mx4.hip's scores come off the block-scaled matrix cores and its codes are integer arithmetic on f32 bits: the same
 $(CSRC)/scan_mx4.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# scan_pq.hip's scores are integer sums of table entries gathered from LDS; its f32 steps are pq_dist's single difference-form chains: the same
+$(CSRC)/scan_pq.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(CSRC)/libleann_hip.so: $(HIP_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HIP_OBJS)

@@ -975,6 +975,65 @@ int leann_mx4_rows_search_refined_batch(const leann_mx4_rows *b, const leann_exa
                                         size_t fetch_k, const uint8_t *allow /* shared bitmap or NULL */, uint64_t *keys, float *dists,
                                         uint32_t *counts);
 
+/* ---- PQ rows: 8-bit product-quantised exhaustive search with LDS lookup tables (additive; csrc/scan_pq.hip) -----------
+ * One byte per dsub columns: the index of the nearest of 256 centroids of that sub-space, 96 B per 768-d row at dsub = 8 and 192 B at
+ * dsub = 4.  The rows are screened exhaustively by an asymmetric-distance scan — per-query tables of 16-bit inner products, gathered
+ * from LDS by the rows' code bytes —, the exact distances restored by the rerank of "refining results on exact rows".  An object of its
+ * own beside the handles; every existing entry point behaves exactly as before.
+ *
+ * Definition.  dsub is 4 or 8; M = ceil(dims / dsub) sub-spaces; sub-vector m of a vector is its columns m dsub .. m dsub + dsub - 1.
+ * Columns at or behind dims count as 0 in rows, queries and codebooks.  Codebooks C [M][256][dsub] are f32 and finite, the caller's
+ * or the trainer's (step 5).  A row or query element that is not finite counts as 0 in steps 1, 4 and 5.
+ *   1. Row codes.  code[i][m] = the c minimising sum_j (x_imj - C_mcj)^2, ties to the lower c; the sum is taken in f32 in this
+ *      difference form, never expanded, so every computed distance is within a relative (dsub + 3) 2^-23 of the true one whatever the
+ *      order or fusing.  leann_pq_rows_export returns [n x pitch] bytes, pitch = 16 ceil(M / 16), padding bytes 0; the object's own
+ *      device layout differs.  leann_pq_encode computes the same on the host, no device: the reference the encode kernel is held to.
+ *   2. Query tables.  L[m][c] = sum_j q_mj C_mcj accumulated in float64 with j ascending (every product is exact there), rounded once
+ *      to f32.  If an element of q or an L is not finite the query has no tables: its count is 0 and its answer all tail.  Otherwise
+ *      E = max(exponent field of max |L| as f32, 1) and w[m][c] = rne((double)L[m][c] 2^(140 - E)), an int16 with |w| <= 2^14.
+ *      leann_pq_query_lut is the host reference, out [M x 256]; for a query without tables it zeroes out, words the last error "...
+ *      has no tables" and returns 1.
+ *   3. Score.  t_i = sum_m w[m][code[i][m]] in int32: exact in any order, |t_i| <= 2^14 * 1024 = 2^24, so (float)t_i is exact for
+ *      every supported width.  The scale is one per query and does not change a query's ranking.
+ *   4. Candidates, refined search, limits, refusals, empty object, stream semantics: steps 4 and 5 and the limits paragraph of
+ *      "sign-bit rows" word for word.  Ties go to the lower position; the tail is UINT64_MAX / -inf for scores and the rerank's +inf
+ *      for distances; 1 <= top_k <= fetch_k <= 1024, dims in [1, 4096] (M <= 1024), n < 2^32 - 1; d_allow is NULL or ONE device
+ *      bitmap of ceil(n / 8) bytes shared by the batch.
+ *   5. Trainer.  n >= 256 sample rows; the caller subsamples, the library does not.  Centroid c of sub-space m starts as sub-vector m
+ *      of row floor(c n / 256).  One iteration assigns every row by step 1, then sets each centroid that has members to
+ *      (float)(S / count), S the float64 sum of its members in row order; a centroid without members keeps its value.  iters = 0
+ *      returns the initial centroids.  The result is the same bytes on every run.  codebooks_out [M][256][dsub] is a host array.
+ * codebooks is a HOST array in every call, copied into the object (columns at or behind dims zeroed: leann_pq_rows_codebooks returns
+ * that copy).  Without a device only leann_pq_encode and leann_pq_query_lut work. */
+typedef struct leann_pq_rows leann_pq_rows;
+int leann_pq_train_device(const float *d_rows, size_t n, size_t dims, size_t ld, size_t dsub, size_t iters, int device,
+                          float *codebooks_out /* host */);
+int leann_pq_train(const float *rows, size_t n, size_t dims, size_t dsub, size_t iters, int device, float *codebooks_out);
+int leann_pq_encode(const float *rows, size_t n, size_t dims, size_t dsub, const float *codebooks, uint8_t *out /* [n x pitch] */);
+int leann_pq_query_lut(const float *q, size_t dims, size_t dsub, const float *codebooks, int16_t *out /* [M x 256] */);
+int leann_pq_rows_from_device(const float *d_rows, size_t n, size_t dims, size_t ld, const float *codebooks, size_t dsub, int device,
+                              uint64_t key_offset, leann_pq_rows **out);
+int leann_pq_rows_from_host(const float *rows, size_t n, size_t dims, const float *codebooks, size_t dsub, int device, uint64_t key_offset,
+                            leann_pq_rows **out);
+size_t leann_pq_rows_len(const leann_pq_rows *b);
+size_t leann_pq_rows_dims(const leann_pq_rows *b);
+size_t leann_pq_rows_dsub(const leann_pq_rows *b);
+size_t leann_pq_rows_pitch(const leann_pq_rows *b); /* bytes per exported row */
+int leann_pq_rows_export(const leann_pq_rows *b, uint8_t *out /* [n x pitch], host */);
+int leann_pq_rows_codebooks(const leann_pq_rows *b, float *out /* [M][256][dsub], host */);
+void leann_pq_rows_close(leann_pq_rows *b);
+int leann_pq_rows_search_batch_device(const leann_pq_rows *b, const float *d_queries, size_t nq, size_t fetch_k,
+                                      const uint8_t *d_allow /* shared bitmap or NULL */, uint64_t *d_keys, float *d_scores,
+                                      uint32_t *d_counts, void *stream);
+int leann_pq_rows_search_batch(const leann_pq_rows *b, const float *queries, size_t nq, size_t fetch_k,
+                               const uint8_t *allow /* shared bitmap or NULL */, uint64_t *keys, float *scores, uint32_t *counts);
+int leann_pq_rows_search_refined_batch_device(const leann_pq_rows *b, const leann_exact_rows *r, const float *d_queries, size_t nq,
+                                              size_t top_k, size_t fetch_k, const uint8_t *d_allow /* shared bitmap or NULL */,
+                                              uint64_t *d_keys, float *d_dists, uint32_t *d_counts, void *stream);
+int leann_pq_rows_search_refined_batch(const leann_pq_rows *b, const leann_exact_rows *r, const float *queries, size_t nq, size_t top_k,
+                                       size_t fetch_k, const uint8_t *allow /* shared bitmap or NULL */, uint64_t *keys, float *dists,
+                                       uint32_t *counts);
+
 /* ---- sharded indexes (the reference has no counterpart: IndexSearcher owns one Box<dyn BackendSearcher>,
  * src/index/searcher.rs:68) --------------------------------------------------------------------------------------------------
  * One process, G devices: the composite handle leann_backend_open returns for a device list, or built here from rows / handles.

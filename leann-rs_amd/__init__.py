@@ -5,8 +5,8 @@ reference's index layer + `leann search` CLI), and this thin ctypes mirror used 
 """
 from ._native import LeannError, lib, device_count, LIB_PATH  # noqa: F401
 from .backend import (BackendBuilder, BackendSearcher, BackendType, BitRows, DiskAnnSearcher, ExactRows,  # noqa: F401
-                      HnswSearcher, Mx4Rows, RowType, ShardedIndex, pack_mx4, pack_sign_bits, quantize_i8, quantize_query_i8,
-                      quantize_query_mx8, rerank_batch_device, round_bf16, split_query_bf16)
+                      HnswSearcher, Mx4Rows, PqRows, RowType, ShardedIndex, pack_mx4, pack_sign_bits, pq_encode, pq_query_lut, pq_train,
+                      quantize_i8, quantize_query_i8, quantize_query_mx8, rerank_batch_device, round_bf16, split_query_bf16)
 from .bm25 import Bm25Index  # noqa: F401
 from .device import DeviceArray, sync  # noqa: F401
 from .metadata import MetaColumns, parse_filter  # noqa: F401

@@ -183,6 +183,23 @@ SIGNATURES = {
     "leann_mx4_rows_search_batch": (C.c_int, [vp, f32p, C.c_size_t, C.c_size_t, u8p, u64p, f32p, u32p]),
     "leann_mx4_rows_search_refined_batch_device": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp]),
     "leann_mx4_rows_search_refined_batch": (C.c_int, [vp, vp, f32p, C.c_size_t, C.c_size_t, C.c_size_t, u8p, u64p, f32p, u32p]),
+    "leann_pq_train_device": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, f32p]),
+    "leann_pq_train": (C.c_int, [f32p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, f32p]),
+    "leann_pq_encode": (C.c_int, [f32p, C.c_size_t, C.c_size_t, C.c_size_t, f32p, u8p]),
+    "leann_pq_query_lut": (C.c_int, [f32p, C.c_size_t, C.c_size_t, f32p, C.POINTER(C.c_int16)]),
+    "leann_pq_rows_from_device": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, f32p, C.c_size_t, C.c_int, C.c_uint64, C.POINTER(vp)]),
+    "leann_pq_rows_from_host": (C.c_int, [f32p, C.c_size_t, C.c_size_t, f32p, C.c_size_t, C.c_int, C.c_uint64, C.POINTER(vp)]),
+    "leann_pq_rows_len": (C.c_size_t, [vp]),
+    "leann_pq_rows_dims": (C.c_size_t, [vp]),
+    "leann_pq_rows_dsub": (C.c_size_t, [vp]),
+    "leann_pq_rows_pitch": (C.c_size_t, [vp]),
+    "leann_pq_rows_export": (C.c_int, [vp, u8p]),
+    "leann_pq_rows_codebooks": (C.c_int, [vp, f32p]),
+    "leann_pq_rows_close": (None, [vp]),
+    "leann_pq_rows_search_batch_device": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp]),
+    "leann_pq_rows_search_batch": (C.c_int, [vp, f32p, C.c_size_t, C.c_size_t, u8p, u64p, f32p, u32p]),
+    "leann_pq_rows_search_refined_batch_device": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp]),
+    "leann_pq_rows_search_refined_batch": (C.c_int, [vp, vp, f32p, C.c_size_t, C.c_size_t, C.c_size_t, u8p, u64p, f32p, u32p]),
     "leann_synth_rows_device": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                          C.c_float, C.c_uint32, C.c_uint64, C.c_uint64, vp, vp]),
     "leann_scan_topk_device": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_size_t,

@@ -1026,6 +1026,148 @@ class Mx4Rows:
             pass
 
 
+def _pq_args(who, x, dsub, codebooks):
+    """rows or one query [.. x dims] and codebooks [M x 256 x dsub] as contiguous f32; shapes that do not belong together are refused"""
+    x, cb = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(codebooks, np.float32)
+    dims = x.shape[-1] if x.ndim else 0
+    if dsub not in (4, 8) or dims < 1:
+        raise LeannError(1, f"{who}: dsub = {dsub} is neither 4 nor 8" if dims >= 1 else f"{who}: dims = 0")
+    if cb.shape != (-(-dims // dsub), 256, dsub):
+        raise LeannError(1, f"{who}: codebooks must be [{-(-dims // dsub)} x 256 x {dsub}] for dims = {dims}")
+    return x, cb
+
+
+def pq_train(x, dsub=8, iters=8, device=0):
+    """codebooks f32 [M x 256 x dsub] for the sample rows x [n >= 256 x dims] (include/leann_backend.h "PQ rows", step 5): Lloyd
+    iterations on the device from the centroids floor(c n / 256), the same bytes on every run; the caller subsamples"""
+    x = np.ascontiguousarray(x, np.float32)
+    if x.ndim != 2 or x.shape[1] < 1 or dsub not in (4, 8):
+        raise LeannError(1, "pq_train: rows must be [n x dims] and dsub 4 or 8")
+    cb = np.zeros((-(-x.shape[1] // dsub), 256, dsub), np.float32)
+    N.check(N.lib().leann_pq_train(_p(x, f32p), x.shape[0], x.shape[1], dsub, iters, device, _p(cb, f32p)))
+    return cb
+
+
+def pq_encode(x, codebooks, dsub=8):
+    """f32 rows [n x dims] -> codes uint8 [n x 16 ceil(M / 16)], the nearest centroid of every sub-space, ties to the lower index: the
+    library's own reference, on the host"""
+    x, cb = _pq_args("pq_encode", x, dsub, codebooks)
+    if x.ndim != 2:
+        raise LeannError(1, "pq_encode: rows must be [n x dims]")
+    out = np.zeros((x.shape[0], 16 * -(-cb.shape[0] // 16)), np.uint8)
+    N.check(N.lib().leann_pq_encode(_p(x, f32p), x.shape[0], x.shape[1], dsub, _p(cb, f32p), _p(out, u8p)))
+    return out
+
+
+def pq_query_lut(q, codebooks, dsub=8):
+    """one f32 query -> (tables int16 [M x 256], has_tables): the host reference of the PQ search's query tables; a query with an
+    element or a table entry that is not finite has none (tables zero, has_tables False)"""
+    q, cb = _pq_args("pq_query_lut", np.asarray(q, np.float32).reshape(-1), dsub, codebooks)
+    out = np.zeros((cb.shape[0], 256), np.int16)
+    rc = N.lib().leann_pq_query_lut(_p(q, f32p), q.shape[0], dsub, _p(cb, f32p), _p(out, C.POINTER(C.c_int16)))
+    if rc == 1 and b"has no tables" in N.lib().leann_last_error():
+        return out, False
+    N.check(rc)
+    return out, True
+
+
+class PqRows:
+    """PQ rows (leann_pq_rows, include/leann_backend.h "PQ rows"): one byte per dsub columns of f32 rows under trained codebooks,
+    searched exhaustively by a table gather from LDS; search_refined_batch restores exact distances on an ExactRows"""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def from_host(cls, X, codebooks, dsub=8, device=0, key_offset=0):
+        X, cb = _pq_args("PqRows.from_host", X, dsub, codebooks)
+        if X.ndim != 2:
+            raise LeannError(1, "PqRows.from_host: rows must be [n x dims]")
+        h = C.c_void_p()
+        N.check(N.lib().leann_pq_rows_from_host(_p(X, f32p), X.shape[0], X.shape[1], _p(cb, f32p), dsub, device, key_offset, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_device(cls, d_rows_ptr, n, dims, ld, codebooks, dsub=8, device=0, key_offset=0):
+        """f32 rows [n x ld] on `device`, a device pointer (int): only read, they need not outlive this object; codebooks on the host"""
+        cb = np.ascontiguousarray(codebooks, np.float32)
+        h = C.c_void_p()
+        N.check(N.lib().leann_pq_rows_from_device(d_rows_ptr, n, dims, ld, _p(cb, f32p), dsub, device, key_offset, C.byref(h)))
+        return cls(h)
+
+    def len(self):
+        return int(N.lib().leann_pq_rows_len(self._h))
+
+    __len__ = len
+
+    def dims(self):
+        return int(N.lib().leann_pq_rows_dims(self._h))
+
+    def dsub(self):
+        return int(N.lib().leann_pq_rows_dsub(self._h))
+
+    def pitch(self):
+        return int(N.lib().leann_pq_rows_pitch(self._h))
+
+    def export(self):
+        """the codes as uint8 [n x pitch], exactly pq_encode's layout"""
+        out = np.zeros((self.len(), self.pitch()), np.uint8)
+        N.check(N.lib().leann_pq_rows_export(self._h, _p(out, u8p)))
+        return out
+
+    def codebooks(self):
+        """the object's copy of the codebooks, f32 [M x 256 x dsub], columns at or behind dims zero"""
+        out = np.zeros((-(-self.dims() // self.dsub()), 256, self.dsub()), np.float32)
+        N.check(N.lib().leann_pq_rows_codebooks(self._h, _p(out, f32p)))
+        return out
+
+    _host_args = BitRows._host_args
+
+    def search_batch(self, queries, fetch_k, allow=None):
+        """the fetch_k allowed rows with the largest int32 table sum per query, ties to the lower position: (keys, scores, counts);
+        the tail is UINT64_MAX / -inf.  allow: None or ONE bitmap [ceil(len/8)] for the batch."""
+        Q, allow = self._host_args(queries, allow)
+        nq = Q.shape[0]
+        keys = np.full((nq, max(fetch_k, 1)), np.iinfo(np.uint64).max, np.uint64)
+        scores = np.full((nq, max(fetch_k, 1)), -np.inf, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        N.check(N.lib().leann_pq_rows_search_batch(self._h, _p(Q, f32p), nq, fetch_k, _p(allow, u8p), _p(keys, u64p), _p(scores, f32p),
+                                                   _p(counts, u32p)))
+        return keys, scores, counts
+
+    def search_batch_device(self, d_queries, nq, fetch_k, d_keys, d_scores, d_counts, d_allow=None, stream=None):
+        """the same with device pointers (ints); synchronises `stream` before it returns"""
+        N.check(N.lib().leann_pq_rows_search_batch_device(self._h, d_queries, nq, fetch_k, d_allow, d_keys, d_scores, d_counts, stream))
+
+    def search_refined_batch(self, exact_rows, queries, top_k, fetch_k, allow=None):
+        """search_batch's candidates scored again on the exact rows of an ExactRows: the best top_k by the f32 distance"""
+        Q, allow = self._host_args(queries, allow)
+        nq = Q.shape[0]
+        keys = np.full((nq, max(top_k, 1)), np.iinfo(np.uint64).max, np.uint64)
+        dists = np.full((nq, max(top_k, 1)), np.inf, np.float32)
+        counts = np.zeros(nq, np.uint32)
+        N.check(N.lib().leann_pq_rows_search_refined_batch(self._h, exact_rows._h if exact_rows is not None else None, _p(Q, f32p), nq,
+                                                           top_k, fetch_k, _p(allow, u8p), _p(keys, u64p), _p(dists, f32p),
+                                                           _p(counts, u32p)))
+        return keys, dists, counts
+
+    def search_refined_batch_device(self, exact_rows, d_queries, nq, top_k, fetch_k, d_keys, d_dists, d_counts, d_allow=None, stream=None):
+        """the same with device pointers (ints); synchronises `stream` before it returns"""
+        N.check(N.lib().leann_pq_rows_search_refined_batch_device(self._h, exact_rows._h if exact_rows is not None else None, d_queries,
+                                                                  nq, top_k, fetch_k, d_allow, d_keys, d_dists, d_counts, stream))
+
+    def close(self):
+        if self._h:
+            N.lib().leann_pq_rows_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ShardedIndex:
     """leann_sharded (include/leann_backend.h "sharded indexes", csrc/shard.hip): the corpus partitioned into contiguous position
     ranges, one sub-index per shard; a search = per-shard traversal + gather of the per-shard lists + merge kernel.  One process
